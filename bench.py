@@ -12,9 +12,13 @@ rescue.  Per pass:
   * boundary 1: one bpsw_matesw_group call per group of 4 096 pairs (the call behind native/jni_mate_sw.c:534 /
     MemSamPe.scala:2091-2092): speculation, H2D, the SW kernel, D2H, the sequential replay and sort/dedup, host arrays out.
 The calls are made by T = 32 native host threads (csrc/bpsw_feeder.cpp), one context each, the way T Spark task threads of one
-executor call the JNI symbols; inputs are generated up front and live in host memory, outputs land in host memory, and a
-sample of the TIMED outputs is compared with the oracle after the timed region ("verified").
-`breakdown.device_resident` keeps the round-1 figure (inputs already in HBM, asynchronous device entries, kernels only).
+executor call the JNI symbols; inputs are generated up front and live in host memory, outputs land in host memory.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full adds what lies outside the timed region: a
+sample of the TIMED outputs compared with the oracle ("verified") and the GCUPS / VALU figures priced on it, the breakdowns
+(`breakdown.device_resident` keeps the round-1 figure: inputs already in HBM, asynchronous device entries, kernels only) and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy (dump_outputs); with the same
+arguments the inputs are the same on every run.
 
 N>1: one process per GPU (torch.distributed over RCCL for the barrier and the max-over-ranks only; the path has no
 data-path collective), each rank streams its own shard of pairs ("weak" scaling: Spark partition -> device).
@@ -325,6 +329,58 @@ def verify_sample(W, cfg_no, rank, wires, ext_outs, groups, grp_cnts, grp_regs, 
     return {"ext_tasks": int(n_ext), "rescue_pairs": int(n_pairs), "rescue_jobs": int(n_jobs), "mismatches": 0}, work
 
 
+DUMP_SEED = 20261016          # the sample --dump-outputs writes: the same tasks and groups on every run with the same arguments
+DUMP_EXT_TASKS = 262_144      # extension results sampled (10 float32 each: 10 MB)
+DUMP_REGION_BYTES = 32 << 20  # rescue regions: whole groups of a seeded order while they fit in this
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(out_dir, ext_outs, ntasks, grp_cnts, grp_regs, grp_totals):
+    """What the caller of the timed path receives after the last timed step -- every wire batch's int16[10 n] results and every
+    rescue group's per-read region counts and regions (each step runs the same inputs, so the host buffers hold the last step's
+    outputs) -- as DIR/<name>.npy in float32 / float64, every value exact:
+      extend_results.npy       float32 [k, 10]  the results of a seeded sample of k extension tasks (all of them when fewer)
+      extend_task_index.npy    float64 [k]      which tasks: index into the step's tasks, wire batch after wire batch
+      rescue_counts.npy        float32 [2 G]    regions per read, every group of the step (boundary 1's out_cnt), group after group
+      rescue_regions.npy       float64 [r, 14]  the regions (ALNREG fields in order, `hash` as its high and low 32 bits) of whole
+                                                groups, taken in a seeded order while they fit in 32 MB
+      rescue_region_groups.npy float64 [s, 2]   those groups: (group index, regions)
+    Files of a boundary the workload does not run are not written."""
+    import bpsw_hip
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    arrays = {}
+    n_ext = int(sum(ntasks))
+    if n_ext:
+        idx = np.arange(n_ext) if n_ext <= DUMP_EXT_TASKS else np.sort(rng.choice(n_ext, size=DUMP_EXT_TASKS, replace=False))
+        ext = np.concatenate([o.reshape(-1, 10) for o in ext_outs])
+        arrays["extend_results"] = ext[idx].astype(np.float32)
+        arrays["extend_task_index"] = idx.astype(np.float64)
+    if grp_cnts:
+        arrays["rescue_counts"] = np.concatenate(grp_cnts).astype(np.float32)
+        cols = [f for f in bpsw_hip.ALNREG_DTYPE.names if f != "hash"]
+        pick, nbytes = [], 0
+        for g in rng.permutation(len(grp_cnts)):     # whole groups, in a seeded order, while their capacity (set by the inputs) fits
+            nbytes += len(grp_regs[g]) * 8 * (len(cols) + 2)
+            if pick and nbytes > DUMP_REGION_BYTES:
+                break
+            pick.append(int(g))
+        pick.sort()
+        rows = []
+        for g in pick:
+            r = grp_regs[g][: int(grp_totals[g])]
+            h = r["hash"]
+            rows.append(np.column_stack([r[f].astype(np.float64) for f in cols] + [(h >> np.uint64(32)).astype(np.float64),
+                                                                                  (h & np.uint64(0xFFFFFFFF)).astype(np.float64)]))
+        arrays["rescue_regions"] = np.concatenate(rows) if rows else np.zeros((0, len(cols) + 2))
+        arrays["rescue_region_groups"] = np.array([[g, int(grp_totals[g])] for g in pick], np.float64).reshape(-1, 2)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes, more than {DUMP_BUDGET}")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 CHR21_LEN = 46_709_983   # GRCh38 chr21 (BASELINE.json configs[1..2]): the length of the counter-hash reference of the coordinate batches
 
 
@@ -588,8 +644,15 @@ def stub_main(args, W):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (each one = `passes` passes over the step's distinct inputs)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and figures outside the timed region: the oracle check of a sample of the timed outputs and the GCUPS / "
+                         "VALU figures priced on it, the breakdowns (device-resident entries, coordinate batches, JNI shim, worker2 tail) and the "
+                         "CPU baseline; without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64; a fixed, seeded sample "
+                         "where an output is larger than the budget, 64 MB in all)")
     ap.add_argument("--config", type=int, default=int(os.environ.get("BENCH_CONFIG", "3")), choices=sorted(WORKLOADS),
                     help="SURVEY.md 8(d) workload number (3 = BASELINE.json configs[2], the metric's configuration)")
     ap.add_argument("--threads", type=int, default=int(os.environ.get("BENCH_THREADS", "0")), help="host feeder threads per GPU (0: auto)")
@@ -600,6 +663,8 @@ def main():
                     help="after the timed region, run its items again with the feeder confined to 4 / 8 / 12 / 16 CPUs (host.reads_per_s_vs_cpus measured live; "
                          "without it the line carries the committed sweep of profiles/<tag>_cpu_sweep.json, labelled as such)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     W = dict(WORKLOADS[args.config])
     shrink = max(1, int(os.environ.get("BENCH_SHRINK", "1")))   # rehearsals (tests): 1/k of the batches, groups and passes; the line says so and is not the metric
     if shrink > 1:
@@ -728,10 +793,12 @@ def main():
     reads_per_step = reads_per_pass * passes
     pairs_per_step = reads_per_step // 2 if W["paired"] else 0
     value = whole_job_rate(reads_per_step, args.steps, world, elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ext_outs, ntasks, grp_cnts, grp_regs, grp_totals)
 
     # ---- a sample of the timed outputs against the oracle (outside the timed region; the only use of oracle/ besides cpu_baseline)
     verified, work = verify_sample(W, args.config, rank, wires, ext_outs, groups, grp_cnts, grp_regs, grp_totals,
-                                   np.random.default_rng(1234 + rank), F.ctxs[0]) if rank == 0 else (None, None)
+                                   np.random.default_rng(1234 + rank), F.ctxs[0]) if rank == 0 and args.full else (None, None)
 
     # ---- per-kernel figures from the HIP events the library records on its launch streams during the timed region ----
     ext_launches, sw_launches = int(st["ext_calls"]), int(st["sw_calls"])
@@ -844,7 +911,7 @@ def main():
                 "note": "ceiling = 256 CUs x 4 SIMD-32 x 2.4 GHz (MI355X_MICROARCH.md); rounds 1-2 priced against half of it (SIMD-16)"}
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             extras["device_resident"] = device_resident_breakdown(W, args.config, rank, wires, ntasks, dev, local_rank, reps=max(3, min(args.steps, 10)))
         except Exception as e:  # noqa: BLE001 -- a breakdown line must never cost the bench its JSON
@@ -942,7 +1009,8 @@ def main():
                                    "(H2D, kernels, D2H, speculate/replay, sort/dedup all inside)",
                    "host_threads_per_gpu": n_threads, "numa_node": numa_node, "feeder_cpus": len(share),
                    "hip_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "ranks_seen": ranks_seen, "shrink": shrink,
-                   "parallelism": f"partition->device x{world} (no collective)", "input_generation_s": round(t_gen, 1)},
+                   "parallelism": f"partition->device x{world} (no collective)", "input_generation_s": round(t_gen, 1),
+                   "full": args.full},
         "verified": verified,
         "roofline": {"bound": "hbm", "kernel": dominant, "dominant_by": dominant_by, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic, "traffic_2xfetch_plus_write": traffic_x2,
@@ -996,7 +1064,7 @@ def main():
                               "read once; the rescue inputs that travel are read, written to pinned staging and read over PCIe"},
         "breakdown": extras,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(W, args.config, rank, xtra)
     elif rank == 0:
         out["cpu_baseline"] = None

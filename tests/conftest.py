@@ -83,12 +83,36 @@ def orc():
     return pyoracle.Oracle()
 
 
+@pytest.hookimpl(hookwrapper=True)
+def pytest_runtest_makereport(item, call):
+    rep = (yield).get_result()
+    setattr(item, "rep_" + rep.when, rep)     # (the `ref` fixture records or checks a test's calls only when the test passed)
+
+
 @pytest.fixture(scope="session")
-def ref():
+def _live_ref():
     import pyoracle
-    if not pyoracle.Ref.available():
-        pytest.skip("oracle/_ref/libbwaref.so not built (reference tree absent)")
-    return pyoracle.Ref()
+    return pyoracle.Ref() if pyoracle.Ref.available() and os.environ.get("BPSW_REF_LIVE") != "0" else None
+
+
+@pytest.fixture
+def ref(request, _live_ref):
+    """The reference's own C: live where oracle/_ref was built (and checked against this test's recording when there is one), else the
+    recording of this test's calls under tests/golden/ref_calls (tests/ref_calls.py).  BPSW_REF_LIVE=0 replays even where the build
+    exists; BPSW_REF_RECORD=DIR writes the recordings of the live tests that passed into DIR."""
+    import ref_calls
+    mod = os.path.splitext(os.path.basename(str(request.node.fspath)))[0]
+    path = ref_calls.recording_path(mod, request.node.name)
+    calls = ref_calls.load(path) if os.path.exists(path) else None
+    if _live_ref is None and calls is None:
+        pytest.skip("oracle/_ref/libbwaref.so not built (reference tree absent) and no recording of this test's reference calls")
+    r = ref_calls.RefCalls(_live_ref, calls, f"{mod}::{request.node.name}")
+    yield r
+    rep = getattr(request.node, "rep_call", None)
+    if rep is not None and rep.passed:
+        r.finish()
+        if _live_ref is not None and os.environ.get("BPSW_REF_RECORD"):
+            ref_calls.save(ref_calls.recording_path(mod, request.node.name, os.environ["BPSW_REF_RECORD"]), r.made)
 
 
 @pytest.fixture(scope="session")

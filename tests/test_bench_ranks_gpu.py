@@ -18,7 +18,7 @@ def test_bench_gpus_2_on_one_device():
     env = dict(os.environ, BENCH_FORCE_DEVICE="0", BENCH_BACKEND="gloo", BENCH_SHRINK="16", BENCH_THREADS="8", GPU_MAX_HW_QUEUES="10")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_STUB"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extras",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

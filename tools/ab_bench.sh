@@ -7,7 +7,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done
 shift
 for e in "${envs[@]}"; do
   if [ "$e" = "-" ]; then e=""; fi
-  line=$(env $e python bench.py "$@" --no-cpu-baseline --no-extras 2>/dev/null | tail -1)
+  line=$(env $e python bench.py "$@" --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1)
   echo "$e | $@ | $(python3 -c "
 import json,sys
 d=json.loads(sys.argv[1])

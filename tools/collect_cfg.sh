@@ -6,11 +6,11 @@ tag=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_cfg
 mkdir -p $out
-python3 bench.py --config 2 --steps 6 --warmup 2 --no-cpu-baseline > $out/${tag}_bench_config2.json 2> $out/c2.err
-python3 bench.py --config 5 --steps 6 --warmup 2 > $out/${tag}_bench_config5.json 2> $out/c5.err
+python3 bench.py --config 2 --steps 6 --warmup 2 --full --no-cpu-baseline > $out/${tag}_bench_config2.json 2> $out/c2.err
+python3 bench.py --config 5 --steps 6 --warmup 2 --full > $out/${tag}_bench_config5.json 2> $out/c5.err
 # each boundary of config 5 alone: the GCUPS of each kernel without the other sharing the device
-BENCH_ONLY=ext python3 bench.py --config 5 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $out/${tag}_bench_config5_ext_only.json 2> $out/c5e.err
-BENCH_ONLY=grp python3 bench.py --config 5 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $out/${tag}_bench_config5_grp_only.json 2> $out/c5g.err
+BENCH_ONLY=ext python3 bench.py --config 5 --steps 6 --warmup 2 --full --no-cpu-baseline --no-extras > $out/${tag}_bench_config5_ext_only.json 2> $out/c5e.err
+BENCH_ONLY=grp python3 bench.py --config 5 --steps 6 --warmup 2 --full --no-cpu-baseline --no-extras > $out/${tag}_bench_config5_grp_only.json 2> $out/c5g.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats5 -o b -- python3 bench.py --config 5 --steps 4 --warmup 2 --no-cpu-baseline --no-extras > $out/c5_stats.json 2> $out/c5_stats.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES --output-format csv -d $out/pmc5 -o b -- python3 bench.py --config 5 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $out/c5_pmc.json 2> $out/c5_pmc.err
 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum --output-format csv -d $out/rdreq5 -o b -- python3 bench.py --config 5 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $out/c5_rdreq.err
