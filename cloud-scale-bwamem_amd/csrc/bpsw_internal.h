@@ -163,6 +163,27 @@ double ring_ticks_per_ms(int device, int c_class);
 bool ring_integrity_on();
 void ring_poison(uint32_t* first_word, size_t stride_words, size_t n_records, size_t second_word_offset);
 int ring_check(const uint32_t* first_word, size_t stride_words, size_t n_records, size_t second_word_offset, const char* what);
+// The ring's client: one descriptor (`payload` behind the ring's head, `n_units` units) from publication to verified completion.
+// `done` / `*seq`: the caller's completion record and its sequence counter (bumped here); `*wait_est_ms`: ring_wait's estimate;
+// `recs`: the caller's result block, poisoned before publication and checked after completion.  Caller has set the device.
+struct RingRecords {
+  uint32_t* first_word;
+  size_t stride_words, n_records, second_word_offset;
+  const char* what;
+};
+struct RingRun {
+  enum How {
+    done,       // every record written; span_ms: first unit taken -> last unit finished, on the device's clock
+    launch,     // the ring cannot take the batch, or will never run it: nothing of it has reached a worker, take a launch instead
+    unwritten,  // ring_check failed: records still poisoned after its grace period (rc)
+    failed,     // the submission or the wait failed (rc)
+  } how;
+  int rc;
+  bool submitted;  // the descriptor was accepted: until it completes, a unit may still write into the caller's blocks
+  float span_ms;
+};
+RingRun ring_run(int device, int c_class, int num_cu, const void* payload, size_t payload_bytes, uint32_t n_units, RingDone* done,
+                 uint32_t* seq, double* wait_est_ms, const RingRecords& recs);
 void ring_integrity_stats(uint64_t* checked, uint64_t* faults);
 void ring_pause(int device);   // close the device's open epochs, wait for their kernels, keep the rings locked ...
 void ring_resume(int device);  // ... until here (bpsw_ref_load / unload: a device-wide synchronisation in between)
@@ -448,12 +469,27 @@ struct bpsw_ctx {
 
   bpsw::PinnedBuffer h_stage_in, h_stage_out, h_pre;
   int shortcut_mask = 63;  // bpsw_set_ext_shortcuts
-  std::vector<int> ext_long_tasks, ext_mid_tasks;  // scratch of bpsw_extend_batch: the tasks of the current batch that go to the full kernel / have a flank of 128-255 bases
+  std::vector<int> ext_long_tasks;  // scratch of bpsw_extend_batch: the tasks of the current batch that go to the full kernel
   double wait_est_ms[6] = {0., 0., 0., 0., 0., 0.};  // wait_event / ring_wait: running average of the device-phase waits ([0] extension launches, [1] SW launches, [2] ring copy-in, [3] spare, [4] extension ring, [5] SW ring: a thread that alternates 1 ms launched batches with 0.085 ms ring batches must not nap through the short ones on the long ones' estimate)
-  bool ring_abandoned = false;       // a ring batch of this context ran into the watchdog: a late unit may still write into the pinned blocks, so the context refuses further calls and bpsw_destroy leaks them
+  bool ring_abandoned = false;       // a ring batch of this context ran into the watchdog: a late unit may still write into the pinned blocks, so the context refuses further calls (ContextEntry) and bpsw_destroy leaks them
   uint32_t ring_seq = 0;             // completion values of this context's ring submissions (RingDone at h_pre + 448)
   void* rescue_scratch = nullptr;  // bpsw_rescue.cpp: vectors reused across bpsw_matesw_group calls (freed by rescue_scratch_free)
   bpsw_stats_t stats;
   float last_ext_ms = 0.f, last_sw_ms = 0.f;
   bool have_ext_ev = false, have_sw_ev = false;
 };
+
+namespace bpsw {
+// The prologue of every C-ABI entry that does device work on a context: lock it, refuse it if it gave up a ring batch, set its
+// device, resolve what its asynchronous device entries left pending.  rc: the first failing step's code; the lock is held either way.
+struct ContextEntry {
+  std::unique_lock<std::mutex> lock;
+  int rc = BPSW_OK;
+  explicit ContextEntry(bpsw_ctx* c) : lock(c->mu) {
+    if (c->ring_abandoned) { rc = fail(BPSW_ERR_DEVICE, "this context gave up a ring batch (watchdog / integrity): create a new one"); return; }
+    const hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) { rc = fail(BPSW_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e)); return; }
+    rc = finish_pending(c);
+  }
+};
+}  // namespace bpsw

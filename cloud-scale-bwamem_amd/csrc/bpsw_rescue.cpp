@@ -343,10 +343,8 @@ extern "C" int bpsw_matesw_group(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bps
   if (mode != BPSW_RESCUE_C && mode != BPSW_RESCUE_SCALA) return fail(BPSW_ERR_ARG, "matesw_group: bad mode");
   const int G_ = g->group_size;
   if (G_ < 0) return fail(BPSW_ERR_ARG, "matesw_group: negative group size");
-  std::lock_guard<std::mutex> lock(c->mu);
-  hipError_t he = hipSetDevice(c->device);
-  if (he != hipSuccess) return fail(BPSW_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(he));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
 
   const double t_begin = stat_ms();
   double t_pack = 0., t_replay = 0.;

@@ -375,6 +375,44 @@ void ring_integrity_stats(uint64_t* checked, uint64_t* faults) {
 
 double ring_ticks_per_ms(int device, int c_class) { return 1000.0 * (double)service(device, c_class).ticks_per_us; }
 
+RingRun ring_run(int device, int c_class, int num_cu, const void* payload, size_t payload_bytes, uint32_t n_units, RingDone* done,
+                 uint32_t* seq, double* wait_est_ms, const RingRecords& recs) {
+  RingRun r = {RingRun::failed, BPSW_OK, false, 0.f};
+  if (++*seq == 0) ++*seq;
+  RingDescHead head;
+  memset(&head, 0, sizeof head);
+  head.n_units = n_units;
+  head.done_value = *seq;
+  head.done_ptr = (uint64_t)(uintptr_t)done;
+  RingDesc desc;
+  memset(&desc, 0, sizeof desc);
+  memcpy(desc.w, &head, sizeof head);
+  memcpy(desc.w + sizeof(RingDescHead) / 4, payload, payload_bytes);
+  ring_poison(recs.first_word, recs.stride_words, recs.n_records, recs.second_word_offset);
+  r.rc = ring_submit(device, c_class, num_cu, desc);
+  if (r.rc != BPSW_OK) {
+    if (ring_usable(device, c_class)) return r;
+    // the epoch could not be started (nothing of this batch has reached a worker): this call and the later ones take launches of their own
+    static std::atomic<bool> said[2];
+    const bool ext = c_class == RING_CLASS_EXT;
+    if (!said[ext ? 1 : 0].exchange(true)) {
+      if (ext) fprintf(stderr, "bPSW: the extension ring of device %d failed (%s); small extension batches are launched one by one from here on\n", device, bpsw_last_error());
+      else fprintf(stderr, "bPSW: the submission ring of device %d failed (%s); SW batches are launched one by one from here on\n", device, bpsw_last_error());
+    }
+    r.how = RingRun::launch;
+    return r;
+  }
+  r.submitted = true;
+  r.rc = ring_wait(device, c_class, done, *seq, wait_est_ms);
+  if (r.rc == BPSW_RING_RELAUNCH) { r.how = RingRun::launch; return r; }  // (another thread's epoch launch failed; nobody will run this batch)
+  if (r.rc != BPSW_OK) return r;
+  r.rc = ring_check(recs.first_word, recs.stride_words, recs.n_records, recs.second_word_offset, recs.what);
+  if (r.rc != BPSW_OK) { r.how = RingRun::unwritten; return r; }
+  r.how = RingRun::done;
+  r.span_ms = (float)((double)(done->t_done.load(std::memory_order_relaxed) - done->t_first.load(std::memory_order_relaxed)) / ring_ticks_per_ms(device, c_class));
+  return r;
+}
+
 // Closes the open epochs of a device and waits for their kernels to end; the rings stay locked until ring_resume, so that a
 // device-wide synchronisation in between (bpsw_ref_load / unload) cannot be held up by an epoch other threads keep feeding.
 void ring_pause(int device) {

@@ -549,7 +549,7 @@ static inline int rd32(const uint8_t* b, size_t at) {
 // Validates a wire batch on the host.  *coord: the batch is a coordinate batch (wire format 2: byte 7 of the header is 2, 40-byte
 // records, query flanks only); l_pac is the length of the loaded reference (0: none), needed to check its coordinates.
 static int scan_wire(const uint8_t* wire, size_t bytes, long long l_pac, int* n_out, int* maxq, int* maxr, bool* coord,
-                     std::vector<int>* long_tasks, std::vector<int>* mid_tasks, int* maxr_short, int* n_mid_out) {
+                     std::vector<int>* long_tasks, int* maxr_short, int* n_mid_out) {
   if (!wire || bytes < 32 || (bytes & 3)) return fail(BPSW_ERR_ARG, "extend: wire batch shorter than its header or not word sized");
   const int n = rd32(wire, 8);
   const int fmt = wire[7];
@@ -569,7 +569,6 @@ static int scan_wire(const uint8_t* wire, size_t bytes, long long l_pac, int* n_
   // on its sliding window and may be deferred to the full kernel from the device
   const bool all_long = (int8_t)wire[2] + (int8_t)wire[3] <= 0;
   long_tasks->clear();
-  mid_tasks->clear();
   int mid = 0;
   for (int t = 0; t < n; ++t) {
     const size_t at = 32 + rec_bytes * (size_t)t;
@@ -583,7 +582,7 @@ static int scan_wire(const uint8_t* wire, size_t bytes, long long l_pac, int* n_
     if (rq > mq) mq = rq;
     const bool is_long = all_long || lq > 255 || rq > 255;
     const bool is_mid = !is_long && (lq > 127 || rq > 127);
-    if (is_mid) { ++mid; mid_tasks->push_back(t); }
+    if (is_mid) ++mid;
     if (is_long) long_tasks->push_back(t);
     int task_mr = 0;
     if (co) {
@@ -620,9 +619,8 @@ int bpsw_extend_batch(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_bytes, int
 
 int bpsw_extend_stage(bpsw_ctx_t* c, size_t bytes, uint8_t** buf) {
   if (!c || !buf) return fail(BPSW_ERR_ARG, "extend_stage: null argument");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { int prc = finish_pending(c); if (prc != BPSW_OK) return prc; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   // room for the batch and for the task list the launch plan may stage behind it (at most one int per 32-byte record)
   HIP_TRY(c->h_stage_in.reserve(bytes + bytes / 8 + 4096));
   c->staged_bytes = bytes;
@@ -659,23 +657,17 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
   if (!c) return fail(BPSW_ERR_ARG, "null context");
   int n = 0, mq = 0, mr = 0;
   bool coord = false;
-  std::lock_guard<std::mutex> g(c->mu);
-  if (c->ring_abandoned) return fail(BPSW_ERR_DEVICE, "this context gave up a ring batch (watchdog / integrity): create a new one");
-  HIP_TRY(hipSetDevice(c->device));
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   const uint8_t* d_pac = nullptr;
   long long l_pac = 0;
   RefHold ref_hold;  // a coordinate batch reads the loaded reference: it stays put until the kernel has been waited for
   if (wire && wire_bytes >= 32 && wire[7] == BPSW_WIRE_COORDS) ref_hold = ref_snapshot(c, &d_pac, &l_pac);
   std::vector<int>& long_tasks = c->ext_long_tasks;
   int mr_short = 0;
-  int n_mid = 0;
-  std::vector<int>& mid_tasks = c->ext_mid_tasks;
-  int rc = scan_wire(wire, wire_bytes, l_pac, &n, &mq, &mr, &coord, &long_tasks, &mid_tasks, &mr_short, &n_mid);
+  int n_mid = 0;  // tasks with a flank of 128-255 bases
+  int rc = scan_wire(wire, wire_bytes, l_pac, &n, &mq, &mr, &coord, &long_tasks, &mr_short, &n_mid);
   if (rc != BPSW_OK) return rc;
-  // "mid" tasks (a query flank of 128-255 bases) run on the short kernel like the others; only they can meet a band wider than its
-  // 128-column window, in which case the kernel defers them to the full kernel on the device (bpsw_extend.hip)
-  (void)mid_tasks;
-  const bool any_mid = n_mid > 0;
   // Launch plan: the short kernel over the whole batch (it skips the long tasks: a flank above 255 bases) and the full kernel over
   // the list of long ones plus what the short kernel defers -- or the full kernel alone when most tasks are long or the split is
   // switched off (BPSW_EXT_SPLIT=0)
@@ -688,20 +680,17 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
   // bases leaves it: nothing is deferred on account of a wide band, one build serves every batch, and the full kernel is for what the
   // host lists (flanks above 255 bases).  (Round 4's second build went with the first profiles that showed it idle.)
   const bool expect_full = !use_short || n_long > 0;
-  (void)any_mid;
   // behind the wire bytes: the full kernel's list as [count, task indices...]; the host stages its own entries and the count, the
   // short kernel appends (room for every task)
   const size_t list_off = (wire_bytes + 15) & ~(size_t)15;
   // The deferring short kernel ALWAYS has a list to defer to (round 4 gave it none when no task could be expected to defer, and
   // trapped if one did): a batch without mid tasks posts an empty list like any other, and the full kernel is launched behind it
   // only when it is not (lazy_full below) -- or unconditionally where the late launch is off (classify entry, BPSW_EXT_LAZY_FULL=0).
-  const bool with_list = use_short;
-  const size_t stage_bytes = with_list ? list_off + 4 * (1 + (size_t)n_long) : wire_bytes;
-  const size_t dev_bytes = with_list ? list_off + 4 * (1 + (size_t)n) : wire_bytes;
+  const size_t stage_bytes = use_short ? list_off + 4 * (1 + (size_t)n_long) : wire_bytes;
+  const size_t dev_bytes = use_short ? list_off + 4 * (1 + (size_t)n) : wire_bytes;
   if (!out_view && (!out || out_len < 10 * (size_t)n)) return fail(BPSW_ERR_CAPACITY, "extend: result buffer smaller than 10*n int16");
   if (out_view) *out_view = nullptr;
   if (n == 0) return BPSW_OK;
-  { int prc = finish_pending(c); if (prc != BPSW_OK) return prc; }
   const size_t out_bytes = 20 * (size_t)n;
   // The full kernel behind the short one, when the host has listed nothing for it (no flank above 255 bases) and few tasks could
   // end up on its list at all (2x150 bp reads: the flanks of 128-131 bases): launched only when the short kernel did defer
@@ -709,12 +698,11 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
   // launches the full kernel and waits again.  An empty launch held the stream for 0.1-0.18 ms of a 1.6 ms call
   // (profiles/r03_trace_overlap.txt).  BPSW_EXT_LAZY_FULL=0: always launch it.
   static const bool lazy_on = !(getenv("BPSW_EXT_LAZY_FULL") && atoi(getenv("BPSW_EXT_LAZY_FULL")) == 0);
-  const bool lazy_full = lazy_on && !side_how && use_short && with_list && n_long == 0;
-  const bool use_full = expect_full || (with_list && !lazy_full);
+  const bool lazy_full = lazy_on && !side_how && use_short && n_long == 0;
+  const bool use_full = expect_full || (use_short && !lazy_full);
   const size_t out_post_bytes = out_bytes + (lazy_full ? 4 : 0);
   // (32-byte result slots in the pinned buffer were tried: the 16 + 4 byte stores of a record then cost two write sectors each,
   // more fabric writes than back-to-back 20-byte records that merge in L2, and the host-side gather cost more than the memcpy)
-  bool zc_slots = false;
   HIP_TRY(c->d_wire.reserve(dev_bytes));
   HIP_TRY(c->d_out.reserve(out_post_bytes));
   // The sift kernel in front of the short kernel (bpsw_extend_sift.hip: it examines the tasks whose flanks have at most 127 bases):
@@ -739,13 +727,13 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
   const bool staged = wire == (const uint8_t*)c->h_stage_in.ptr;
   if (staged && stage_bytes > c->h_stage_in.cap) return fail(BPSW_ERR_ARG, "extend_commit: the staged batch is larger than what bpsw_extend_stage was asked for");
   HIP_TRY(c->h_stage_in.reserve(stage_bytes));
-  HIP_TRY(c->h_stage_out.reserve(zc_slots ? 32 * (size_t)n : out_post_bytes));
+  HIP_TRY(c->h_stage_out.reserve(out_post_bytes));
   if (lazy_full) *(volatile int*)((char*)c->h_stage_out.ptr + out_bytes) = 0;
   const double t_in = stat_ms();
   ext_call_mark(c->device);
   struct ExtMark { int d; ~ExtMark() { ext_call_mark(d); } } ext_mark{c->device};
   if (!staged) memcpy(c->h_stage_in.ptr, wire, wire_bytes);
-  if (with_list) {  // rides on the same copy
+  if (use_short) {  // the full kernel's list rides on the same copy
     int* hl = (int*)((char*)c->h_stage_in.ptr + list_off);
     hl[0] = n_long;
     if (n_long) memcpy(hl + 1, long_tasks.data(), 4 * (size_t)n_long);
@@ -768,7 +756,7 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
     // the device --; sixteen callers make 105 k / 68 k / 46 k calls/s against 33 k / 30 k / 26 k, four callers 46 k / 37 k / 22 k against
     // 32 k / 30 k / 22 k: tests/small_call_table.py, profiles/r05_small_calls*.txt)
     static const int ext_ring_max = getenv("BPSW_EXT_RING_MAX_TASKS") ? atoi(getenv("BPSW_EXT_RING_MAX_TASKS")) : 256;
-    const bool eligible = ring_enabled() && ext_ring_on && use_short && n_long == 0 && !use_sift && !side_how && !zc_slots &&
+    const bool eligible = ring_enabled() && ext_ring_on && use_short && n_long == 0 && !use_sift && !side_how &&
                           (zerocopy_mask() & 1) != 0 && mq <= 255 && mr_short <= EXT_RING_RCAP && n <= ext_ring_max;
     if (eligible && ring_usable(c->device, RING_CLASS_EXT)) {
       t_dev0 = stat_ms();
@@ -786,16 +774,7 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
         ring_wire = c->d_wire.ptr;
         copy_first_ms = stat_ms() - t_dev0;
       }
-      RingDesc desc;
-      memset(&desc, 0, sizeof desc);
-      RingDescHead head;
-      memset(&head, 0, sizeof head);
-      RingDone* done = (RingDone*)((char*)c->h_pre.ptr + 448);
-      if (++c->ring_seq == 0) ++c->ring_seq;
       const int per_unit = n <= 2048 ? 1 : 4;  // tasks per ticket: one atomic per task is fine for a few hundred tasks
-      head.n_units = (uint32_t)((n + per_unit - 1) / per_unit);
-      head.done_value = c->ring_seq;
-      head.done_ptr = (uint64_t)(uintptr_t)done;
       ExtRingPayload pl;
       memset(&pl, 0, sizeof pl);
       pl.wire = (uint64_t)(uintptr_t)ring_wire; pl.out = (uint64_t)(uintptr_t)c->h_stage_out.ptr;
@@ -804,38 +783,30 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
       pl.tail_bound = c->ext_sc.tail_bound; pl.certify = c->ext_sc.certify;
       pl.coord = coord ? 1 : 0; pl.pac = (uint64_t)(uintptr_t)(coord ? d_pac : nullptr); pl.l_pac = coord ? l_pac : 0;  // (ref_hold keeps the reference put)
       for (int r = 0; r < 5; ++r) pl.mat_row[r] = c->ext_sc.mat.row[r];
-      memcpy(desc.w, &head, sizeof head);
-      memcpy(desc.w + sizeof(RingDescHead) / 4, &pl, sizeof pl);
-      ring_poison((uint32_t*)c->h_stage_out.ptr, 5, (size_t)n, 4);  // (idx and the width word of every record: the tripwire of bpsw_ring.cpp)
-      int rc = ring_submit(c->device, RING_CLASS_EXT, c->num_cu, desc);
-      if (rc != BPSW_OK && !ring_usable(c->device, RING_CLASS_EXT)) {
-        // the epoch could not be started (nothing of this batch has reached a worker): this call and the later ones take launches of their own
+      // (the tripwire of bpsw_ring.cpp looks at idx and the width word of every record -- also the net under a task the resident kernel
+      // could not finish: it has no defer list, and a record left as it was would otherwise pass for a result)
+      const RingRun run = ring_run(c->device, RING_CLASS_EXT, c->num_cu, &pl, sizeof pl, (uint32_t)((n + per_unit - 1) / per_unit),
+                                   (RingDone*)((char*)c->h_pre.ptr + 448), &c->ring_seq, &c->wait_est_ms[4],
+                                   RingRecords{(uint32_t*)c->h_stage_out.ptr, 5, (size_t)n, 4, "extension"});
+      if (run.how == RingRun::failed) {
+        if (run.submitted) c->ring_abandoned = true;  // (the descriptor still names this context's pinned blocks: see bpsw_destroy)
+        return run.rc;
+      }
+      if (run.how == RingRun::unwritten) {
+        // still missing after ring_check's grace period: not a late write but a task the resident kernel left alone.  The launch path
+        // below has the full kernel behind it and computes the whole batch again into the same block.
         static std::atomic<bool> said{false};
-        if (!said.exchange(true)) fprintf(stderr, "bPSW: the extension ring of device %d failed (%s); small extension batches are launched one by one from here on\n", c->device, bpsw_last_error());
-        copy_first_ms = 0.;
-      } else {
-        if (rc != BPSW_OK) return rc;
-        rc = ring_wait(c->device, RING_CLASS_EXT, done, c->ring_seq, &c->wait_est_ms[4]);
-        if (rc == BPSW_RING_RELAUNCH) { copy_first_ms = 0.; goto ring_left; }  // (another thread's epoch launch failed; nobody will run this batch)
-        if (rc != BPSW_OK) { c->ring_abandoned = true; return rc; }
-        // every record written?  (also the net under a task the resident kernel could not finish -- it has no defer list: a record left
-        // as it was would otherwise pass for a result)
-        rc = ring_check((const uint32_t*)c->h_stage_out.ptr, 5, (size_t)n, 4, "extension");
-        if (rc != BPSW_OK) {
-          // still missing after ring_check's grace period: not a late write but a task the resident kernel left alone.  The launch path
-          // below has the full kernel behind it and computes the whole batch again into the same block.
-          static std::atomic<bool> said{false};
-          if (!said.exchange(true)) fprintf(stderr, "bPSW: an extension batch came back from the ring with unwritten records; it is run again through a launch (%s)\n", bpsw_last_error());
-          copy_first_ms = 0.;
-          goto ring_left;
-        }
-        ring_kernel_ms = (float)((double)(done->t_done.load(std::memory_order_relaxed) - done->t_first.load(std::memory_order_relaxed)) / ring_ticks_per_ms(c->device, RING_CLASS_EXT));
+        if (!said.exchange(true)) fprintf(stderr, "bPSW: an extension batch came back from the ring with unwritten records; it is run again through a launch (%s)\n", bpsw_last_error());
+      }
+      if (run.how == RingRun::done) {
+        ring_kernel_ms = run.span_ms;
         t_dev1 = stat_ms();
         via_ring = true;
         c->stats.ext_ring_calls++;
+      } else {
+        copy_first_ms = 0.;  // the launch path below books its own copy
       }
     }
-  ring_left:;
   }
   if (!via_ring) {
     // The copy of the wire batch.  While rescue batches are in flight on this device (bpsw_sw_runtime.cpp counts them) it is made
@@ -898,7 +869,6 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
     ExtScoring c_sc_full = c->ext_sc;  // what a late launch of the full kernel gets (lazy_full)
     {
       ExtScoring sc = c->ext_sc;
-      if (zc_slots) sc.out_stride = 16;
       if (coord) { sc.pac = d_pac; sc.l_pac = l_pac; }
       c_sc_full = sc;
       if (side_how) {  // diagnostics: the kernel notes per side whether a shortcut or the DP produced the result
@@ -908,7 +878,7 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
       }
       on_dispatch = true;
       int* d_queue = (int*)((char*)c->d_pre.ptr + 128);
-      int* d_list = with_list ? (int*)((char*)c->d_wire.ptr + list_off) : nullptr;
+      int* d_list = use_short ? (int*)((char*)c->d_wire.ptr + list_off) : nullptr;
       if (use_short) {
         KernelEvents kev;
         kev.start = c->ev[1]; kev.stop = (use_full && !lazy_full) ? nullptr : c->ev[2];
@@ -943,8 +913,7 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
         // the call holds its stream for that long)
         // (this is the launch that is NOT late -- the classify entry, BPSW_EXT_LAZY_FULL=0, or tasks the host listed itself: a quarter of
         // the mid tasks sizes it, at least one workgroup; the late launch below is sized by the posted length of the list)
-        const bool may_defer = use_short;
-        const int grid_tasks = !use_short ? n : n_long + (may_defer ? 4 : 0);  // (a wide band defers nothing since round 5: room for the unexpected only)
+        const int grid_tasks = !use_short ? n : n_long + 4;  // (a wide band defers nothing since round 5: room for the unexpected only)
         HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, grid_tasks, k_out, sc, mq, mr, c->num_cu, d_queue, nullptr, s,
                                   nullptr, false, kev, false, use_short ? d_list : nullptr));
       }
@@ -972,14 +941,7 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
     t_dev1 = stat_ms();
     c->stats.ext_wait_ms += lease.wait_ms;
   }
-  if (zc_slots) {  // gather the 20-byte records out of their 32-byte slots
-    const uint8_t* src = (const uint8_t*)c->h_stage_out.ptr;
-    uint8_t* dst = (uint8_t*)out;
-    for (int t = 0; t < n; ++t) {
-      memcpy(dst + 20 * (size_t)t, src + 32 * (size_t)t, 16);
-      memcpy(dst + 20 * (size_t)t + 16, src + 32 * (size_t)t + 16, 4);
-    }
-  } else if (out_view) {
+  if (out_view) {
     *out_view = (const int16_t*)c->h_stage_out.ptr;  // valid until the next call on this context
   } else {
     memcpy(out, c->h_stage_out.ptr, out_bytes);
@@ -1008,10 +970,8 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
 static const int ASYNC_QCAP = 256, ASYNC_RCAP = 4096;
 
 // the synchronous geometry-dependent launch (batches that outgrow the async geometry; the experimental kernels)
-static int ext_device_sync_launch(bpsw_ctx_t* c, const void* d_wire, size_t wire_bytes, int n_tasks, void* d_out, hipStream_t s,
-                                  const ExtPrepass* h_pre, const int* h_counts) {
+static int ext_device_sync_launch(bpsw_ctx_t* c, const void* d_wire, int n_tasks, void* d_out, hipStream_t s, const ExtPrepass* h_pre) {
   HIP_TRY(hipEventRecord(c->ev[4], s));
-  (void)wire_bytes; (void)h_counts;
   HIP_TRY(launch_ext_kernel((const uint32_t*)d_wire, n_tasks, (int16_t*)d_out, c->ext_sc, h_pre->max_qlen, h_pre->max_rlen, c->num_cu,
                             (int*)((char*)c->d_pre.ptr + 128), nullptr, s));
   HIP_TRY(hipEventRecord(c->ev[5], s));
@@ -1037,8 +997,7 @@ int finish_pending_ext(bpsw_ctx_t* c) {
   c->ext_geom_q = std::max(c->ext_geom_q, h_pre->max_qlen);
   c->ext_geom_r = std::max(c->ext_geom_r, h_pre->max_rlen);
   if (h_pre->max_qlen > p.qcap || h_pre->max_rlen > p.rcap) {  // the kernel left the batch untouched: launch it for real
-    int counts[3] = {0, 0, p.n_tasks};
-    int rc = ext_device_sync_launch(c, p.d_wire, p.wire_bytes, p.n_tasks, p.d_out, p.s, h_pre, counts);
+    int rc = ext_device_sync_launch(c, p.d_wire, p.n_tasks, p.d_out, p.s, h_pre);
     if (rc != BPSW_OK) return rc;
     HIP_TRY(hipStreamSynchronize(p.s));
   }
@@ -1054,9 +1013,8 @@ int bpsw_extend_batch_device(bpsw_ctx_t* c, const void* d_wire, size_t wire_byte
       ((uintptr_t)d_wire & 15) || ((uintptr_t)d_out & 3))
     return fail(BPSW_ERR_ARG, "extend_device: bad buffer arguments");
   if (n_tasks == 0) return BPSW_OK;
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { int rc = finish_pending(c); if (rc != BPSW_OK) return rc; }  // the scan buffers of this context are about to be reused
+  ContextEntry entry(c);  // (finish_pending: the scan buffers of this context are about to be reused)
+  if (entry.rc != BPSW_OK) return entry.rc;
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
   HIP_TRY(c->d_ext_lists.reserve(4 * ((size_t)n_tasks + 1) + 16));  // the full kernel's device-side task list (nothing pending: safe to grow)
   ExtPrepass* d_pre = (ExtPrepass*)c->d_pre.ptr;

@@ -1,5 +1,4 @@
 // bpsw_sw_runtime.cpp -- C ABI entry points for the local-SW (mate rescue) jobs.
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -72,7 +71,6 @@ int sw_launches_in_flight(int device) { return g_sw_in_flight[device >= 0 && dev
 void sw_launch_in_flight(int device, int delta) { g_sw_in_flight[device >= 0 && device < 64 ? device : 0].fetch_add(delta, std::memory_order_relaxed); }
 
 int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st, int mq, int mt, bool pac_mode, const int32_t** results) {
-  if (c->ring_abandoned) return fail(BPSW_ERR_DEVICE, "this context gave up a ring batch (watchdog / integrity): create a new one");
   SwScoring sc;
   int rc = make_scoring(opt, xtra, &sc);
   if (rc != BPSW_OK) return rc;
@@ -144,15 +142,6 @@ int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st
       dev.q_pool = dd + st.o_qpool; dev.t_pool = pac_mode ? nullptr : dd + st.o_tpool; dev.packed = (const uint32_t*)(dd + st.o_packed);
       c->stats.sw_h2d_ms += stat_ms() - t_dev0;  // (wall time of the copy as the caller saw it)
     }
-    RingDesc desc;
-    memset(&desc, 0, sizeof desc);
-    RingDescHead head;
-    memset(&head, 0, sizeof head);
-    RingDone* done = (RingDone*)((char*)c->h_pre.ptr + 448);
-    if (++c->ring_seq == 0) ++c->ring_seq;
-    head.n_units = (uint32_t)((n + 1) / 2);
-    head.done_value = c->ring_seq;
-    head.done_ptr = (uint64_t)(uintptr_t)done;
     SwRingPayload pl;
     memset(&pl, 0, sizeof pl);
     pl.packed = (uint64_t)(uintptr_t)dev.packed; pl.q_pool = (uint64_t)(uintptr_t)dev.q_pool; pl.t_pool = (uint64_t)(uintptr_t)dev.t_pool;
@@ -160,37 +149,24 @@ int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st
     pl.n_jobs = n; pl.bias = ring_bias;
     for (int r = 0; r < 5; ++r) pl.mat_row[r] = sc.mat.row[r];
     pl.a = sc.a; pl.b = sc.b; pl.o_del = sc.o_del; pl.e_del = sc.e_del; pl.o_ins = sc.o_ins; pl.e_ins = sc.e_ins; pl.xtra = sc.xtra;
-    memcpy(desc.w, &head, sizeof head);
-    memcpy(desc.w + sizeof(RingDescHead) / 4, &pl, sizeof pl);
-    ring_poison((uint32_t*)k_out, 7, (size_t)n, 6);  // (score and qb of every record: the tripwire of bpsw_ring.cpp)
-    rc = ring_submit(c->device, ring_class, c->num_cu, desc);
-    if (rc != BPSW_OK && !ring_usable(c->device, ring_class)) {
-      // the epoch could not be started (nothing of this batch has reached the device): this call and the later ones take a launch of their own
-      static std::atomic<bool> said{false};
-      if (!said.exchange(true)) fprintf(stderr, "bPSW: the submission ring of device %d failed (%s); SW batches are launched one by one from here on\n", c->device, bpsw_last_error());
-      ring_class = 0;
-      dev.q_pool = d + st.o_qpool; dev.t_pool = pac_mode ? nullptr : d + st.o_tpool; dev.packed = (const uint32_t*)(d + st.o_packed);
-    } else {
-      if (rc != BPSW_OK) return rc;
-      rc = ring_wait(c->device, ring_class, done, c->ring_seq, &c->wait_est_ms[5]);
-      if (rc == BPSW_RING_RELAUNCH) {  // another thread's epoch launch failed while this batch waited to be carried over: nobody will run it
-        ring_class = 0;
-        dev.q_pool = d + st.o_qpool; dev.t_pool = pac_mode ? nullptr : d + st.o_tpool; dev.packed = (const uint32_t*)(d + st.o_packed);
-        goto launch_instead;
-      }
-      if (rc != BPSW_OK) { c->ring_abandoned = true; return rc; }  // (the descriptor still names this context's pinned blocks: see bpsw_destroy)
-      rc = ring_check((const uint32_t*)k_out, 7, (size_t)n, 6, "rescue job");
-      if (rc != BPSW_OK) { c->ring_abandoned = true; return rc; }
-      const float span_ms = (float)((double)(done->t_done.load(std::memory_order_relaxed) - done->t_first.load(std::memory_order_relaxed)) / ring_ticks_per_ms(c->device, ring_class));
+    // (the tripwire of bpsw_ring.cpp looks at the score and qb of every record)
+    const RingRun run = ring_run(c->device, ring_class, c->num_cu, &pl, sizeof pl, (uint32_t)((n + 1) / 2), (RingDone*)((char*)c->h_pre.ptr + 448),
+                                 &c->ring_seq, &c->wait_est_ms[5], RingRecords{(uint32_t*)k_out, 7, (size_t)n, 6, "rescue job"});
+    if (run.how == RingRun::done) {
       c->stats.grp_dev_ms += stat_ms() - t_dev0;
       c->stats.sw_calls++; c->stats.sw_jobs += (uint64_t)n; c->stats.sw_ring_calls++;
-      c->stats.sw_kernel_ms += span_ms;  // first unit taken -> last unit finished, on the device's clock
-      c->last_sw_ms = span_ms;
+      c->stats.sw_kernel_ms += run.span_ms;  // first unit taken -> last unit finished, on the device's clock
+      c->last_sw_ms = run.span_ms;
       c->have_sw_ev = false;
       *results = (const int32_t*)c->h_stage_out.ptr;
       return BPSW_OK;
     }
-  launch_instead:;
+    if (run.how != RingRun::launch) {  // failed, or records unwritten
+      if (run.submitted) c->ring_abandoned = true;  // (the descriptor still names this context's pinned blocks: see bpsw_destroy)
+      return run.rc;
+    }
+    // a launch instead, over the batch where it was staged
+    dev.q_pool = d + st.o_qpool; dev.t_pool = pac_mode ? nullptr : d + st.o_tpool; dev.packed = (const uint32_t*)(d + st.o_packed);
   }
   {
     struct InFlight { int d; explicit InFlight(int dev) : d(dev) { sw_launch_in_flight(d, 1); } ~InFlight() { sw_launch_in_flight(d, -1); } } in_flight(c->device);
@@ -276,9 +252,8 @@ extern "C" {
 
 int bpsw_swalign2_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_sw_jobs_t* jobs, int32_t* out) {
   if (!c || !jobs) return fail(BPSW_ERR_ARG, "swalign: null argument");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   return run_sw_jobs_host(c, opt, jobs, out);
 }
 
@@ -329,14 +304,12 @@ int bpsw_swalign2_batch_device(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_
   if (j->n == 0) return BPSW_OK;
   if (j->n < 0 || !j->q_len || !j->t_len || !j->q_off || !j->t_off || !j->q_rev || !j->q_pool)
     return fail(BPSW_ERR_ARG, "swalign_device: null job arrays");
-  std::lock_guard<std::mutex> g(c->mu);
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   const uint8_t* d_pac = nullptr;
   long long l_pac = 0;
   const RefHold ref_hold = ref_snapshot(c, &d_pac, &l_pac);
   if (!j->t_pool && l_pac <= 0) return fail(BPSW_ERR_ARG, "swalign_device: t_pool is null and no reference is loaded (bpsw_ref_load)");
-  HIP_TRY(hipSetDevice(c->device));
-  rc = finish_pending(c);
-  if (rc != BPSW_OK) return rc;
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
   SwJobsDev dev;
   dev.n = j->n; dev.q_len = j->q_len; dev.t_len = j->t_len; dev.q_off = j->q_off; dev.t_off = j->t_off;
@@ -392,9 +365,8 @@ int bpsw_swalign2_batch_device(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_
 int bpsw_ref_load(bpsw_ctx_t* c, const uint8_t* pac, int64_t l_pac) {
   if (!c || !pac || l_pac < 1) return fail(BPSW_ERR_ARG, "ref_load: null reference or non-positive length");
   if (l_pac > (int64_t)1 << 40) return fail(BPSW_ERR_LIMIT, "ref_load: reference longer than 2^40 bases");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   DeviceRef& r = device_ref(c->device);
   RefWriteHold wr(&r.gate);  // no call may be between its snapshot and its last wait
   std::lock_guard<std::mutex> gr(r.mu);
@@ -411,9 +383,8 @@ int bpsw_ref_load(bpsw_ctx_t* c, const uint8_t* pac, int64_t l_pac) {
 
 int bpsw_ref_unload(bpsw_ctx_t* c) {
   if (!c) return fail(BPSW_ERR_ARG, "null context");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   DeviceRef& r = device_ref(c->device);
   RefWriteHold wr(&r.gate);
   std::lock_guard<std::mutex> gr(r.mu);
@@ -437,13 +408,12 @@ int bpsw_ref_fetch(bpsw_ctx_t* c, int32_t n, const int64_t* beg, const int64_t* 
   if (!c || n < 0 || (n > 0 && (!beg || !end || !out_off || !out_len)) || (out_pool_bytes > 0 && !out_pool))
     return fail(BPSW_ERR_ARG, "ref_fetch: null argument");
   if (n == 0) return BPSW_OK;
-  std::lock_guard<std::mutex> g(c->mu);
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   const uint8_t* d_pac = nullptr;
   long long l_pac = 0;
   const RefHold ref_hold = ref_snapshot(c, &d_pac, &l_pac);
   if (l_pac <= 0) return fail(BPSW_ERR_ARG, "ref_fetch: no reference is loaded (bpsw_ref_load)");
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
   const size_t o_beg = 0, o_end = align16(8 * (size_t)n), o_off = align16(o_end + 8 * (size_t)n);
   const size_t in_total = align16(o_off + 8 * (size_t)n);
   const size_t o_len = 0, o_err = align16(8 * (size_t)n), o_pool = align16(o_err + 16);
@@ -483,13 +453,12 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   if (opt->a < 1 || opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 1 || opt->e_ins < 1)
     return fail(BPSW_ERR_ARG, "chain2aln: scoring must have a >= 1, gap opens >= 0 and gap extensions >= 1");
   if (opt->w < 1 || opt->w > 254) return fail(BPSW_ERR_LIMIT, "chain2aln: band width must be 1..254");
-  std::lock_guard<std::mutex> g(c->mu);
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   const uint8_t* d_pac = nullptr;
   long long l_pac = 0;
   const RefHold ref_hold = ref_snapshot(c, &d_pac, &l_pac);
   if (l_pac <= 0) return fail(BPSW_ERR_ARG, "chain2aln: no reference is loaded (bpsw_ref_load)");
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
 
   // ---- host twin of a table scan: validate, build the prefix arrays the kernel indexes with ----
   std::vector<int32_t> chain_base((size_t)n);
@@ -635,9 +604,8 @@ int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jo
     if ((size_t)(ncol * tl) > mz) mz = (size_t)(ncol * tl);
     if (ql > mq) mq = ql;
   }
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   const size_t o_qlen = 0, o_tlen = align16(4 * (size_t)n), o_w = align16(o_tlen + 4 * (size_t)n);
   const size_t o_qoff = align16(o_w + 4 * (size_t)n), o_toff = align16(o_qoff + 8 * (size_t)n);
   const size_t o_qpool = align16(o_toff + 8 * (size_t)n), o_tpool = align16(o_qpool + j->q_pool_bytes);
@@ -692,7 +660,9 @@ int bpsw_last_kernel_ms(bpsw_ctx_t* c, float* ext_ms, float* sw_ms) {
   if (!c) return fail(BPSW_ERR_ARG, "null context");
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  { int prc = finish_pending(c); if (prc != BPSW_OK) return prc; }  // deferred errors of the asynchronous device entries surface here
+  // (deferred errors of the asynchronous device entries surface here.  A reader: it keeps its plain lock, and a context that gave up a
+  // ring batch -- on which nothing can be pending -- still reports its last times)
+  { int prc = finish_pending(c); if (prc != BPSW_OK) return prc; }
   if (c->have_ext_ev) {
     HIP_TRY(hipEventSynchronize(c->ev[5]));
     HIP_TRY(hipEventElapsedTime(&c->last_ext_ms, c->ev[4], c->ev[5]));

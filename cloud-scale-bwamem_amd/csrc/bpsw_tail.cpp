@@ -604,9 +604,8 @@ void bpsw_tail_opt_default(bpsw_tail_opt_t* t) {  // datatype/MemOptType.scala:4
 
 int bpsw_bns_load(bpsw_ctx_t* c, int32_t n_seqs, const int64_t* offset, const int32_t* len, const char* names) {
   if (!c || n_seqs < 1 || !offset || !len) return fail(BPSW_ERR_ARG, "bns_load: null or empty contig table");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   DeviceRef& r = device_ref(c->device);
   RefWriteHold wr(&r.gate);
   std::lock_guard<std::mutex> gr(r.mu);
@@ -644,9 +643,8 @@ int bpsw_reg2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt
   if (n == 0) return BPSW_OK;
   if (n < 0 || !j->read_len || !j->read_off || !j->read_pool || !j->regs) return fail(BPSW_ERR_ARG, "reg2aln: null job arrays");
   if (j->max_cigar < 1 || j->max_md < 1) return fail(BPSW_ERR_ARG, "reg2aln: max_cigar and max_md must be positive");
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   BnsView bns;
   rc = snapshot_bns(c, &bns);
   if (rc != BPSW_OK) return rc;
@@ -700,9 +698,8 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
     n_regs += (size_t)g->reg_cnt[r];
   }
   if (n_regs && !g->regs) return fail(BPSW_ERR_ARG, "sam_pe: null region array");
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  { const int prc_ = finish_pending(c); if (prc_ != BPSW_OK) return prc_; }
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
   BnsView bns;
   rc = snapshot_bns(c, &bns);
   if (rc != BPSW_OK) return rc;

@@ -10,8 +10,8 @@
 //     completion word stored behind its own s_waitcnt vmcnt(0)                    ->  a release store
 //     h_tail acquire load / descriptor words                                      ->  acquire load
 //     the closing handshake's sequentially consistent stores and loads            ->  seq_cst, as on the host side
-// A "unit" computes a checksum the caller can recompute, into the caller's result block, which the caller poisoned before it
-// published the descriptor (ring_poison / ring_check: the product's own tripwire runs here too).
+// A "unit" computes a checksum the caller can recompute, into the caller's result block.  The callers are the product's own ring
+// client (ring_run), with its tripwire (ring_poison / ring_check).
 //
 // What the run checks: every call of every thread returns, with its own results; nothing is lost across idle closes, used-up rings
 // (capacity 64), pauses (bpsw_ref_load's ring_pause / ring_resume) and both ring classes at once; and the sanitizer saw no race,
@@ -179,36 +179,18 @@ static void own_launch(Caller& c, uint32_t n_units, uint32_t salt) {
 }
 
 static int one_call(Caller& c, int c_class, uint32_t n_units, uint32_t salt) {
-  RingDesc desc;
-  memset(&desc, 0, sizeof desc);
-  RingDescHead head;
-  memset(&head, 0, sizeof head);
-  if (++c.seq == 0) ++c.seq;
-  head.n_units = n_units; head.done_value = c.seq; head.done_ptr = (uint64_t)(uintptr_t)c.done;
   TestPayload pl;
   pl.out = (uint64_t)(uintptr_t)c.out; pl.salt = salt; pl.pad = 0;
-  memcpy(desc.w, &head, sizeof head);
-  memcpy(desc.w + sizeof(RingDescHead) / 4, &pl, sizeof pl);
   if (!ring_usable(0, c_class)) {  // a ring that failed earlier: as sw_stage_run / extend_batch_impl, a launch per batch from here on
     own_launch(c, n_units, salt);
     g_fallback.fetch_add(1);
   } else {
-    ring_poison(c.out, 1, n_units, 0);
-    int rc = ring_submit(0, c_class, 256, desc);
-    if (rc != BPSW_OK && !ring_usable(0, c_class)) {  // this call met the failed epoch launch
+    const RingRun run = ring_run(0, c_class, 256, &pl, sizeof pl, n_units, c.done, &c.seq, &c.est, RingRecords{c.out, 1, n_units, 0, "harness"});
+    if (run.how == RingRun::launch) {  // the call met the failed epoch launch, or another thread's failed while this batch waited to be carried over
       own_launch(c, n_units, salt);
-      g_fallback.fetch_add(1);
-    } else {
-      if (rc != BPSW_OK) return rc;
-      rc = ring_wait(0, c_class, c.done, c.seq, &c.est);
-      if (rc == BPSW_RING_RELAUNCH) {  // another thread's epoch launch failed while this batch waited to be carried over
-        own_launch(c, n_units, salt);
-        g_relaunched.fetch_add(1);
-      } else {
-        if (rc != BPSW_OK) return rc;
-        rc = ring_check(c.out, 1, n_units, 0, "harness");
-        if (rc != BPSW_OK) return rc;
-      }
+      (run.submitted ? g_relaunched : g_fallback).fetch_add(1);
+    } else if (run.how != RingRun::done) {
+      return run.rc;
     }
   }
   for (uint32_t u = 0; u < n_units; ++u)

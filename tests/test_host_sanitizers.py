@@ -99,8 +99,24 @@ if mode in ("sw_drop", "sw_late"):
             assert False, "an abandoned context took another call"
         except bpsw_hip.BpswError as e:
             assert "gave up a ring batch" in str(e)                      # ... and the context takes no further call
+        soa = synth.ext_tasks(48, read_len=150, seed=8801)
+        wire = bpsw_hip.wire_pack(soa)
+        q = np.array([0, 1, 2, 3] * 10, np.uint8)
+        t = np.concatenate([q[:15], [3, 3], q[15:]]).astype(np.uint8)
+        gargs = (bpsw_hip.default_opt(), [len(q)], [len(t)], [20], [0], [0], np.concatenate([q, np.zeros(24, np.uint8)]),
+                 np.concatenate([t, np.zeros(22, np.uint8)]))
+        for call in (lambda cx: cx.extend_batch(wire), lambda cx: cx.global_batch(*gargs)):   # (every entry that does device work refuses it)
+            try:
+                call(c)
+                assert False, "an abandoned context took another call"
+            except bpsw_hip.BpswError as e:
+                assert "gave up a ring batch" in str(e), str(e)
         c2 = bpsw_hip.Context(0)                                         # a new one does
         assert np.array_equal(c2.swalign2_batch(bpsw_hip.default_opt(), XTRA, **jobs), want)
+        assert np.array_equal(np.asarray(c2.extend_batch(wire)).reshape(-1), np.asarray(orc.wire_extend(wire)[0]).reshape(-1))
+        score, ncig, cig = c2.global_batch(*gargs)
+        gs, gc = orc.sw_global(q, t, po.default_mat(), 6, 1, 6, 1, 20)
+        assert score[0] == gs and ncig[0] == len(gc) and np.array_equal(cig[0, : ncig[0]], gc)
     else:
         assert raised is None and np.array_equal(got, want)             # late but whole: counted, reported once, results intact
     print("FAULT_OK", mode, checked, faults)
