@@ -174,11 +174,7 @@ __device__ __forceinline__ void ext_do_task(const int task, const int sifted, co
         int oInsT = oIns, eInsT = eIns;  // opaque copies, as below
         asm volatile("" : "+s"(oInsT), "+s"(eInsT));
         int ov = 0;
-#if BPSW_EXT_ADAPTIVE
         r = sw_extend_adaptive(lane_s, qLen, COORD ? min(rLen, qLen + w + 2) : rLen, NibbleQ{words, qStart}, ts, pl, mat, oDel, eDel, oInsT, eInsT, w, sc.zdrop, sc.zdrop_mode, hInit, amax, &ov);
-#else
-        r = sw_extend_reg_short<true>(lane, qLen, COORD ? min(rLen, qLen + w + 2) : rLen, NibbleQ{words, qStart}, ts, mat, oDel, eDel, oInsT, eInsT, w, sc.zdrop, sc.zdrop_mode, hInit, amax, &ov);
-#endif
         if (uni(ov)) {  // (never since round 5: sw_extend_adaptive holds every band of a flank this kernel takes)
           deferred = true;
           break;
@@ -542,7 +538,7 @@ hipError_t launch_ext_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out
   (void)counter_zeroed;  // the queue head (d_counter[0], [1]) is zero between launches: the kernel's last wave resets it
   // tasks per dequeue: 0 = guided (see the kernel), n > 0 = fixed chunks of n (1 balances a lone launch best)
   static const int chunk = [] { const int v = getenv("BPSW_EXT_CHUNK") ? atoi(getenv("BPSW_EXT_CHUNK")) : 0; return v < 0 ? 0 : (v > 64 ? 64 : v); }();  // 0: guided
-  static const int guide_cap = [] { const int v = getenv("BPSW_EXT_GUIDE_CAP") ? atoi(getenv("BPSW_EXT_GUIDE_CAP")) : 8; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
+  constexpr int guide_cap = 8;
 #define BPSW_EXT_GO(CO, SH)                                                                                                     \
   BPSW_LAUNCH(kev, (ext_kernel<CO, SH>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, d_wire, n_tasks, d_out, sc, qcap, rcap, \
               (int)per_wave, chunk, guide_cap, d_counter, d_task_list, d_pre_check, d_defer, short_qmax, d_sift_flag, d_sift_recs, d_defer_post, d_todo_list, inject_defer)

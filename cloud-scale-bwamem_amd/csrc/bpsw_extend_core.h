@@ -194,27 +194,9 @@ __device__ __forceinline__ int s_first_one(unsigned long long v) {  // -1 when v
   return r;
 }
 
-// Where the wave-uniform row control runs.  Measured on MI355X (tools/microbench_issue.hip, profiles/): a SIMD issues
-// one integer VALU / DPP / v_cmp / v_readlane wave-instruction per ~3.7 cycles and one SALU instruction per ~3.7
-// cycles; mixed streams from several waves reach about one instruction per 2.4 cycles.  Two builds:
-//   BPSW_EXT_VECTOR_CONTROL 1: uniform values kept in VGPRs through an opaque asm (fewer SALU, more VALU instructions)
-//   BPSW_EXT_VECTOR_CONTROL 0: control on the scalar pipe
-// Early in the round the kernel issued 355 M VALU + 200 M SALU (build 1) or 239 M + 323 M (build 0) per 30 k-task batch and
-// both took the same time: the sum was what counted.  After the closed forms and the row-loop work the kernel is at
-// 95 M VALU + 39 M SALU (build 1), the step is bound by its VALU instructions, and build 0 is faster (8 batches in flight
-// 172 -> 176.5 M reads/s, bench step 116.7 -> 118.6): it is the default again.
-#ifndef BPSW_EXT_VECTOR_CONTROL
-#define BPSW_EXT_VECTOR_CONTROL 0
-#endif
-__device__ __forceinline__ int vu(int s) {
-#if BPSW_EXT_VECTOR_CONTROL
-  int v;
-  asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
-  return v;
-#else
-  return s;
-#endif
-}
+// An identity, left from a build that kept the row control in VGPRs.  Its two calls in sw_extend_reg's band update stay: written as
+// plain values there, the same source compiles to differently scheduled code for the kernels that use the sweep.
+__device__ __forceinline__ int vu(int s) { return s; }
 __device__ __forceinline__ bool any_lane(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 constexpr int NEG_A = -(1 << 20);  // "no cell" for the register sweeps: below every score, and NEG_A << 7 does not overflow
 
@@ -260,11 +242,17 @@ __device__ ExtRes sw_extend_reg(const int lane, const int qLen, const int tLen, 
     jE[s] = j * eIns - oeIns;
     c2[s] = (j - 1) * eIns;
   }
-  // SWUtil.scala:118-125 -- wave-uniform state, held in VGPRs (see vu)
-  int mx = vu(h0), max_i = vu(-1), max_j = vu(-1), max_ie = vu(-1), gscore = vu(-1), max_off = vu(0);
-  int beg = vu(0), end = vu(qLen);
-  int h1raw = vu(h0 - oDel);  // h0 - (oDel + eDel*(i+1)) after the decrement below
-  int iv = vu(0);             // vector copy of the row index
+  // SWUtil.scala:118-125 -- wave-uniform state.  Its row control runs on the scalar pipe.  Measured on MI355X
+  // (tools/microbench_issue.hip, profiles/): a SIMD issues one integer VALU / DPP / v_cmp / v_readlane wave-instruction per ~3.7
+  // cycles and one SALU instruction per ~3.7 cycles; mixed streams from several waves reach about one instruction per 2.4 cycles.
+  // Early on, a build that kept these values in VGPRs through an opaque asm issued 355 M VALU + 200 M SALU per 30 k-task batch
+  // against this form's 239 M + 323 M, and both took the same time: the sum was what counted.  After the closed forms and the
+  // row-loop work that build was at 95 M VALU + 39 M SALU, bound by its VALU instructions, and this form is faster (8 batches in
+  // flight 172 -> 176.5 M reads/s, bench step 116.7 -> 118.6).
+  int mx = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0;
+  int beg = 0, end = qLen;
+  int h1raw = h0 - oDel;  // h0 - (oDel + eDel*(i+1)) after the decrement below
+  int iv = 0;             // a copy of the row index
 
   const int i_tail = amax > 0 ? qLen : 0x7fffffff;  // first row the tail bound applies to (one scalar compare per row)
   for (int i = 0; i < tLen; ++i, iv += 1) {
@@ -450,7 +438,7 @@ __device__ ExtRes sw_extend_reg(const int lane, const int qLen, const int tLen, 
 // matches, so a flank always STARTS with an error; at 1 % substitutions about half of all flanks have no second one.
 // Verified against the oracle on 45 894 random flanks (homopolymers, tandem repeats, N, five gap-cost sets, w 2..200,
 // z-drop 0/3/5/100, both parses: 0 differences) and by every parity test, whose batches take this path for ~half the sides.
-// ExtScoring::exact_a / ChainParams::exact_a carry a (0: matrix not of that form, or BPSW_EXT_EXACT=0).
+// ExtScoring::exact_a / ChainParams::exact_a carry a (0: matrix not of that form, or bit 0 of bpsw_set_ext_shortcuts clear).
 __device__ __forceinline__ int mat_score(const MatRows& mat, const int t, const int q) {
   return (int)(int8_t)((mat.row[t] >> (8 * q)) & 0xff);
 }
@@ -1105,10 +1093,7 @@ __device__ ExtRes sw_extend_lean1(const int lane, const int qLen, const int tLen
 // SWExtend on the register path for any qLen <= 255.  Up to 63 columns: one column per lane; up to 127: two per lane; longer
 // flanks: the sliding 128-column window (sw_extend_leanS), started by the slot sweep when the first rows are wider than the
 // window (eh: LDS row for the hand-over, qLen + 2 pairs; without it such calls stay on the slot sweep), and run again on the
-// slot sweep in the rare case that a later row outgrows the window.  BPSW_EXT_SLIDE=0 at compile time: slot sweep only.
-#ifndef BPSW_EXT_SLIDE
-#define BPSW_EXT_SLIDE 1
-#endif
+// slot sweep in the rare case that a later row outgrows the window.
 template <class QC>
 __device__ __forceinline__ ExtRes sw_extend_reg_any(const int lane, const int qLen, const int tLen, const QC& qcode,
                                                     const uint8_t* __restrict__ ts, const MatRows& mat, const int oDel,
@@ -1118,7 +1103,6 @@ __device__ __forceinline__ ExtRes sw_extend_reg_any(const int lane, const int qL
   const int slots = (qLen + 64) >> 6;
   if (slots == 1) return sw_extend_lean1(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax);
   if (slots == 2) return sw_extend_lean2(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax);
-#if BPSW_EXT_SLIDE
   {
     int overflow = 0;
     ExtRes r;
@@ -1135,30 +1119,9 @@ __device__ __forceinline__ ExtRes sw_extend_reg_any(const int lane, const int qL
       if (!overflow) return r;
     }
   }
-#endif
   // the slot sweep from the first row to the last
   if (slots == 3) return sw_extend_reg<3>(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax);
   return sw_extend_reg<4>(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax);
-}
-
-// The sweeps that need few registers: one or two columns per lane and the sliding window, none of which needs an LDS row.
-// ext_kernel<.., SHORT> is built from these alone and fits 48 VGPRs -- eight waves per SIMD instead of five (bpsw_extend.hip).
-constexpr int EXT_SHORT_QMAX = 255;  // the register sweeps' limit; the host may set a launch's limit lower (127: no window, no deferral)
-template <bool WINDOW, class QC>
-__device__ __forceinline__ ExtRes sw_extend_reg_short(const int lane, const int qLen, const int tLen, const QC& qcode,
-                                                      const uint8_t* __restrict__ ts, const MatRows& mat, const int oDel,
-                                                      const int eDel, const int oIns, const int eIns, const int w,
-                                                      const int zdrop, const int zmode, const int h0, const int amax,
-                                                      int* __restrict__ overflow) {
-  if (qLen < 64) return sw_extend_lean1(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax);
-  if (!WINDOW || qLen < 128) return sw_extend_lean2(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax);
-  // longer flanks (the WINDOW build of the kernel admits them up to 255 bases): the sliding window, when row 0's band
-  // [0, min(qLen, w+1)] fits it and as long as no later row outgrows it -- else *overflow = 1 and the task goes to the full kernel
-  if (min(qLen, w + 1) > 127) {
-    *overflow = 1;
-    return ExtRes{0, 0, 0, 0, 0, 0};
-  }
-  return sw_extend_leanS(lane, qLen, tLen, qcode, ts, mat, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax, nullptr, nullptr, overflow);
 }
 
 // Wave-level dequeue: lane 0 alone performs one returning atomic add, the result is broadcast.  Written as

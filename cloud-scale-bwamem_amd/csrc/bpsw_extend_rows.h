@@ -19,22 +19,12 @@
 //   * Every piece derives its per-lane constants from an opaque copy of the lane number at its own entry (rows_opaque, round 5):
 //     hoisted to the top of the kernel they were a dozen VGPRs more than the short kernel's 64 hold.
 // Same arithmetic, same order of evaluation as sw_extend_lean1 / lean2 / leanS (bpsw_extend_core.h), which stay for the full
-// kernel and chain2aln_kernel; BPSW_EXT_ADAPTIVE=0 at build time puts the short kernels back on them.
+// kernel and chain2aln_kernel.
 #pragma once
 #include "bpsw_extend_core.h"
 
 namespace bpsw {
 namespace {
-
-#ifndef BPSW_EXT_ADAPTIVE
-#define BPSW_EXT_ADAPTIVE 1
-#endif
-#ifndef BPSW_EXT_ROWS_FAST
-#define BPSW_EXT_ROWS_FAST 1  // 0: every row of the assembly loops on their general form (A/B runs)
-#endif
-#ifndef BPSW_EXT_ROWS_ASM
-#define BPSW_EXT_ROWS_ASM 1  // 0: the C++ form of the one-column loop everywhere (A/B runs, and the reference the tests compare with)
-#endif
 
 // the call's state between the pieces of the sweep: wave-uniform scalars, and per lane the (H,E) row and the profile
 struct RowState {
@@ -87,7 +77,7 @@ __device__ __forceinline__ void rows_load_profile(RowState& st, const ProfLds& p
 }
 
 // The C++ form of the sweep over a window, COLS columns per lane (1: 64 columns, 2: 128), for at most max_rows rows.  It serves
-// every row the assembly loop declines, every row of the two-column layout, and is the reference the assembly is tested against.
+// every row the assembly loops decline.
 //   ROWS_DONE        the call is over (m == 0, z-drop, the tail-row bound, the last target row)
 //   ROWS_MORE        max_rows rows swept
 //   ROWS_OTHER_MODE  COLS == 1: the next row's band does not fit 64 columns; COLS == 2: it fits ROWS_NARROW columns again
@@ -578,21 +568,11 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
 // anyway.  Measured (one MI355X, 24 contexts of 30 k-task batches, kernels alone): 2x250 bp at 8 % / 2 % 28.35 -> 27.42 ms per round
 // (-3.3 %), configs[4] 2.41 -> 2.53 x 10^7 reads/s; 2x150 bp at 1 % unchanged within the noise (2.28 ms) -- a row's time follows its
 // instruction COUNT (about 2.2 cycles each whatever the kind), and that fell by a twentieth, not by the fifth the vector
-// pipe's share of it did.  BPSW_ROWS_UNIQ=0 builds the old form (tools/build_variant.sh old -DBPSW_ROWS_UNIQ=0 for an A/B).
-#ifndef BPSW_ROWS_UNIQ
-#define BPSW_ROWS_UNIQ 1
-#endif
+// pipe's share of it did.
 // ... unless the band already ends at the query end: `end` never exceeds qLen (a zero cell can pull it back, it then grows by one a row up
 // to qLen again) and qLen - base fits the window, so the run is bounded by its other limits only.  Without this a flank whose band
 // sat near the window's top left the loop every few rows for a dispatcher pass that moved nothing (round 6).
-#ifndef BPSW_ROWS_ATQ
-#define BPSW_ROWS_ATQ 1
-#endif
-#if BPSW_ROWS_ATQ
 #define ROWSF_ROOM_ATQ "s_cmp_eq_u32 %[end], %[qlen]\n\ts_cselect_b32 %[fastend], %[hardend], %[fastend]\n\t"
-#else
-#define ROWSF_ROOM_ATQ
-#endif
 #define ROWS_GSCAN_(V, NOP) \
       "v_max_i32_dpp " V ", " V ", " V " row_shr:1 row_mask:0xf bank_mask:0xf\n\t" NOP \
       "v_max_i32_dpp " V ", " V ", " V " row_shr:2 row_mask:0xf bank_mask:0xf\n\t" NOP \
@@ -600,18 +580,8 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
       "v_max_i32_dpp " V ", " V ", " V " row_shr:8 row_mask:0xf bank_mask:0xf\n\t" NOP \
       "v_max_i32_dpp " V ", " V ", " V " row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" NOP \
       "v_max_i32_dpp " V ", " V ", " V " row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-#if BPSW_ROWS_UNIQ
 // (the maximum so far lives in its plain form, mx -- one v_readlane gives the new one; its key form mxhi = mx << 7 | 127 is made where the
 // key scan's result is compared with it)
-#define ROWSF_TAIL_CMP_MAX "s_cmp_le_i32 %[t1], %[mx]\n\t"
-#define ROWSF_MX_FROM_KEY
-#define ROWSF_MX_OUT(s_mx, s_mxhi) (s_mx)
-#else
-#define ROWSF_TAIL_CMP_MAX "s_lshl_b32 %[t2], %[t1], 7\n\ts_or_b32 %[t2], %[t2], 127\n\ts_cmp_le_i32 %[t2], %[mxhi]\n\t"
-#define ROWSF_MX_FROM_KEY "s_lshr_b32 %[mx], %[mxhi], 7\n\t"
-#define ROWSF_MX_OUT(s_mx, s_mxhi) ((s_mxhi) >> 7)
-#endif
-#if BPSW_ROWS_UNIQ
 #define ROWS1F_KEY_INIT \
       "v_cmp_lt_i32_e64 %[u64], %[mx], %[vA]\n\t"  /* the cells that beat the call's maximum so far (mx: its plain form is the state here) */
 #define ROWS1F_SCANS \
@@ -664,47 +634,10 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
       "s_abs_i32 %[t1], %[t1]\n\t" \
       "s_max_i32 %[moff], %[moff], %[t1]\n\t" \
       "s_branch L_ftrim" SFX "_%=\n\t"
-#else
-#define ROWS1F_KEY_INIT \
-      "v_lshl_or_b32 %[vK], %[vA], 7, %[vLane]\n\t"  /* a << 7 | column */
-#define ROWS1F_SCANS \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:2 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:2 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:4 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:4 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-      "s_nop 1\n\t" \
-      "v_mov_b32_dpp %[vPp], %[vG] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"  /* exclusive prefix of g */ \
-      "v_readlane_b32 %[mkey], %[vK], 63\n\t"
-#define ROWS1F_DECIDE(SFX) \
-      "s_cmp_gt_i32 %[mkey], %[mxhi]\n\t"  /* m > max                              SWUtil.scala:187-193 */ \
-      "s_cbranch_scc0 L_fnoimp" SFX "_%=\n\t" \
-      "s_or_b32 %[mxhi], %[mkey], 127\n\t" \
-      "s_mov_b32 %[maxi], %[i]\n\t" \
-      "s_and_b32 %[mj], %[mkey], 127\n\t" \
-      "s_add_i32 %[maxj], %[mj], %[base]\n\t" \
-      "s_sub_i32 %[t1], %[maxj], %[i]\n\t" \
-      "s_abs_i32 %[t1], %[t1]\n\t" \
-      "s_max_i32 %[moff], %[moff], %[t1]\n\t"
-#define ROWS1F_OUTOFLINE(SFX)
-#endif
 
 // ---- the same for the two-column loop (ROWS2F_TEXT): the cells that beat the maximum so far are two ballots (even columns, odd columns);
 // their counts, and the column of the one cell when there is one, are scalar work that fills the wait states between the DPP steps of
 // the one scan that is left
-#if BPSW_ROWS_UNIQ
 #define ROWS2F_KEY_AND_SCANS(H1STEP) \
       "v_cmp_lt_i32_e64 %[u64], %[mx], %[vA0]\n\t"  /* the even / odd cells that beat the call's maximum so far */ \
       "v_cmp_lt_i32 vcc, %[mx], %[vA1]\n\t" \
@@ -778,53 +711,13 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
       "s_abs_i32 %[t1], %[t1]\n\t" \
       "s_max_i32 %[moff], %[moff], %[t1]\n\t" \
       "s_branch L_g2trim" SFX "_%=\n\t"
-#else
-#define ROWS2F_KEY_AND_SCANS(H1STEP) \
-      "v_lshl_or_b32 %[vK], %[vA0], 7, %[vL2]\n\t" \
-      "v_lshl_or_b32 %[vS0], %[vA1], 7, %[vL2p1]\n\t" \
-      "v_max_i32 %[vG], %[vG], %[vG0]\n\t"  /* the lane's two columns folded */ \
-      "v_max_i32 %[vK], %[vK], %[vS0]\n\t"  /* a << 7 | column: row maximum and its LAST column */ \
-      H1STEP \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:2 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:2 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:4 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:4 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-      "s_nop 0\n\t" \
-      "v_max_i32_dpp %[vG], %[vG], %[vG] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-      "v_max_i32_dpp %[vK], %[vK], %[vK] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-      "s_nop 1\n\t" \
-      "v_mov_b32_dpp %[vPp], %[vG] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"  /* prefix over the columns of the lanes below */ \
-      "v_readlane_b32 %[mkey], %[vK], 63\n\t"
-#define ROWS2F_DECIDE(SFX) \
-      "s_cmp_gt_i32 %[mkey], %[mxhi]\n\t"  /* m > max                              SWUtil.scala:187-193 */ \
-      "s_cbranch_scc0 L_g2noimp" SFX "_%=\n\t" \
-      "s_or_b32 %[mxhi], %[mkey], 127\n\t" \
-      "s_mov_b32 %[maxi], %[i]\n\t" \
-      "s_and_b32 %[mj], %[mkey], 127\n\t" \
-      "s_add_i32 %[maxj], %[mj], %[base]\n\t" \
-      "s_sub_i32 %[t1], %[maxj], %[i]\n\t" \
-      "s_abs_i32 %[t1], %[t1]\n\t" \
-      "s_max_i32 %[moff], %[moff], %[t1]\n\t"
-#define ROWS2F_OUTOFLINE(SFX)
-#endif
 #define ROWSF_TAILTEST(SFX) \
       /* a row at or past the query end: tail_row_bound -- U = max(u0 - i eDel, qa); the call is over once U <= max and U < gscore */ \
-      /* (in the loop's own forms: U << 7 | 127 <= mxhi; (U + 1) << 16 <= gskey) */ \
+      /* (in the loop's own forms: U <= mx; (U + 1) << 16 <= gskey) */ \
       "s_mul_i32 %[t1], %[i], %[edel]\n\t" \
       "s_sub_i32 %[t1], %[u0], %[t1]\n\t" \
       "s_max_i32 %[t1], %[t1], %[qa]\n\t" \
-      ROWSF_TAIL_CMP_MAX \
+      "s_cmp_le_i32 %[t1], %[mx]\n\t" \
       "s_cbranch_scc0 L_ttgo" SFX "_%=\n\t" \
       "s_add_i32 %[t1], %[t1], 1\n\t" \
       "s_lshl_b32 %[t1], %[t1], 16\n\t" \
@@ -856,7 +749,7 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
       "s_sub_i32 %[t2], %[end], %[base]\n\t" \
       "v_readlane_b32 %[t1], %[vS], %[t2]\n\t"  /* lane end - base: H(i, qLen-1) */ \
       "s_max_i32 %[gskey], %[gskey], %[t1]\n\t"
-// The second body of a fast loop (round 6, BPSW_ROWS_ATQ): rows whose band ENDS AT THE QUERY END and is last row's (LIVE) or last row's
+// The second body of a fast loop (round 6): rows whose band ENDS AT THE QUERY END and is last row's (LIVE) or last row's
 // moved up by one lane (DEAD) -- three rows in four of a 2x150 bp batch.  Such a row is only ever entered from a row that has just
 // established end == qLen, so it needs neither the test in front of the gscore step nor the one that decides whether `end` grows:
 // four instructions fewer.  Everything out of line (the key scan, the z-drop tests, the trimming on a zero cell) is shared with the
@@ -1062,22 +955,11 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
                "s_cbranch_scc1 L_fbodyq" SFX "_%=\n\t" \
                "s_branch L_fbound" SFX "_%=\n\t")
 #define ROWSF_TAILMIN "s_min_i32 %[hardend], %[hardend], %[itail]\n\t"
-#ifndef BPSW_ROWS_ATQ
-#define BPSW_ROWS_ATQ 1
-#endif
-#if BPSW_ROWS_ATQ
 #define ROWS1F_ALL \
   ROWS1F_LIVE_("_l", "_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_fbound_lt_%=\n\t", "", "L_fbodyq", ROWS1F_LIVE_QBODY("_l")) \
   ROWS1F_DEAD_("_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_fbound_dt_%=\n\t", "", "L_fshq", ROWS1F_DEAD_QBODY("_d")) \
   ROWS1F_LIVE_("_lt", "_dt", "", "", ROWSF_TAILTEST("_lt"), "L_fbody", "") \
   ROWS1F_DEAD_("_dt", "", "", ROWSF_TAILTEST("_dt"), "L_fsh", "")
-#else
-#define ROWS1F_ALL \
-  ROWS1F_LIVE_("_l", "_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_fbound_lt_%=\n\t", "", "L_fbody", "") \
-  ROWS1F_DEAD_("_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_fbound_dt_%=\n\t", "", "L_fsh", "") \
-  ROWS1F_LIVE_("_lt", "_dt", "", "", ROWSF_TAILTEST("_lt"), "L_fbody", "") \
-  ROWS1F_DEAD_("_dt", "", "", ROWSF_TAILTEST("_dt"), "L_fsh", "")
-#endif
 // all the instantiations in one statement (two statements under a branch make the compiler route the scalar state through VGPRs):
 // sel 0 = the general loop (ROWS1_TEXT, with or without the tail-row test), 1 = the fast loop in its LIVE phase, 2 = DEAD.
 // Every read-write operand is early-clobber: an input that happens to hold the same value (end and qLen on row 0) must not share
@@ -1101,13 +983,11 @@ __device__ __forceinline__ int rows_cpp4(RowState& st, Row4& q, const int lane_a
       "s_branch L_end_%=\n\t" \
       ROWS1F_ALL \
       "L_ftotail_%=:\n\t"  /* the rows at and past the query end: the general loop with the tail-row test, in its own form of the state */ \
-      ROWSF_MX_FROM_KEY \
       "s_ashr_i32 %[gs], %[gskey], 16\n\t" \
       "s_sext_i32_i16 %[maxie], %[gskey]\n\t" \
       "s_mov_b32 %[form], 0\n\t" \
       "s_branch L_row_t_%=\n\t" \
       "L_ftogen_%=:\n\t"  /* the left clamp may bind from here on: the general loop */ \
-      ROWSF_MX_FROM_KEY \
       "s_ashr_i32 %[gs], %[gskey], 16\n\t" \
       "s_sext_i32_i16 %[maxie], %[gskey]\n\t" \
       "s_mov_b32 %[form], 0\n\t" \
@@ -1168,7 +1048,7 @@ __device__ __forceinline__ int rows1_asm(RowState& st, const int lane_arg, const
   st.H0 = vH; st.E0 = vE; st.plo0 = vP; st.base = s_base;
   st.i = s_i; st.beg = s_beg; st.end = s_end; st.h1raw = s_h1raw; st.max_i = s_maxi; st.max_j = s_maxj; st.max_off = s_moff;
   if (s_form) {  // the statement ended in the fast loop: its forms of max and (gscore, max_ie)
-    st.mx = ROWSF_MX_OUT(s_mx, s_mxhi); st.gscore = s_gskey >> 16; st.max_ie = (int)(short)(s_gskey & 0xffff);
+    st.mx = s_mx; st.gscore = s_gskey >> 16; st.max_ie = (int)(short)(s_gskey & 0xffff);
   } else {
     st.mx = s_mx; st.max_ie = s_maxie; st.gscore = s_gs;
   }
@@ -1649,19 +1529,11 @@ __device__ __forceinline__ int rows1_asm(RowState& st, const int lane_arg, const
               "v_mov_b32_dpp %[vH0], %[vA1] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t" \
               "v_mov_b32 %[vH1], %[vA0]\n\t", \
               "s_add_i32 %[beg], %[beg], 1\n\t", "s_add_i32 %[t3], %[beg], 1\n\t", "", "", "", "", TAIL_MIN, TAIL_SWITCH, TAILTOP, "")
-#if BPSW_ROWS_ATQ
 #define ROWS2F_ALL \
   ROWS2F_LIVE_("_l", "_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_g2bound_lt_%=\n\t", "", "L_g2bodyq", ROWS2F_LIVE_QBODY("_l", "_lq")) \
   ROWS2F_DEAD_("_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_g2bound_dt_%=\n\t", "") \
   ROWS2F_LIVE_("_lt", "_dt", "", "", ROWSF_TAILTEST("_lt2"), "L_g2body", "") \
   ROWS2F_DEAD_("_dt", "", "", ROWSF_TAILTEST("_dt2"))
-#else
-#define ROWS2F_ALL \
-  ROWS2F_LIVE_("_l", "_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_g2bound_lt_%=\n\t", "", "L_g2body", "") \
-  ROWS2F_DEAD_("_d", ROWSF_TAILMIN, "s_cmp_ge_i32 %[i], %[itail]\n\ts_cbranch_scc1 L_g2bound_dt_%=\n\t", "") \
-  ROWS2F_LIVE_("_lt", "_dt", "", "", ROWSF_TAILTEST("_lt2"), "L_g2body", "") \
-  ROWS2F_DEAD_("_dt", "", "", ROWSF_TAILTEST("_dt2"))
-#endif
 // all the instantiations in one statement, as ROWS1_ASM: sel 0 = the general loop, 1 = the fast loop in its LIVE phase, 2 = DEAD
 #define ROWS2_ASM \
   asm volatile( \
@@ -1682,13 +1554,11 @@ __device__ __forceinline__ int rows1_asm(RowState& st, const int lane_arg, const
       "s_branch L_end_%=\n\t" \
       ROWS2F_ALL \
       "L_ftotail_%=:\n\t"  /* the rows at and past the query end: the general loop with the tail-row test, in its own form of the state */ \
-      ROWSF_MX_FROM_KEY \
       "s_ashr_i32 %[gs], %[gskey], 16\n\t" \
       "s_sext_i32_i16 %[maxie], %[gskey]\n\t" \
       "s_mov_b32 %[form], 0\n\t" \
       "s_branch L_row_t_%=\n\t" \
       "L_ftogen_%=:\n\t"  /* the left clamp may bind from here on: the general loop */ \
-      ROWSF_MX_FROM_KEY \
       "s_ashr_i32 %[gs], %[gskey], 16\n\t" \
       "s_sext_i32_i16 %[maxie], %[gskey]\n\t" \
       "s_mov_b32 %[form], 0\n\t" \
@@ -1747,7 +1617,7 @@ __device__ __forceinline__ int rows2_asm(RowState& st, const int lane_arg, const
   st.H0 = vH0; st.E0 = vE0; st.H1 = vH1; st.E1 = vE1; st.plo0 = vP0; st.plo1 = vP1; st.base = s_base;
   st.i = s_i; st.beg = s_beg; st.end = s_end; st.h1raw = s_h1raw; st.max_i = s_maxi; st.max_j = s_maxj; st.max_off = s_moff;
   if (s_form) {
-    st.mx = ROWSF_MX_OUT(s_mx, s_mxhi); st.gscore = s_gskey >> 16; st.max_ie = (int)(short)(s_gskey & 0xffff);
+    st.mx = s_mx; st.gscore = s_gskey >> 16; st.max_ie = (int)(short)(s_gskey & 0xffff);
   } else {
     st.mx = s_mx; st.max_ie = s_maxie; st.gscore = s_gs;
   }
@@ -1808,9 +1678,6 @@ __device__ ExtRes sw_extend_adaptive(const int lane, const int qLen, const int t
                                      const ProfLds& pl, const MatRows& mat, const int oDel, const int eDel, const int oIns, const int eIns, const int w,
                                      const int zdrop, const int zmode, const int h0, const int amax, int* __restrict__ overflow) {
   const int oeIns = oIns + eIns, oeDel = oDel + eDel;
-#if defined(BPSW_DIAG_SKIP) && BPSW_DIAG_SKIP == 1  // instruction-count experiments only: the call returns before any setup
-  return ExtRes{h0, 0, 0, 0, 0, 0};
-#endif
   RowState st;
   st.i = 0; st.beg = 0; st.end = qLen; st.h1raw = h0 - oDel;
   st.mx = h0; st.max_i = -1; st.max_j = -1; st.max_ie = -1; st.gscore = -1; st.max_off = 0;  // SWUtil.scala:118-125
@@ -1851,13 +1718,9 @@ __device__ ExtRes sw_extend_adaptive(const int lane, const int qLen, const int t
   int vTS = 0, ts_chunk = -1;
   unsigned long long n_rows = 0ull;  // the N rows of the target chunk in vTS
   const unsigned ts_addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) const uint8_t*)ts);  // for the loops' own chunk reload
-#if defined(BPSW_DIAG_SKIP) && BPSW_DIAG_SKIP == 2  // ... after the setup, before the first row
-  return ExtRes{h0 + st.H0 * 0, 0, 0, 0, 0, 0};
-#endif
   for (;;) {
     int r;
     if (cols == 1) {
-#if BPSW_EXT_ROWS_ASM
       if (st.i >= tLen) break;
       r = ROWS_SLOW;
       if (const int row_end = rows_asm_end(st.i, tLen, i_tail, ts, lane, &vTS, &ts_chunk, &n_rows); row_end > st.i) {
@@ -1869,13 +1732,12 @@ __device__ ExtRes sw_extend_adaptive(const int lane, const int qLen, const int t
         const bool live = st.i < i_h1z;
         // (the tail rows' bound U <= u0, qa must fit the loops' 16-bit forms of gscore)
         const bool tail = st.i >= i_tail;
-        const int sel = uni((BPSW_EXT_ROWS_FAST && st.beg + w + 1 > st.i && (!tail || (u0 < 30000 && qa < 30000))) ? (live ? 1 : 2) + (tail ? 2 : 0) : 0);
+        const int sel = uni((st.beg + w + 1 > st.i && (!tail || (u0 < 30000 && qa < 30000))) ? (live ? 1 : 2) + (tail ? 2 : 0) : 0);
         r = rows1_asm(st, lane, qLen, (sel == 0 && !tail) ? smin2(row_end, i_tail) : row_end, vTS, w, eDel, oeDel, oeIns, eIns, zdrop, zmode, i_tail, u0, qa, st.i >= i_tail, sel, tLen, i_h1z, ts_addr, pl.addr);
         if (r == ROWS_MORE) continue;
       }
       if (r == ROWS_SLOW)
-#endif
-        r = rows_cpp<1>(st, lane, qLen, tLen, pl, ts, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax, BPSW_EXT_ROWS_ASM ? 1 : 0x7fffffff);
+        r = rows_cpp<1>(st, lane, qLen, tLen, pl, ts, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax, 1);
       if (r == ROWS_OTHER_MODE) {  // the band outgrew 64 columns: two columns per lane, window at the band's left end
         const int nb = st.beg & ~1;
         if (st.end - nb > 127) { *overflow = 1; return ExtRes{0, 0, 0, 0, 0, 0}; }
@@ -1889,7 +1751,6 @@ __device__ ExtRes sw_extend_adaptive(const int lane, const int qLen, const int t
         continue;
       }
     } else {
-#if BPSW_EXT_ROWS_ASM
       if (st.i >= tLen) break;
       r = ROWS_SLOW;
       if (const int row_end = rows_asm_end(st.i, tLen, i_tail, ts, lane, &vTS, &ts_chunk, &n_rows); row_end > st.i) {
@@ -1898,13 +1759,12 @@ __device__ ExtRes sw_extend_adaptive(const int lane, const int qLen, const int t
         const bool live = st.i < i_h1z;
         // (the tail rows' bound U <= u0, qa must fit the loops' 16-bit forms of gscore)
         const bool tail = st.i >= i_tail;
-        const int sel = uni((BPSW_EXT_ROWS_FAST && st.beg + w + 1 > st.i && (!tail || (u0 < 30000 && qa < 30000))) ? (live ? 1 : 2) + (tail ? 2 : 0) : 0);
+        const int sel = uni((st.beg + w + 1 > st.i && (!tail || (u0 < 30000 && qa < 30000))) ? (live ? 1 : 2) + (tail ? 2 : 0) : 0);
         r = rows2_asm(st, lane, qLen, (sel == 0 && !tail) ? smin2(row_end, i_tail) : row_end, vTS, w, eDel, oeDel, oeIns, eIns, zdrop, zmode, i_tail, u0, qa, st.i >= i_tail, sel, tLen, i_h1z, ts_addr, pl.addr);
         if (r == ROWS_MORE) continue;
       }
       if (r == ROWS_SLOW)
-#endif
-        r = rows_cpp<2>(st, lane, qLen, tLen, pl, ts, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax, BPSW_EXT_ROWS_ASM ? 1 : 0x7fffffff);
+        r = rows_cpp<2>(st, lane, qLen, tLen, pl, ts, oDel, eDel, oIns, eIns, w, zdrop, zmode, h0, amax, 1);
       if (r == ROWS_OVERFLOW) {
         // the band outgrew 128 columns: four columns per lane (round 4 gave the task up here: *overflow).  New column nb + 4 lane + c
         // sits in old lane d + 2 lane + (c >> 1), slot c & 1, with d = (nb - base) / 2

@@ -55,10 +55,8 @@ struct ExtScoring {
   const uint8_t* pac;
   long long l_pac;
 };
-bool certify_enabled();
-int certify_level(const int8_t mat[25]);  // 0 off, 1 single-gap certificate, 2 also the two-gap-open extension
-bool tail_bound_enabled();  // BPSW_EXT_TAIL=0 disables (A/B runs)
-// a > 0 if mat[c][c] == a for the four bases and every other entry is < a; else 0.  BPSW_EXT_EXACT=0 disables.
+int certify_level(const int8_t mat[25]);  // 1 single-gap certificate, 2 also the two-gap-open extension, 3 also flank_start_gap_form
+// a > 0 if mat[c][c] == a for the four bases and every other entry is < a; else 0.
 int exact_match_score(const int8_t mat[25]);
 void apply_shortcuts(int mask, const int8_t mat[25], int* exact_a, int* certify, int* tail_bound);  // bpsw_set_ext_shortcuts
 
@@ -404,7 +402,7 @@ int sw_launches_in_flight(int device);
 void sw_launch_in_flight(int device, int delta);
 double wait_est_update(double est, double took_ms, int polls, bool napped);  // the next estimate of a kind of wait
 bool wait_naps(double est_ms);                                       // whether wait_nap sleeps at all for this estimate
-void wait_nap(double est_ms);                                        // the sleep before the first look (BPSW_WAIT_MODE, bpsw_runtime.cpp)
+void wait_nap(double est_ms);                                        // the sleep before the first look (bpsw_runtime.cpp)
 void wait_poll_pause(int polls, double waited_ms, double est_ms);    // between two looks
 hipError_t wait_event(bpsw_ctx* c, hipEvent_t ev, int kind);  // kind 0: extension call, 1: SW call (separate duration estimates)
 int zerocopy_mask();  // BPSW_ZEROCOPY, see bpsw_runtime.cpp

@@ -356,7 +356,6 @@ extern "C" int bpsw_matesw_group(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bps
   // loaded on the context; their lengths follow bnsGetSeq (win_len)
   GR.pac_mode = g->ref_pool == nullptr;
   const bool rescue_on = (opt->flag & 0x20) == 0;  // MEM_F_NO_RESCUE, native/bwamem.h:18
-  static const bool lean = !(getenv("BPSW_RESCUE_LEAN") && atoi(getenv("BPSW_RESCUE_LEAN")) == 0);  // 0: speculate every anchor (A/B)
 
   // ---- 1. one pass: prefix sums, validation, speculation against the initial lists -----------------------------------
   // (a third of a call's CPU time in round 4, and the calls' CPU time is what bounds the bench step since the rescue kernel is
@@ -427,7 +426,7 @@ extern "C" int bpsw_matesw_group(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bps
           // its result is in, the replay asks for (a second, small round: only when that first rescue failed or landed elsewhere) --
           // instead of computing them all and dropping 9 % of the jobs unused (bench step: 467.8 -> 427.3 jobs per group, no
           // second round at all; tests/test_rescue_gpu.py forces one with decoy anchors)
-          if (lean && emitted) break;
+          if (emitted) break;
           int skip[4];
           skip_flags(GR, a, minit, (size_t)n_mate, skip);
           if (skip[0] + skip[1] + skip[2] + skip[3] != 4) {
@@ -497,11 +496,9 @@ extern "C" int bpsw_matesw_group(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bps
           if (g->ref_off[w.x] < 0 || (uint64_t)(g->ref_off[w.x] + len) > g->ref_pool_bytes)
             return fail(BPSW_ERR_ARG, "matesw_group: window outside ref_pool");
           tbytes += align16((size_t)len);
-#ifndef BPSW_PACK_NO_PREFETCH
           // (the window's bytes are copied further down, from wherever the caller's pool has them: ask for its lines now)
           const uint8_t* wp = g->ref_pool + g->ref_off[w.x];
           for (int64_t o = 0; o < len; o += 64) __builtin_prefetch(wp + o);
-#endif
         }
         mt = std::max(mt, (int)len);
       }
@@ -552,7 +549,6 @@ extern "C" int bpsw_matesw_group(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bps
     }
     // ---- 3. replay the pairs that had a job ------------------------------------------------------------------------
     const double t_r0 = stat_ms();
-#ifndef BPSW_REPLAY_NO_PREFETCH
     // (the thread has slept through the device phase and other threads have had its core: the touched pairs' region records and their
     // anchors' window rows are cold again.  Ask for the next pairs' lines while one is replayed.)
     const auto prefetch_pair = [&](const size_t tj) {
@@ -566,11 +562,8 @@ extern "C" int bpsw_matesw_group(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bps
       }
     };
     for (size_t tj = 0; tj < nt && tj < 8; ++tj) prefetch_pair(tj);
-#endif
     for (size_t ti = 0; ti < nt; ++ti) {
-#ifndef BPSW_REPLAY_NO_PREFETCH
       if (ti + 8 < nt) prefetch_pair(ti + 8);
-#endif
       if (S.done[ti]) continue;
       const int k = S.touched[ti];
       if (!replay_pair(GR, k, ti, S.v, S.want)) continue;

@@ -171,10 +171,7 @@ __device__ inline bool ring_next_unit(const RingArgs& A, const int lane, RingWor
       __hip_atomic_fetch_add(&A.D->diag_claim_ticks, W.diag_t_claim - t_pub, __ATOMIC_RELAXED, RING_DEV);
     }
 #endif
-#ifndef BPSW_RING_ACQ
-#define BPSW_RING_ACQ 1
-#endif
-    if (BPSW_RING_ACQ) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // nothing this CU's vector cache holds of an earlier batch's staging block
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // nothing this CU's vector cache holds of an earlier batch's staging block
     return true;
   }
 }

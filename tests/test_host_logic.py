@@ -119,7 +119,7 @@ def test_wait_estimate_is_not_poisoned_by_an_outlier():
     assert est <= 0.75 * work + 0.25 * (3 * work + 0.2) + 1e-9
     overslept, calls = 0.0, 0
     while naps(est):
-        nap = 0.7 * est - 0.06               # wait_nap's sleep (BPSW_WAIT_MODE=0)
+        nap = 0.7 * est - 0.06               # wait_nap's sleep
         overslept += max(nap - work, 0.0)
         est = upd(est, max(nap, work), 0 if nap >= work else 2, 1)
         calls += 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds an experimental variant of libbPSW_hip.so with extra compiler flags:
-#   tools/build_variant.sh m2 -DBPSW_EXT_VECTOR_CONTROL=2   ->  cloud-scale-bwamem_amd/lib_exp/libbPSW_hip_m2.so
+#   tools/build_variant.sh waves -DBPSW_DIAG_WAVES   ->  cloud-scale-bwamem_amd/lib_exp/libbPSW_hip_waves.so
 # and run anything against it with BPSW_LIB=<that path>.
 set -e
 name=$1; shift
