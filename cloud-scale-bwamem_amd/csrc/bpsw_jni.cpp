@@ -56,6 +56,24 @@ void clear_pending(JNIEnv* env) {
   if (jni::ExceptionCheck(env)) jni::ExceptionClear(env);
 }
 
+void throw_runtime(JNIEnv* env, const std::string& msg) {
+  clear_pending(env);
+  jclass rte = jni::FindClass(env, "java/lang/RuntimeException");
+  if (rte) jni::ThrowNew(env, rte, msg.c_str());
+}
+
+// The body of every Java_* entry: no C++ exception may unwind into the JVM (std::bad_alloc of a scratch vector, ...), so one
+// becomes the RuntimeException "bPSW: <entry>: <what>" and the entry returns `fallback`.
+template <class R, class Body>
+inline R jni_entry(JNIEnv* env, const char* entry, R fallback, Body body) {
+  try {
+    return body();
+  } catch (const std::exception& e) {
+    throw_runtime(env, std::string("bPSW: ") + entry + ": " + e.what());
+    return fallback;
+  }
+}
+
 // Spark partition -> device (north_star: "Spark-partition -> device index").  The partition id is not in
 // either JNI signature; org.apache.spark.TaskContext.get().partitionId() is reachable through JNIEnv.  The class and the two
 // method IDs are resolved once per process (a global reference keeps the class, and with it the IDs, alive).
@@ -95,6 +113,7 @@ int spark_partition_id(JNIEnv* env) {
   return (int)id;
 }
 
+// nullptr: no context could be made; the RuntimeException "bPSW: no usable HIP device: ..." is pending
 bpsw_ctx_t* thread_context(JNIEnv* env) {
   const int part = spark_partition_id(env);
   const int want = bpsw_device_for_partition(part);  // entry (partition mod count) of BPSW_DEVICES; -1 without a TaskContext
@@ -103,9 +122,28 @@ bpsw_ctx_t* thread_context(JNIEnv* env) {
   if (t_ctx.ctx && (want < 0 || want == t_ctx.device)) return t_ctx.ctx;
   if (t_ctx.ctx) { bpsw_destroy(t_ctx.ctx); t_ctx.ctx = nullptr; }
   // want < 0: no TaskContext (harness) -> bpsw_create spreads threads round-robin over BPSW_DEVICES
-  if (bpsw_create(want, &t_ctx.ctx) != BPSW_OK) return nullptr;
+  if (bpsw_create(want, &t_ctx.ctx) != BPSW_OK) {
+    throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error());
+    return nullptr;
+  }
   t_ctx.device = bpsw_device_of(t_ctx.ctx);
   return t_ctx.ctx;
+}
+
+// load(ctx) on a context of its own on every device, since any task thread may land on any device (partition -> device).  The number
+// of devices loaded; when one fails, the RuntimeException "bPSW: <entry>: ..." is pending.
+template <class Load>
+jint load_on_every_device(JNIEnv* env, const char* entry, Load load) {
+  const int ndev = bpsw_device_count();
+  if (ndev <= 0) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return 0; }
+  for (int d = 0; d < ndev; ++d) {
+    bpsw_ctx_t* c = nullptr;
+    int rc = bpsw_create(d, &c);
+    if (rc == BPSW_OK) rc = load(c);
+    if (c) bpsw_destroy(c);
+    if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: ") + entry + ": " + bpsw_last_error()); return d; }
+  }
+  return ndev;
 }
 
 double now_us() {
@@ -118,16 +156,6 @@ struct ShimTimes { double in_us, call_us, out_us, units; };
 thread_local ShimTimes t_times = {0, 0, 0, 0};
 thread_local int t_mate_path = 0;  // what the last mateSWJNI on this thread did: 1 the lazy path, 2 the eager one (bpsw_jni_last_mate_path, for the tests)
 
-void throw_runtime(JNIEnv* env, const std::string& msg) {
-  clear_pending(env);
-  jclass rte = jni::FindClass(env, "java/lang/RuntimeException");
-  if (rte) jni::ThrowNew(env, rte, msg.c_str());
-}
-
-struct OptIds {
-  jfieldID a, b, oDel, eDel, oIns, eIns, penUnpaired, penClip5, penClip3, w, zdrop, T, flag, minSeedLen, maxIns,
-      maxMatesw, maskLevelRedun, mat;
-};
 struct RegIds {
   jfieldID rBeg, rEnd, qBeg, qEnd, score, trueScore, sub, csub, subNum, width, seedCov, secondary, hash;
 };
@@ -231,14 +259,21 @@ struct BytePool {
     if (pad) memset(grow(pad), 0, pad);
   }
 };
-// What a mateSWJNI call builds for bpsw_matesw_group, kept per thread and reused: a call of 4 096 pairs moves ~10 MB through these,
-// and allocating (and zero-filling) them afresh on every call was a measurable part of the shim.
+// What a mateSWJNI / mateSWFlatJNI call builds for bpsw_matesw_group, kept per thread and reused: a call of 4 096 pairs moves ~10 MB
+// through these, and allocating (and zero-filling) them afresh on every call was a measurable part of the shim.
 struct MateScratch {
-  std::vector<int32_t> seq_len, reg_cnt, ref_cnt, out_cnt, tmp_cnt;
-  std::vector<int64_t> seq_off, at, base, ref_rb, ref_re, ref_len, ref_off;
-  std::vector<long> where;
-  std::vector<bpsw_alnreg_t> regs, tmp, out;
+  // the group (all paths) and what bpsw_matesw_group returns
+  std::vector<int32_t> seq_len, reg_cnt, ref_cnt, out_cnt;
+  std::vector<int64_t> seq_off, ref_rb, ref_re, ref_len, ref_off;
+  std::vector<bpsw_alnreg_t> regs, out;
   BytePool seq_pool, ref_pool;
+  // the eager walk: regions in arrival order and the end of each, the next slot of each end in regs, each end's first window row
+  std::vector<bpsw_alnreg_t> arrived;
+  std::vector<long> where;
+  std::vector<int64_t> at, base;
+  // mateSWFlatJNI: regLongs and regInts as they came, the long[] it returns
+  std::vector<int64_t> reg_longs, result;
+  std::vector<int32_t> reg_ints;
 };
 thread_local MateScratch t_ms;
 
@@ -251,29 +286,6 @@ void read_bytes(JNIEnv* env, jbyteArray arr, BytePool& pool, int64_t* off, int32
   *len = n;
   pool.pad16();
 }
-
-
-// ---- mateSWJNI without the object walk over pairs that need nothing (round 5) -------------------------------------------------------
-// The reference's contract hands over every region, every mate and every rescue window of a group as objects (native/jni_mate_sw.c:
-// 239-518), and 96 % of a 4 096-pair call through this shim was reading and rebuilding them -- while nine pairs in ten are properly
-// paired, need no SW at all and come back exactly as they went in.  So: (1) one light pass over MateSWType[] reads what the skip test
-// needs of a region (its end, rBeg, score: 6 JNI calls instead of 18) and checks that the array is in (pair, end, rank) order with
-// regIdx = rank, as memSamPeGroupJNIPrepare builds it (MemSamPe.scala:1962-1990); (2) the skip test of the library itself
-// (bpsw_rescue_skip.h) selects the pairs that may need a job; (3) only THEIR regions (all fields), mates and windows are unmarshalled,
-// into a group of their own, and bpsw_matesw_group runs on that; (4) the result array holds new objects for those pairs and, for every
-// other end, the caller's own MateSWType objects -- they already carry (readIdx, pairIdx, regIdx = rank) and the unchanged region.
-// The Scala caller rebuilds its lists from the returned array and drops the input arrays (MemSamPe.scala:2010-2044), so sharing the
-// objects is safe.  Anything that does not look like what memSamPeGroupJNIPrepare builds (SeqSWType[] not one per end in order,
-// RefSWType[] not in (pair, end, anchor) order, regIdx != rank, a malformed object) returns 1: the caller takes the eager path below,
-// which accepts any order and raises the errors.  BPSW_JNI_LAZY=0: always the eager path.
-struct LightReg { int64_t rb; int32_t score, e; };
-struct LazyScratch {
-  std::vector<LightReg> light;
-  std::vector<int64_t> reg_at, base;
-  std::vector<int32_t> reg_cnt, ref_cnt, touched;
-  std::vector<uint8_t> is_touched;
-};
-thread_local LazyScratch t_lazy;
 
 void read_region(JNIEnv* env, jobject a, const RegIds& rf, bpsw_alnreg_t* r) {
   r->rb = jni::GetLongField(env, a, rf.rBeg); r->re = jni::GetLongField(env, a, rf.rEnd);
@@ -299,6 +311,116 @@ jobject new_mate_object(JNIEnv* env, const MateIds* ids, jint k, jint i, jint ra
   jni::SetObjectField(env, m, ids->mAln, a);
   return m;
 }
+
+// RefSWType o's rBegArray / rEndArray / lenArray into window row x and the bytes of its windows into ref_pool, counting the windows
+// named by coordinates only and those that carry bytes.  nullptr, or what is wrong with the object (the eager walk raises it).
+const char* read_ref_windows(JNIEnv* env, const MateIds* ids, jobject o, size_t x, MateScratch& ms, size_t* coord_windows,
+                             size_t* byte_windows) {
+  jlongArray ab = (jlongArray)jni::GetObjectField(env, o, ids->rB), ae = (jlongArray)jni::GetObjectField(env, o, ids->rE);
+  jlongArray al = (jlongArray)jni::GetObjectField(env, o, ids->rL);
+  if (!ab || !ae || !al || jni::GetArrayLength(env, ab) < 4 || jni::GetArrayLength(env, ae) < 4 || jni::GetArrayLength(env, al) < 4)
+    return "RefSWType arrays must hold 4 longs";
+  jni::GetLongArrayRegion(env, ab, 0, 4, &ms.ref_rb[x]);
+  jni::GetLongArrayRegion(env, ae, 0, 4, &ms.ref_re[x]);
+  jni::GetLongArrayRegion(env, al, 0, 4, &ms.ref_len[x]);
+  for (int r = 0; r < 4; ++r) {
+    const int64_t len = ms.ref_len[x + r];
+    if (ms.ref_rb[x + r] < 0 && ms.ref_re[x + r] < 0) continue;  // failed orientation: rBeg=rEnd=-1, ref=null (MemSamPe.scala:1863-1868)
+    jbyteArray bytes = (jbyteArray)jni::GetObjectField(env, o, ids->rRef[r]);
+    if (!bytes && len != 0) { ++*coord_windows; continue; }  // named by (rBeg, rEnd) only: read from the device-resident reference
+    ++*byte_windows;
+    if (len <= 0) continue;  // bnsGetSeq returned nothing (window bridging the strands)
+    int32_t got = 0;
+    read_bytes(env, bytes, ms.ref_pool, &ms.ref_off[x + r], &got);
+    if (got < len) return "reference window shorter than lenArray";
+  }
+  return nullptr;
+}
+
+// g's tables from the scratch; a pool handed over is never empty.  Windows named by coordinates travel without lengths, offsets
+// and bytes: the library reads them from the reference loaded with loadPacJNI.
+void fill_group(bpsw_rescue_group_t& g, MateScratch& ms, bool coordinates) {
+  if (ms.seq_pool.n == 0) memset(ms.seq_pool.grow(16), 0, 16);
+  g.seq_len = ms.seq_len.data(); g.seq_off = ms.seq_off.data(); g.seq_pool = ms.seq_pool.p; g.seq_pool_bytes = ms.seq_pool.n;
+  g.reg_cnt = ms.reg_cnt.data(); g.regs = ms.regs.data(); g.ref_cnt = ms.ref_cnt.data();
+  g.ref_rb = ms.ref_rb.data(); g.ref_re = ms.ref_re.data();
+  if (coordinates) {
+    g.ref_len = nullptr; g.ref_off = nullptr; g.ref_pool = nullptr; g.ref_pool_bytes = 0;
+    return;
+  }
+  if (ms.ref_pool.n == 0) memset(ms.ref_pool.grow(16), 0, 16);
+  g.ref_len = ms.ref_len.data(); g.ref_off = ms.ref_off.data(); g.ref_pool = ms.ref_pool.p; g.ref_pool_bytes = ms.ref_pool.n;
+}
+
+// BPSW_MATESW_COMPAT=scala: the rescue as MemSamPe.scala does it rather than as the C code does (read on every call)
+bool scala_rescue() {
+  const char* compat = getenv("BPSW_MATESW_COMPAT");
+  return compat && strcmp(compat, "scala") == 0;
+}
+
+// bpsw_matesw_group into out_cnt / out, once more with room for what it asked for when out was too small.  false: the
+// RuntimeException "bPSW: <entry>: ..." is pending.
+bool run_rescue(JNIEnv* env, bpsw_ctx_t* ctx, const char* entry, const bpsw_opt_t& opt, const bpsw_rescue_group_t& g,
+                std::vector<int32_t>& out_cnt, std::vector<bpsw_alnreg_t>& out, int64_t* total) {
+  const int mode = scala_rescue() ? BPSW_RESCUE_SCALA : BPSW_RESCUE_C;
+  int rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), total);
+  if (rc == BPSW_ERR_CAPACITY) {
+    out.resize((size_t)*total);
+    rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), total);
+  }
+  if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: ") + entry + ": " + bpsw_last_error()); return false; }
+  return true;
+}
+
+// MemOptType's int fields in the order of MateIds::opt_int, which is also the order of mateSWFlatJNI's optInts
+void set_opt_ints(bpsw_opt_t& opt, const int32_t v[16]) {
+  int32_t* dst[16] = {&opt.a, &opt.b, &opt.o_del, &opt.e_del, &opt.o_ins, &opt.e_ins, &opt.pen_unpaired, &opt.pen_clip5,
+                      &opt.pen_clip3, &opt.w, &opt.zdrop, &opt.T, &opt.flag, &opt.min_seed_len, &opt.max_ins, &opt.max_matesw};
+  for (int i = 0; i < 16; ++i) *dst[i] = v[i];
+}
+
+// n regions of the flat entries: `stride` longs each (rBeg, rEnd, then the hash when stride is 3; without it the hash is 0) and
+// 10 ints each (qBeg, qEnd, score, trueScore, sub, csub, subNum, width, seedCov, secondary)
+void decode_regions(const int64_t* longs, int stride, const int32_t* ints, int64_t n, bpsw_alnreg_t* out) {
+  for (int64_t j = 0; j < n; ++j) {
+    bpsw_alnreg_t& a = out[j];
+    const int64_t* l = longs + stride * j;
+    const int32_t* v = ints + 10 * j;
+    a.rb = l[0]; a.re = l[1]; a.hash = stride > 2 ? (uint64_t)l[2] : 0;
+    a.qb = v[0]; a.qe = v[1]; a.score = v[2]; a.truesc = v[3]; a.sub = v[4]; a.csub = v[5]; a.sub_n = v[6]; a.w = v[7]; a.seedcov = v[8];
+    a.secondary = v[9];
+  }
+}
+
+// MemPeStat[4] of the flat entries: 5 doubles per orientation (low, high, failed, avg, std)
+void decode_pes(const double* v, bpsw_pestat_t pes[4]) {
+  for (int r = 0; r < 4; ++r, v += 5) {
+    pes[r].low = (int32_t)v[0]; pes[r].high = (int32_t)v[1]; pes[r].failed = (int32_t)v[2];
+    pes[r].avg = v[3]; pes[r].std = v[4];
+  }
+}
+
+// ---- mateSWJNI without the object walk over pairs that need nothing (round 5) -------------------------------------------------------
+// The reference's contract hands over every region, every mate and every rescue window of a group as objects (native/jni_mate_sw.c:
+// 239-518), and 96 % of a 4 096-pair call through this shim was reading and rebuilding them -- while nine pairs in ten are properly
+// paired, need no SW at all and come back exactly as they went in.  So: (1) one light pass over MateSWType[] reads what the skip test
+// needs of a region (its end, rBeg, score: 6 JNI calls instead of 18) and checks that the array is in (pair, end, rank) order with
+// regIdx = rank, as memSamPeGroupJNIPrepare builds it (MemSamPe.scala:1962-1990); (2) the skip test of the library itself
+// (bpsw_rescue_skip.h) selects the pairs that may need a job; (3) only THEIR regions (all fields), mates and windows are unmarshalled,
+// into a group of their own, and bpsw_matesw_group runs on that; (4) the result array holds new objects for those pairs and, for every
+// other end, the caller's own MateSWType objects -- they already carry (readIdx, pairIdx, regIdx = rank) and the unchanged region.
+// The Scala caller rebuilds its lists from the returned array and drops the input arrays (MemSamPe.scala:2010-2044), so sharing the
+// objects is safe.  Anything that does not look like what memSamPeGroupJNIPrepare builds (SeqSWType[] not one per end in order,
+// RefSWType[] not in (pair, end, anchor) order, regIdx != rank, a malformed object) returns 1: the caller takes the eager path below,
+// which accepts any order and raises the errors.
+struct LightReg { int64_t rb; int32_t score, e; };
+struct LazyScratch {
+  std::vector<LightReg> light;
+  std::vector<int64_t> reg_at, base;
+  std::vector<int32_t> reg_cnt, ref_cnt, touched;
+  std::vector<uint8_t> is_touched;
+};
+thread_local LazyScratch t_lazy;
 
 // 0: done (*ret_out set), 1: take the eager path, -1: a Java exception is pending
 int mate_sw_lazy(JNIEnv* env, const MateIds* ids, const bpsw_opt_t& opt, const bpsw_rescue_group_t& g0, jint groupSize, jobjectArray seqArr,
@@ -356,8 +478,7 @@ int mate_sw_lazy(JNIEnv* env, const MateIds* ids, const bpsw_opt_t& opt, const b
     int32_t low[4], high[4];
     int failed_mask = 0;
     for (int r = 0; r < 4; ++r) { low[r] = g0.pes[r].low; high[r] = g0.pes[r].high; failed_mask |= (g0.pes[r].failed ? 1 : 0) << r; }
-    const char* compat = getenv("BPSW_MATESW_COMPAT");
-    const bool scala = compat && strcmp(compat, "scala") == 0;
+    const bool scala = scala_rescue();
     for (jint k = 0; k < groupSize; ++k) {
       bool touched = false;
       for (int i = 0; i < 2 && !touched; ++i) {
@@ -385,15 +506,14 @@ int mate_sw_lazy(JNIEnv* env, const MateIds* ids, const bpsw_opt_t& opt, const b
   std::vector<int32_t>&seq_len = ms.seq_len, &reg_cnt = ms.reg_cnt, &ref_cnt = ms.ref_cnt;
   std::vector<int64_t>& seq_off = ms.seq_off;
   seq_len.assign(rends ? rends : 1, 0); reg_cnt.assign(rends ? rends : 1, 0); ref_cnt.assign(rends ? rends : 1, 0); seq_off.assign(rends ? rends : 1, 0);
-  BytePool &seq_pool = ms.seq_pool, &ref_pool = ms.ref_pool;
-  seq_pool.clear(); ref_pool.clear();
+  BytePool& seq_pool = ms.seq_pool;
+  seq_pool.clear(); ms.ref_pool.clear();
   std::vector<bpsw_alnreg_t>& regs = ms.regs;
   regs.clear();
-  std::vector<int64_t>&ref_rb = ms.ref_rb, &ref_re = ms.ref_re, &ref_len = ms.ref_len, &ref_off = ms.ref_off;
   size_t rows = 0;
   for (size_t ti = 0; ti < nt; ++ti)
     for (int i = 0; i < 2; ++i) rows += (size_t)L.ref_cnt[2 * (size_t)L.touched[ti] + (size_t)i];
-  ref_rb.assign(4 * rows, -1); ref_re.assign(4 * rows, -1); ref_len.assign(4 * rows, 0); ref_off.assign(4 * rows, 0);
+  ms.ref_rb.assign(4 * rows, -1); ms.ref_re.assign(4 * rows, -1); ms.ref_len.assign(4 * rows, 0); ms.ref_off.assign(4 * rows, 0);
   size_t coord_windows = 0, byte_windows = 0, row_at = 0;
   for (size_t ti = 0; ti < nt; ++ti) {
     const jint k = L.touched[ti];
@@ -423,59 +543,25 @@ int mate_sw_lazy(JNIEnv* env, const MateIds* ids, const bpsw_opt_t& opt, const b
         if (!o || jni::GetIntField(env, o, ids->rRid) != k || jni::GetIntField(env, o, ids->rPid) != i || jni::GetIntField(env, o, ids->rReg) != j) {
           jni::PopLocalFrame(env, nullptr); return 1;
         }
-        const size_t x = 4 * row_at;
-        jlongArray ab = (jlongArray)jni::GetObjectField(env, o, ids->rB), ae = (jlongArray)jni::GetObjectField(env, o, ids->rE);
-        jlongArray al = (jlongArray)jni::GetObjectField(env, o, ids->rL);
-        if (!ab || !ae || !al || jni::GetArrayLength(env, ab) < 4 || jni::GetArrayLength(env, ae) < 4 || jni::GetArrayLength(env, al) < 4) {
-          jni::PopLocalFrame(env, nullptr); return 1;
-        }
-        jni::GetLongArrayRegion(env, ab, 0, 4, (jlong*)&ref_rb[x]);
-        jni::GetLongArrayRegion(env, ae, 0, 4, (jlong*)&ref_re[x]);
-        jni::GetLongArrayRegion(env, al, 0, 4, (jlong*)&ref_len[x]);
-        for (int r = 0; r < 4; ++r) {
-          if (ref_rb[x + r] < 0 && ref_re[x + r] < 0) continue;  // failed orientation (MemSamPe.scala:1863-1868)
-          jbyteArray bytes = (jbyteArray)jni::GetObjectField(env, o, ids->rRef[r]);
-          if (!bytes && ref_len[x + r] != 0) { ++coord_windows; continue; }
-          ++byte_windows;
-          if (ref_len[x + r] <= 0) continue;
-          int32_t got = 0;
-          read_bytes(env, bytes, ref_pool, &ref_off[x + r], &got);
-          if (got < ref_len[x + r]) { jni::PopLocalFrame(env, nullptr); return 1; }
-        }
+        if (read_ref_windows(env, ids, o, 4 * row_at, ms, &coord_windows, &byte_windows)) { jni::PopLocalFrame(env, nullptr); return 1; }
       }
       jni::PopLocalFrame(env, nullptr);
     }
   }
   if (coord_windows > 0 && byte_windows > 0) return 1;
-  if (seq_pool.n == 0) memset(seq_pool.grow(16), 0, 16);
-  if (ref_pool.n == 0) memset(ref_pool.grow(16), 0, 16);
   bpsw_rescue_group_t g = g0;
   g.group_size = (int32_t)nt;
-  g.seq_len = seq_len.data(); g.seq_off = seq_off.data(); g.seq_pool = seq_pool.p; g.seq_pool_bytes = seq_pool.n;
-  g.reg_cnt = reg_cnt.data(); g.regs = regs.data(); g.ref_cnt = ref_cnt.data();
-  g.ref_rb = ref_rb.data(); g.ref_re = ref_re.data(); g.ref_len = ref_len.data(); g.ref_off = ref_off.data();
-  g.ref_pool = ref_pool.p; g.ref_pool_bytes = ref_pool.n;
-  if (coord_windows > 0) { g.ref_pool = nullptr; g.ref_pool_bytes = 0; g.ref_len = nullptr; g.ref_off = nullptr; }
+  fill_group(g, ms, coord_windows > 0);
   std::vector<int32_t>& out_cnt = ms.out_cnt;
   std::vector<bpsw_alnreg_t>& out = ms.out;
   out_cnt.assign(rends ? rends : 1, 0);
   int64_t total_r = 0;
   const double t1 = now_us();
+  bpsw_ctx_t* ctx = thread_context(env);  // (a call that needs no device still fails without one, like every other: no silent CPU path)
+  if (!ctx) return -1;
   if (nt) {
-    bpsw_ctx_t* ctx = thread_context(env);
-    if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return -1; }
     out.resize(regs.size() + rows + 16);
-    const char* compat = getenv("BPSW_MATESW_COMPAT");
-    const int mode = (compat && strcmp(compat, "scala") == 0) ? BPSW_RESCUE_SCALA : BPSW_RESCUE_C;
-    int rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), &total_r);
-    if (rc == BPSW_ERR_CAPACITY) {
-      out.resize((size_t)total_r);
-      rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), &total_r);
-    }
-    if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: mateSWJNI: ") + bpsw_last_error()); return -1; }
-  } else if (!thread_context(env)) {  // (a call that needs no device still fails without one, like every other: no silent CPU path)
-    throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error());
-    return -1;
+    if (!run_rescue(env, ctx, "mateSWJNI", opt, g, out_cnt, out, &total_r)) return -1;
   }
   // ---- (4) the result: (pair, end, rank) order; untouched ends keep the caller's objects ----
   const double t2 = now_us();
@@ -545,12 +631,12 @@ JNIEXPORT void JNICALL Java_cs_ucla_edu_bwaspark_jni_HelloWorld_helloWorld(JNIEn
 JNIEXPORT jshortArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI(JNIEnv* env, jobject,
                                                                                             jint retTaskNum,
                                                                                             jbyteArray arrayIn) {
-  try {
+  return jni_entry(env, "swExtendFPGAJNI", jshortArray(nullptr), [&]() -> jshortArray {
   if (!arrayIn || retTaskNum < 0) { throw_runtime(env, "bPSW: swExtendFPGAJNI: bad arguments"); return nullptr; }
   const double t0 = now_us();
   const jsize bytes = jni::GetArrayLength(env, arrayIn);
   bpsw_ctx_t* ctx = thread_context(env);
-  if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return nullptr; }
+  if (!ctx) return nullptr;
   // Single touch: the JVM's bytes go straight into the context's pinned staging block, from where the copy engine reads them
   // (the reference does one memcpy into its shared-memory segment, src/main/jni_fpga/sw_extend_fpga.c:146-155); the results are
   // handed to SetShortArrayRegion from the pinned block the kernel wrote them to.  No heap allocation, no second copy.
@@ -569,17 +655,14 @@ JNIEXPORT jshortArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swEx
   if (res_len > 0) jni::SetShortArrayRegion(env, ret, 0, (jsize)res_len, res);
   t_times = {t1 - t0, t2 - t1, now_us() - t2, (double)(res_len / 10)};
   return ret;
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: swExtendFPGAJNI: ") + e.what());
-    return nullptr;
-  }
+  });
 }
 
 // ---- boundary 1 ------------------------------------------------------------------------------------
 JNIEXPORT jobjectArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWJNI(
     JNIEnv* env, jobject, jobject optObj, jlong pacLen, jobjectArray pesArr, jint groupSize, jobjectArray seqArr,
     jobjectArray mateArr, jobjectArray refArr, jintArray refSizeArr) {
-  try {
+  return jni_entry(env, "mateSWJNI", jobjectArray(nullptr), [&]() -> jobjectArray {
   if (!optObj || !pesArr || !seqArr || !mateArr || !refArr || !refSizeArr || groupSize < 0) {
     throw_runtime(env, "bPSW: mateSWJNI: bad arguments");
     return nullptr;
@@ -587,17 +670,15 @@ JNIEXPORT jobjectArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWJNI
   const double t0 = now_us();
   const MateIds* ids = mate_ids(env);
   if (!ids) return nullptr;  // NoClassDefFoundError / NoSuchFieldError pending
-  jclass regCls = ids->regCls, mateCls = ids->mateCls;
   // ---- MemOptType (native/jni_mate_sw.c:102-128, 177-221) ----
   bpsw_opt_t opt;
   bpsw_opt_default(&opt);
   {
-    int32_t* dst[16] = {&opt.a, &opt.b, &opt.o_del, &opt.e_del, &opt.o_ins, &opt.e_ins, &opt.pen_unpaired, &opt.pen_clip5,
-                        &opt.pen_clip3, &opt.w, &opt.zdrop, &opt.T, &opt.flag, &opt.min_seed_len, &opt.max_ins, &opt.max_matesw};
-    for (int i = 0; i < 16; ++i) *dst[i] = jni::GetIntField(env, optObj, ids->opt_int[i]);
-    jfieldID mlr = ids->opt_mlr, matId = ids->opt_mat;
-    opt.mask_level_redun = jni::GetFloatField(env, optObj, mlr);
-    jbyteArray matArr = (jbyteArray)jni::GetObjectField(env, optObj, matId);
+    jint oi[16];
+    for (int i = 0; i < 16; ++i) oi[i] = jni::GetIntField(env, optObj, ids->opt_int[i]);
+    set_opt_ints(opt, oi);
+    opt.mask_level_redun = jni::GetFloatField(env, optObj, ids->opt_mlr);
+    jbyteArray matArr = (jbyteArray)jni::GetObjectField(env, optObj, ids->opt_mat);
     if (!matArr || jni::GetArrayLength(env, matArr) < 25) { throw_runtime(env, "bPSW: mateSWJNI: opt.mat must hold 25 bytes"); return nullptr; }
     jni::GetByteArrayRegion(env, matArr, 0, 25, reinterpret_cast<jbyte*>(opt.mat));
     jni::DeleteLocalRef(env, matArr);
@@ -619,21 +700,17 @@ JNIEXPORT jobjectArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWJNI
     }
   }
   {  // the lazy path (above): only the pairs that may need a job are unmarshalled; 1 = the arrays are not in the order it relies on
-    static const bool lazy_on = !(getenv("BPSW_JNI_LAZY") && atoi(getenv("BPSW_JNI_LAZY")) == 0);
-    if (lazy_on) {
-      jobjectArray lazy_ret = nullptr;
-      const int st = mate_sw_lazy(env, ids, opt, g, groupSize, seqArr, mateArr, refArr, refSizeArr, t0, &lazy_ret);
-      if (st == 0) return lazy_ret;
-      if (st < 0) return nullptr;
-    }
+    jobjectArray lazy_ret = nullptr;
+    const int st = mate_sw_lazy(env, ids, opt, g, groupSize, seqArr, mateArr, refArr, refSizeArr, t0, &lazy_ret);
+    if (st == 0) return lazy_ret;
+    if (st < 0) return nullptr;
   }
   const size_t ends = 2 * (size_t)groupSize;
   MateScratch& ms = t_ms;
   std::vector<int32_t>&seq_len = ms.seq_len, &reg_cnt = ms.reg_cnt, &ref_cnt = ms.ref_cnt;
   std::vector<int64_t>& seq_off = ms.seq_off;
   seq_len.assign(ends, 0); reg_cnt.assign(ends, 0); ref_cnt.assign(ends, 0); seq_off.assign(ends, 0);
-  BytePool &seq_pool = ms.seq_pool, &ref_pool = ms.ref_pool;
-  seq_pool.clear(); ref_pool.clear();
+  ms.seq_pool.clear(); ms.ref_pool.clear();
   auto end_index = [&](jint k, jint i) -> long { return (k < 0 || k >= groupSize || i < 0 || i > 1) ? -1 : 2l * k + i; };
 
   {  // ---- SeqSWType[] (native/jni_mate_sw.c:258-278) ----
@@ -645,35 +722,25 @@ JNIEXPORT jobjectArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWJNI
       if (e < 0) { throw_runtime(env, "bPSW: mateSWJNI: SeqSWType index outside the group"); return nullptr; }
       jbyteArray bytes = (jbyteArray)jni::GetObjectField(env, o, strans);
       int32_t got = 0;
-      read_bytes(env, bytes, seq_pool, &seq_off[(size_t)e], &got);
+      read_bytes(env, bytes, ms.seq_pool, &seq_off[(size_t)e], &got);
       const jint declared = jni::GetIntField(env, o, slen);
       seq_len[(size_t)e] = declared < got ? declared : got;
       if (bytes) jni::DeleteLocalRef(env, bytes);
       jni::DeleteLocalRef(env, o);
     }
   }
-  const RegIds& rf = ids->rf;
-  jfieldID mRid = ids->mRid, mPid = ids->mPid, mReg = ids->mReg, mAln = ids->mAln;
-
   std::vector<bpsw_alnreg_t>& regs = ms.regs;
   {  // ---- MateSWType[] -> regions grouped by (k,i) in arrival order (native/jni_mate_sw.c:300-345) ----
     const jsize n = jni::GetArrayLength(env, mateArr);
-    std::vector<bpsw_alnreg_t>& tmp = ms.tmp;
+    std::vector<bpsw_alnreg_t>& arrived = ms.arrived;
     std::vector<long>& where = ms.where;
-    tmp.resize((size_t)n); where.resize((size_t)n);
+    arrived.resize((size_t)n); where.resize((size_t)n);
     for (jsize s = 0; s < n; ++s) {
       jobject o = jni::GetObjectArrayElement(env, mateArr, s);
-      const long e = o ? end_index(jni::GetIntField(env, o, mRid), jni::GetIntField(env, o, mPid)) : -1;
-      jobject a = e >= 0 ? jni::GetObjectField(env, o, mAln) : nullptr;
+      const long e = o ? end_index(jni::GetIntField(env, o, ids->mRid), jni::GetIntField(env, o, ids->mPid)) : -1;
+      jobject a = e >= 0 ? jni::GetObjectField(env, o, ids->mAln) : nullptr;
       if (!a) { throw_runtime(env, "bPSW: mateSWJNI: malformed MateSWType"); return nullptr; }
-      bpsw_alnreg_t& r = tmp[(size_t)s];
-      r.rb = jni::GetLongField(env, a, rf.rBeg); r.re = jni::GetLongField(env, a, rf.rEnd);
-      r.qb = jni::GetIntField(env, a, rf.qBeg); r.qe = jni::GetIntField(env, a, rf.qEnd);
-      r.score = jni::GetIntField(env, a, rf.score); r.truesc = jni::GetIntField(env, a, rf.trueScore);
-      r.sub = jni::GetIntField(env, a, rf.sub); r.csub = jni::GetIntField(env, a, rf.csub);
-      r.sub_n = jni::GetIntField(env, a, rf.subNum); r.w = jni::GetIntField(env, a, rf.width);
-      r.seedcov = jni::GetIntField(env, a, rf.seedCov); r.secondary = jni::GetIntField(env, a, rf.secondary);
-      r.hash = (uint64_t)jni::GetLongField(env, a, rf.hash);
+      read_region(env, a, ids->rf, &arrived[(size_t)s]);
       where[(size_t)s] = e;
       ++reg_cnt[(size_t)e];
       jni::DeleteLocalRef(env, a);
@@ -683,9 +750,8 @@ JNIEXPORT jobjectArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWJNI
     at.assign(ends + 1, 0);
     for (size_t e = 0; e < ends; ++e) at[e + 1] = at[e] + reg_cnt[e];
     regs.resize((size_t)n);
-    for (jsize s = 0; s < n; ++s) regs[(size_t)at[(size_t)where[(size_t)s]]++] = tmp[(size_t)s];
+    for (jsize s = 0; s < n; ++s) regs[(size_t)at[(size_t)where[(size_t)s]]++] = arrived[(size_t)s];
   }
-  std::vector<int64_t>&ref_rb = ms.ref_rb, &ref_re = ms.ref_re, &ref_len = ms.ref_len, &ref_off = ms.ref_off;
   size_t coord_windows = 0, byte_windows = 0;
   {  // ---- refSizeArray + RefSWType[] (native/jni_mate_sw.c:352-518) ----
     if (jni::GetArrayLength(env, refSizeArr) < (jsize)ends) { throw_runtime(env, "bPSW: mateSWJNI: refSizeArray too short"); return nullptr; }
@@ -697,96 +763,49 @@ JNIEXPORT jobjectArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWJNI
       base[e + 1] = base[e] + ref_cnt[e];
     }
     const size_t rows = (size_t)base[ends];
-    ref_rb.assign(4 * rows, -1); ref_re.assign(4 * rows, -1); ref_len.assign(4 * rows, 0); ref_off.assign(4 * rows, 0);
-    jfieldID rRid = ids->rRid, rPid = ids->rPid, rReg = ids->rReg, rB = ids->rB, rE = ids->rE, rL = ids->rL;
-    const jfieldID* rRef = ids->rRef;
+    ms.ref_rb.assign(4 * rows, -1); ms.ref_re.assign(4 * rows, -1); ms.ref_len.assign(4 * rows, 0); ms.ref_off.assign(4 * rows, 0);
     const jsize n = jni::GetArrayLength(env, refArr);
     for (jsize s = 0; s < n; ++s) {
       if (jni::PushLocalFrame(env, 16) != JNI_OK) return nullptr;
       jobject o = jni::GetObjectArrayElement(env, refArr, s);
-      const long e = o ? end_index(jni::GetIntField(env, o, rRid), jni::GetIntField(env, o, rPid)) : -1;
-      const jint j = o ? jni::GetIntField(env, o, rReg) : -1;
+      const long e = o ? end_index(jni::GetIntField(env, o, ids->rRid), jni::GetIntField(env, o, ids->rPid)) : -1;
+      const jint j = o ? jni::GetIntField(env, o, ids->rReg) : -1;
       if (e < 0 || j < 0 || j >= ref_cnt[(size_t)e]) { jni::PopLocalFrame(env, nullptr); throw_runtime(env, "bPSW: mateSWJNI: RefSWType index outside refSizeArray"); return nullptr; }
-      const size_t x = 4 * (size_t)(base[(size_t)e] + j);
-      jlongArray ab = (jlongArray)jni::GetObjectField(env, o, rB), ae = (jlongArray)jni::GetObjectField(env, o, rE);
-      jlongArray al = (jlongArray)jni::GetObjectField(env, o, rL);
-      if (!ab || !ae || !al || jni::GetArrayLength(env, ab) < 4 || jni::GetArrayLength(env, ae) < 4 || jni::GetArrayLength(env, al) < 4) {
-        jni::PopLocalFrame(env, nullptr); throw_runtime(env, "bPSW: mateSWJNI: RefSWType arrays must hold 4 longs"); return nullptr;
-      }
-      jni::GetLongArrayRegion(env, ab, 0, 4, (jlong*)&ref_rb[x]);
-      jni::GetLongArrayRegion(env, ae, 0, 4, (jlong*)&ref_re[x]);
-      jni::GetLongArrayRegion(env, al, 0, 4, (jlong*)&ref_len[x]);
-      for (int r = 0; r < 4; ++r) {
-        if (ref_rb[x + r] < 0 && ref_re[x + r] < 0) continue;  // failed orientation: rBeg=rEnd=-1, ref=null (MemSamPe.scala:1863-1868)
-        jbyteArray bytes = (jbyteArray)jni::GetObjectField(env, o, rRef[r]);
-        if (!bytes && ref_len[x + r] != 0) { ++coord_windows; continue; }  // named by (rBeg, rEnd) only: read from the device-resident reference
-        ++byte_windows;
-        if (ref_len[x + r] <= 0) continue;          // bnsGetSeq returned nothing (window bridging the strands)
-        int32_t got = 0;
-        read_bytes(env, bytes, ref_pool, &ref_off[x + r], &got);
-        if (got < ref_len[x + r]) { jni::PopLocalFrame(env, nullptr); throw_runtime(env, "bPSW: mateSWJNI: reference window shorter than lenArray"); return nullptr; }
-      }
+      const char* bad = read_ref_windows(env, ids, o, 4 * (size_t)(base[(size_t)e] + j), ms, &coord_windows, &byte_windows);
       jni::PopLocalFrame(env, nullptr);
+      if (bad) { throw_runtime(env, std::string("bPSW: mateSWJNI: ") + bad); return nullptr; }
     }
   }
-  if (seq_pool.n == 0) memset(seq_pool.grow(16), 0, 16);
-  if (ref_pool.n == 0) memset(ref_pool.grow(16), 0, 16);
-  g.seq_len = seq_len.data(); g.seq_off = seq_off.data(); g.seq_pool = seq_pool.p; g.seq_pool_bytes = seq_pool.n;
-  g.reg_cnt = reg_cnt.data(); g.regs = regs.data(); g.ref_cnt = ref_cnt.data();
-  g.ref_rb = ref_rb.data(); g.ref_re = ref_re.data(); g.ref_len = ref_len.data(); g.ref_off = ref_off.data();
-  g.ref_pool = ref_pool.p; g.ref_pool_bytes = ref_pool.n;
-  if (coord_windows > 0) {
-    if (byte_windows > 0) { throw_runtime(env, "bPSW: mateSWJNI: RefSWType windows must all carry bytes or all be coordinates"); return nullptr; }
-    g.ref_pool = nullptr; g.ref_pool_bytes = 0; g.ref_len = nullptr; g.ref_off = nullptr;
-  }
+  if (coord_windows > 0 && byte_windows > 0) { throw_runtime(env, "bPSW: mateSWJNI: RefSWType windows must all carry bytes or all be coordinates"); return nullptr; }
+  fill_group(g, ms, coord_windows > 0);
 
   bpsw_ctx_t* ctx = thread_context(env);
-  if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return nullptr; }
+  if (!ctx) return nullptr;
   std::vector<int32_t>& out_cnt = ms.out_cnt;
   std::vector<bpsw_alnreg_t>& out = ms.out;
   out_cnt.resize(ends ? ends : 1);
-  out.resize(regs.size() + 4 * ref_rb.size() / 4 + 16);
+  out.resize(regs.size() + ms.ref_rb.size() + 16);
   int64_t total = 0;
   const double t1 = now_us();
-  const char* compat = getenv("BPSW_MATESW_COMPAT");
-  const int mode = (compat && strcmp(compat, "scala") == 0) ? BPSW_RESCUE_SCALA : BPSW_RESCUE_C;
-  int rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), &total);
-  if (rc == BPSW_ERR_CAPACITY) {
-    out.resize((size_t)total);
-    rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), &total);
-  }
-  if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: mateSWJNI: ") + bpsw_last_error()); return nullptr; }
+  if (!run_rescue(env, ctx, "mateSWJNI", opt, g, out_cnt, out, &total)) return nullptr;
 
   // ---- result: MateSWType[] in (k, i, rank) order (native/jni_mate_sw.c:548-591) ----
   const double t2 = now_us();
-  jobjectArray ret = jni::NewObjectArray(env, (jsize)total, mateCls, nullptr);
+  jobjectArray ret = jni::NewObjectArray(env, (jsize)total, ids->mateCls, nullptr);
   if (!ret) return nullptr;
   int64_t at = 0;
   for (size_t e = 0; e < ends; ++e)
     for (int32_t rank = 0; rank < out_cnt[e]; ++rank, ++at) {
       if (jni::PushLocalFrame(env, 8) != JNI_OK) return nullptr;
-      const bpsw_alnreg_t& r = out[(size_t)at];
-      jobject m = jni::AllocObject(env, mateCls), a = jni::AllocObject(env, regCls);
-      if (!m || !a) { jni::PopLocalFrame(env, nullptr); return nullptr; }
-      jni::SetIntField(env, m, mRid, (jint)(e >> 1)); jni::SetIntField(env, m, mPid, (jint)(e & 1)); jni::SetIntField(env, m, mReg, rank);
-      jni::SetLongField(env, a, rf.rBeg, r.rb); jni::SetLongField(env, a, rf.rEnd, r.re);
-      jni::SetIntField(env, a, rf.qBeg, r.qb); jni::SetIntField(env, a, rf.qEnd, r.qe);
-      jni::SetIntField(env, a, rf.score, r.score); jni::SetIntField(env, a, rf.trueScore, r.truesc);
-      jni::SetIntField(env, a, rf.sub, r.sub); jni::SetIntField(env, a, rf.csub, r.csub);
-      jni::SetIntField(env, a, rf.subNum, r.sub_n); jni::SetIntField(env, a, rf.width, r.w);
-      jni::SetIntField(env, a, rf.seedCov, r.seedcov); jni::SetIntField(env, a, rf.secondary, r.secondary);
-      jni::SetLongField(env, a, rf.hash, (jlong)r.hash);
-      jni::SetObjectField(env, m, mAln, a);
+      jobject m = new_mate_object(env, ids, (jint)(e >> 1), (jint)(e & 1), rank, out[(size_t)at]);
+      if (!m) { jni::PopLocalFrame(env, nullptr); return nullptr; }
       jni::SetObjectArrayElement(env, ret, (jsize)at, m);
       jni::PopLocalFrame(env, nullptr);
     }
   t_times = {t1 - t0, t2 - t1, now_us() - t2, (double)total};
   t_mate_path = 2;
   return ret;
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: mateSWJNI: ") + e.what());
-    return nullptr;
-  }
+  });
 }
 
 // ---- boundary 1 with flat arrays (round 4) -------------------------------------------------------------------------------------
@@ -814,7 +833,7 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJ
     JNIEnv* env, jobject, jintArray optInts, jfloat maskLevelRedun, jbyteArray matArr, jlong pacLen, jdoubleArray pesArr, jint groupSize,
     jintArray seqLenArr, jbyteArray seqsArr, jintArray regCntArr, jlongArray regLongsArr, jintArray regIntsArr, jintArray refCntArr,
     jlongArray refRbArr, jlongArray refReArr, jlongArray refLenArr, jbyteArray refBytesArr) {
-  try {
+  return jni_entry(env, "mateSWFlatJNI", jlongArray(nullptr), [&]() -> jlongArray {
   if (groupSize < 0 || groupSize > 0x3fffffff) { throw_runtime(env, "bPSW: mateSWFlatJNI: groupSize out of range"); return nullptr; }
   const jsize ends_j = 2 * groupSize;
   if (!optInts || !matArr || !pesArr || !seqLenArr || !seqsArr || !regCntArr || !regLongsArr || !regIntsArr || !refCntArr || !refRbArr ||
@@ -830,9 +849,7 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJ
   {
     jint oi[16];
     jni::GetIntArrayRegion(env, optInts, 0, 16, oi);
-    int32_t* dst[16] = {&opt.a, &opt.b, &opt.o_del, &opt.e_del, &opt.o_ins, &opt.e_ins, &opt.pen_unpaired, &opt.pen_clip5,
-                        &opt.pen_clip3, &opt.w, &opt.zdrop, &opt.T, &opt.flag, &opt.min_seed_len, &opt.max_ins, &opt.max_matesw};
-    for (int i = 0; i < 16; ++i) *dst[i] = oi[i];
+    set_opt_ints(opt, oi);
     opt.mask_level_redun = maskLevelRedun;
     jni::GetByteArrayRegion(env, matArr, 0, 25, reinterpret_cast<jbyte*>(opt.mat));
   }
@@ -843,15 +860,12 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJ
   {
     jdouble pe[20];
     jni::GetDoubleArrayRegion(env, pesArr, 0, 20, pe);
-    for (int r = 0; r < 4; ++r) {
-      g.pes[r].low = (int32_t)pe[5 * r]; g.pes[r].high = (int32_t)pe[5 * r + 1]; g.pes[r].failed = (int32_t)pe[5 * r + 2];
-      g.pes[r].avg = pe[5 * r + 3]; g.pes[r].std = pe[5 * r + 4];
-    }
+    decode_pes(pe, g.pes);
   }
   const size_t ends = (size_t)ends_j;
   MateScratch& ms = t_ms;
   std::vector<int32_t>&seq_len = ms.seq_len, &reg_cnt = ms.reg_cnt, &ref_cnt = ms.ref_cnt;
-  std::vector<int64_t>&seq_off = ms.seq_off, &ref_rb = ms.ref_rb, &ref_re = ms.ref_re, &ref_len = ms.ref_len, &ref_off = ms.ref_off;
+  std::vector<int64_t>&seq_off = ms.seq_off, &ref_len = ms.ref_len, &ref_off = ms.ref_off;
   seq_len.resize(ends + 1); reg_cnt.resize(ends + 1); ref_cnt.resize(ends + 1); seq_off.resize(ends + 1);
   if (ends) {
     jni::GetIntArrayRegion(env, seqLenArr, 0, ends_j, seq_len.data());
@@ -873,32 +887,21 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJ
   seq_pool.clear(); ref_pool.clear();
   if (seq_bytes) jni::GetByteArrayRegion(env, seqsArr, 0, (jsize)seq_bytes, reinterpret_cast<jbyte*>(seq_pool.grow((size_t)seq_bytes)));
   memset(seq_pool.grow(16), 0, 16);
-  std::vector<bpsw_alnreg_t>& regs = ms.regs;
-  regs.resize((size_t)n_regs + 1);
-  {
-    std::vector<int64_t>& rl = ms.at;    // (scratch vectors of the object-array entry, reused)
-    std::vector<int32_t>& ri = ms.out_cnt;
-    rl.resize((size_t)(3 * n_regs) + 1); ri.resize((size_t)(10 * n_regs) + 1);
-    if (n_regs) {
-      jni::GetLongArrayRegion(env, regLongsArr, 0, (jsize)(3 * n_regs), reinterpret_cast<jlong*>(rl.data()));
-      jni::GetIntArrayRegion(env, regIntsArr, 0, (jsize)(10 * n_regs), ri.data());
-    }
-    for (int64_t j = 0; j < n_regs; ++j) {
-      bpsw_alnreg_t& a = regs[(size_t)j];
-      const int32_t* v = ri.data() + 10 * j;
-      a.rb = rl[(size_t)(3 * j)]; a.re = rl[(size_t)(3 * j + 1)]; a.hash = (uint64_t)rl[(size_t)(3 * j + 2)];
-      a.qb = v[0]; a.qe = v[1]; a.score = v[2]; a.truesc = v[3]; a.sub = v[4]; a.csub = v[5]; a.sub_n = v[6]; a.w = v[7]; a.seedcov = v[8];
-      a.secondary = v[9];
-    }
+  ms.regs.resize((size_t)n_regs + 1);
+  ms.reg_longs.resize((size_t)(3 * n_regs) + 1); ms.reg_ints.resize((size_t)(10 * n_regs) + 1);
+  if (n_regs) {
+    jni::GetLongArrayRegion(env, regLongsArr, 0, (jsize)(3 * n_regs), ms.reg_longs.data());
+    jni::GetIntArrayRegion(env, regIntsArr, 0, (jsize)(10 * n_regs), ms.reg_ints.data());
   }
-  ref_rb.resize((size_t)(4 * rows) + 1); ref_re.resize((size_t)(4 * rows) + 1);
+  decode_regions(ms.reg_longs.data(), 3, ms.reg_ints.data(), n_regs, ms.regs.data());
+  ms.ref_rb.resize((size_t)(4 * rows) + 1); ms.ref_re.resize((size_t)(4 * rows) + 1);
   if (rows) {
-    jni::GetLongArrayRegion(env, refRbArr, 0, (jsize)(4 * rows), reinterpret_cast<jlong*>(ref_rb.data()));
-    jni::GetLongArrayRegion(env, refReArr, 0, (jsize)(4 * rows), reinterpret_cast<jlong*>(ref_re.data()));
+    jni::GetLongArrayRegion(env, refRbArr, 0, (jsize)(4 * rows), ms.ref_rb.data());
+    jni::GetLongArrayRegion(env, refReArr, 0, (jsize)(4 * rows), ms.ref_re.data());
   }
   if (refLenArr) {
     ref_len.resize((size_t)(4 * rows) + 1); ref_off.resize((size_t)(4 * rows) + 1);
-    if (rows) jni::GetLongArrayRegion(env, refLenArr, 0, (jsize)(4 * rows), reinterpret_cast<jlong*>(ref_len.data()));
+    if (rows) jni::GetLongArrayRegion(env, refLenArr, 0, (jsize)(4 * rows), ref_len.data());
     int64_t ref_bytes = 0;
     for (int64_t x = 0; x < 4 * rows; ++x) {
       if (ref_len[(size_t)x] < 0) { throw_runtime(env, "bPSW: mateSWFlatJNI: negative window length"); return nullptr; }
@@ -908,32 +911,23 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJ
     if ((int64_t)jni::GetArrayLength(env, refBytesArr) < ref_bytes) { throw_runtime(env, "bPSW: mateSWFlatJNI: refBytes shorter than refLen says"); return nullptr; }
     if (ref_bytes) jni::GetByteArrayRegion(env, refBytesArr, 0, (jsize)ref_bytes, reinterpret_cast<jbyte*>(ref_pool.grow((size_t)ref_bytes)));
     memset(ref_pool.grow(16), 0, 16);
-    g.ref_len = ref_len.data(); g.ref_off = ref_off.data(); g.ref_pool = ref_pool.p; g.ref_pool_bytes = ref_pool.n;
   }
-  g.seq_len = seq_len.data(); g.seq_off = seq_off.data(); g.seq_pool = seq_pool.p; g.seq_pool_bytes = seq_pool.n;
-  g.reg_cnt = reg_cnt.data(); g.regs = regs.data(); g.ref_cnt = ref_cnt.data(); g.ref_rb = ref_rb.data(); g.ref_re = ref_re.data();
+  fill_group(g, ms, refLenArr == nullptr);
 
   bpsw_ctx_t* ctx = thread_context(env);
-  if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return nullptr; }
-  std::vector<int32_t>& out_cnt = ms.tmp_cnt;
+  if (!ctx) return nullptr;
+  std::vector<int32_t>& out_cnt = ms.out_cnt;
   std::vector<bpsw_alnreg_t>& out = ms.out;
   out_cnt.resize(ends ? ends : 1);
   out.resize((size_t)n_regs + (size_t)rows + 16);
   int64_t total = 0;
   const double t1 = now_us();
-  const char* compat = getenv("BPSW_MATESW_COMPAT");
-  const int mode = (compat && strcmp(compat, "scala") == 0) ? BPSW_RESCUE_SCALA : BPSW_RESCUE_C;
-  int rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), &total);
-  if (rc == BPSW_ERR_CAPACITY) {
-    out.resize((size_t)total);
-    rc = bpsw_matesw_group(ctx, &opt, &g, mode, out_cnt.data(), out.data(), (int64_t)out.size(), &total);
-  }
-  if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: mateSWFlatJNI: ") + bpsw_last_error()); return nullptr; }
+  if (!run_rescue(env, ctx, "mateSWFlatJNI", opt, g, out_cnt, out, &total)) return nullptr;
 
   const double t2 = now_us();
   const int64_t n_out = (int64_t)ends + 8 * total;
   if (n_out > 0x7fffffffLL) { throw_runtime(env, "bPSW: mateSWFlatJNI: result exceeds a Java array; use a smaller group"); return nullptr; }
-  std::vector<int64_t>& res = ms.base;
+  std::vector<int64_t>& res = ms.result;
   res.resize((size_t)n_out + 1);
   for (size_t e = 0; e < ends; ++e) res[e] = out_cnt[e];
   const auto pack = [](int32_t lo, int32_t hi) { return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo); };
@@ -945,41 +939,24 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJ
   }
   jlongArray ret = jni::NewLongArray(env, (jsize)n_out);
   if (!ret) return nullptr;  // OutOfMemoryError already pending
-  if (n_out) jni::SetLongArrayRegion(env, ret, 0, (jsize)n_out, reinterpret_cast<const jlong*>(res.data()));
+  if (n_out) jni::SetLongArrayRegion(env, ret, 0, (jsize)n_out, res.data());
   t_times = {t1 - t0, t2 - t1, now_us() - t2, (double)total};
   return ret;
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: mateSWFlatJNI: ") + e.what());
-    return nullptr;
-  }
+  });
 }
 
 // ---- reference on the device -------------------------------------------------------------
 // Scala side (one line in jni/MateSWJNI.scala):  @native def loadPacJNI(pac: Array[Byte], pacLen: Long): Int
 // Call once per executor JVM before the first mateSWJNI; returns the number of devices that now hold the reference.
 JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_loadPacJNI(JNIEnv* env, jobject, jbyteArray pacArr, jlong pacLen) {
-  try {
+  return jni_entry(env, "loadPacJNI", jint(0), [&]() -> jint {
   if (!pacArr || pacLen < 1) { throw_runtime(env, "bPSW: loadPacJNI: bad arguments"); return 0; }
   const jsize bytes = jni::GetArrayLength(env, pacArr);
   if ((int64_t)bytes < (pacLen + 3) / 4) { throw_runtime(env, "bPSW: loadPacJNI: pac shorter than (pacLen+3)/4 bytes"); return 0; }
   std::vector<uint8_t> pac((size_t)bytes);
   jni::GetByteArrayRegion(env, pacArr, 0, bytes, reinterpret_cast<jbyte*>(pac.data()));
-  const int ndev = bpsw_device_count();
-  if (ndev <= 0) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return 0; }
-  int loaded = 0;
-  for (int d = 0; d < ndev; ++d) {  // any task thread may land on any device (partition -> device)
-    bpsw_ctx_t* c = nullptr;
-    int rc = bpsw_create(d, &c);
-    if (rc == BPSW_OK) rc = bpsw_ref_load(c, pac.data(), pacLen);
-    if (c) bpsw_destroy(c);
-    if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: loadPacJNI: ") + bpsw_last_error()); return loaded; }
-    ++loaded;
-  }
-  return loaded;
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: loadPacJNI: ") + e.what());
-    return 0;
-  }
+  return load_on_every_device(env, "loadPacJNI", [&](bpsw_ctx_t* c) { return bpsw_ref_load(c, pac.data(), pacLen); });
+  });
 }
 
 // ---- the whole memChainToAlnBatched round loop in one call -------------------------------------
@@ -994,7 +971,7 @@ JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_loadPacJNI(JNIEnv
 JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_chainToAlnJNI(
     JNIEnv* env, jobject, jintArray optInts, jbyteArray matArr, jintArray readLenArr, jbyteArray readsArr, jintArray chainCntArr,
     jintArray seedCntArr, jlongArray seedRBegArr, jintArray seedQBegArr, jintArray seedLenArr) {
-  try {
+  return jni_entry(env, "chainToAlnJNI", jlongArray(nullptr), [&]() -> jlongArray {
   if (!optInts || !matArr || !readLenArr || !readsArr || !chainCntArr || !seedCntArr || !seedRBegArr || !seedQBegArr || !seedLenArr ||
       jni::GetArrayLength(env, optInts) < 10 || jni::GetArrayLength(env, matArr) < 25) {
     throw_runtime(env, "bPSW: chainToAlnJNI: bad arguments");
@@ -1042,7 +1019,7 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_chain
   b.n_reads = n; b.read_len = read_len.data(); b.read_off = read_off.data(); b.read_pool = pool.data(); b.read_pool_bytes = (size_t)pool_bytes;
   b.chain_cnt = chain_cnt.data(); b.seed_cnt = seed_cnt.data(); b.seed_rbeg = seed_rbeg.data(); b.seed_qbeg = seed_qbeg.data(); b.seed_len = seed_len.data();
   bpsw_ctx_t* ctx = thread_context(env);
-  if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return nullptr; }
+  if (!ctx) return nullptr;
   std::vector<int32_t> out_cnt((size_t)n + 1);
   std::vector<bpsw_alnreg_t> out((size_t)nseeds + 1);
   int64_t total = 0;
@@ -1063,10 +1040,7 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_chain
   if (!ret) return nullptr;  // OutOfMemoryError already pending
   if (!flat.empty()) jni::SetLongArrayRegion(env, ret, 0, (jsize)flat.size(), flat.data());
   return ret;
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: chainToAlnJNI: ") + e.what());
-    return nullptr;
-  }
+  });
 }
 
 // ---- worker2's tail -----------------------------------------------------------------------------
@@ -1075,7 +1049,7 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_chain
 // Call once per executor JVM after loadPacJNI (bns.anns(i).offset / .len / .name); returns the number of devices loaded.
 JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_loadBnsJNI(JNIEnv* env, jobject, jlongArray offArr, jintArray lenArr,
                                                                           jbyteArray namesArr) {
-  try {
+  return jni_entry(env, "loadBnsJNI", jint(0), [&]() -> jint {
   if (!offArr || !lenArr) { throw_runtime(env, "bPSW: loadBnsJNI: bad arguments"); return 0; }
   const jsize n = jni::GetArrayLength(env, offArr);
   if (n < 1 || jni::GetArrayLength(env, lenArr) != n) { throw_runtime(env, "bPSW: loadBnsJNI: offset and len must have one entry per contig"); return 0; }
@@ -1092,22 +1066,10 @@ JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_loadBnsJNI(JNIEnv
     for (jsize i = 0; i < nb; ++i) zeros += names[(size_t)i] == 0;
     if (zeros < n) { throw_runtime(env, "bPSW: loadBnsJNI: fewer NUL-terminated names than contigs"); return 0; }
   }
-  const int ndev = bpsw_device_count();
-  if (ndev <= 0) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return 0; }
-  int loaded = 0;
-  for (int d = 0; d < ndev; ++d) {
-    bpsw_ctx_t* c = nullptr;
-    int rc = bpsw_create(d, &c);
-    if (rc == BPSW_OK) rc = bpsw_bns_load(c, n, reinterpret_cast<const int64_t*>(off.data()), len.data(), namesArr ? names.data() : nullptr);
-    if (c) bpsw_destroy(c);
-    if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: loadBnsJNI: ") + bpsw_last_error()); return loaded; }
-    ++loaded;
-  }
-  return loaded;
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: loadBnsJNI: ") + e.what());
-    return 0;
-  }
+  return load_on_every_device(env, "loadBnsJNI", [&](bpsw_ctx_t* c) {
+    return bpsw_bns_load(c, n, off.data(), len.data(), namesArr ? names.data() : nullptr);
+  });
+  });
 }
 
 // Scala side (jni/MateSWJNI.scala); replaces the body of memSamPeGroupRest (worker2/MemSamPe.scala:1390-1612):
@@ -1207,20 +1169,11 @@ bool tail_unmarshal(JNIEnv* env, const char* who, jintArray optInts, jdoubleArra
   std::vector<jint> ri((size_t)(10 * n_regs) + 1);
   if (n_regs) { jni::GetLongArrayRegion(env, regLongsArr, 0, (jsize)(2 * n_regs), rl.data()); jni::GetIntArrayRegion(env, regIntsArr, 0, (jsize)(10 * n_regs), ri.data()); }
   tc.regs.resize((size_t)n_regs + 1);
-  for (int64_t j = 0; j < n_regs; ++j) {
-    bpsw_alnreg_t& a = tc.regs[(size_t)j];
-    const jint* v = ri.data() + 10 * j;
-    a.rb = rl[(size_t)(2 * j)]; a.re = rl[(size_t)(2 * j + 1)];
-    a.qb = v[0]; a.qe = v[1]; a.score = v[2]; a.truesc = v[3]; a.sub = v[4]; a.csub = v[5]; a.sub_n = v[6]; a.w = v[7]; a.seedcov = v[8];
-    a.secondary = v[9]; a.hash = 0;
-  }
+  decode_regions(rl.data(), 2, ri.data(), n_regs, tc.regs.data());
   bpsw_pairs_t& g = tc.g;
   memset(&g, 0, sizeof g);
   g.group_size = G; g.id0 = id0;
-  for (int r = 0; r < 4; ++r) {
-    g.pes[r].low = (int32_t)re[2 + 5 * r]; g.pes[r].high = (int32_t)re[3 + 5 * r]; g.pes[r].failed = (int32_t)re[4 + 5 * r];
-    g.pes[r].avg = re[5 + 5 * r]; g.pes[r].std = re[6 + 5 * r];
-  }
+  decode_pes(re + 2, g.pes);
   g.read_len = tc.read_len.data(); g.read_off = tc.read_off.data(); g.read_pool = tc.reads.data(); g.qual_pool = qualsArr ? tc.quals.data() : nullptr;
   g.read_pool_bytes = (size_t)at; g.name_off = tc.name_off.data(); g.name_pool = tc.names.data(); g.reg_cnt = tc.reg_cnt.data(); g.regs = tc.regs.data();
   tc.out_off.assign((size_t)n2 + 1, 0);
@@ -1265,13 +1218,13 @@ JNIEXPORT jbyteArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailJN
     JNIEnv* env, jobject, jintArray optInts, jdoubleArray realsArr, jbyteArray matArr, jlong id0, jintArray readLenArr, jbyteArray readsArr,
     jbyteArray qualsArr, jintArray nameLenArr, jbyteArray namesArr, jintArray regCntArr, jlongArray regLongsArr, jintArray regIntsArr,
     jlongArray outOffArr) {
-  try {
+  return jni_entry(env, "samPeTailJNI", jbyteArray(nullptr), [&]() -> jbyteArray {
   TailCall tc;
   if (!tail_unmarshal(env, "samPeTailJNI", optInts, realsArr, matArr, id0, readLenArr, readsArr, qualsArr, nameLenArr, namesArr, regCntArr,
                       regLongsArr, regIntsArr, tc)) return nullptr;
   if (!outOffArr || jni::GetArrayLength(env, outOffArr) < tc.n2 + 1) { throw_runtime(env, "bPSW: samPeTailJNI: outOff needs 2*groupSize + 1 entries"); return nullptr; }
   bpsw_ctx_t* ctx = thread_context(env);
-  if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return nullptr; }
+  if (!ctx) return nullptr;
   size_t need = 0;
   int rc = bpsw_sam_pe_batch(ctx, &tc.opt, &tc.topt, &tc.g, tc.text.data(), tc.text.size(), tc.out_off.data(), &need, nullptr);
   if (rc == BPSW_ERR_CAPACITY && need > tc.text.size()) {
@@ -1280,10 +1233,7 @@ JNIEXPORT jbyteArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailJN
   }
   if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: samPeTailJNI: ") + bpsw_last_error()); return nullptr; }
   return tail_result(env, "samPeTailJNI", tc, need, outOffArr);
-  } catch (const std::exception& e) {  // nothing C++ may unwind into the JVM (std::bad_alloc of a scratch vector, ...)
-    throw_runtime(env, std::string("bPSW: samPeTailJNI: ") + e.what());
-    return nullptr;
-  }
+  });
 }
 
 // The same call in two halves (round 5): the task thread only ENQUEUES its groups -- the arguments are copied into native buffers behind
@@ -1295,12 +1245,12 @@ JNIEXPORT jbyteArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailJN
 JNIEXPORT jlong JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailSubmitJNI(
     JNIEnv* env, jobject, jintArray optInts, jdoubleArray realsArr, jbyteArray matArr, jlong id0, jintArray readLenArr, jbyteArray readsArr,
     jbyteArray qualsArr, jintArray nameLenArr, jbyteArray namesArr, jintArray regCntArr, jlongArray regLongsArr, jintArray regIntsArr) {
-  try {
+  return jni_entry(env, "samPeTailSubmitJNI", jlong(0), [&]() -> jlong {
   std::unique_ptr<TailCall> tc(new TailCall());
   if (!tail_unmarshal(env, "samPeTailSubmitJNI", optInts, realsArr, matArr, id0, readLenArr, readsArr, qualsArr, nameLenArr, namesArr, regCntArr,
                       regLongsArr, regIntsArr, *tc)) return 0;
   bpsw_ctx_t* ctx = thread_context(env);  // (the partition -> device choice of every other entry)
-  if (!ctx) { throw_runtime(env, std::string("bPSW: no usable HIP device: ") + bpsw_last_error()); return 0; }
+  if (!ctx) return 0;
   tc->pool = tail_pool_of(bpsw_device_of(ctx));
   if (!tc->pool) { throw_runtime(env, std::string("bPSW: samPeTailSubmitJNI: ") + bpsw_last_error()); return 0; }
   if (bpsw_tail_pool_submit(tc->pool, &tc->opt, &tc->topt, &tc->g, BPSW_TAIL_POOL_TAIL_ONLY, tc->text.data(), tc->text.size(), tc->out_off.data(),
@@ -1312,14 +1262,11 @@ JNIEXPORT jlong JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailSubmitJ
   const int64_t h = g_tail_next++;
   g_tail_calls[h] = std::move(tc);
   return (jlong)h;
-  } catch (const std::exception& e) {
-    throw_runtime(env, std::string("bPSW: samPeTailSubmitJNI: ") + e.what());
-    return 0;
-  }
+  });
 }
 
 JNIEXPORT jbyteArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCollectJNI(JNIEnv* env, jobject, jlong handle, jlongArray outOffArr) {
-  try {
+  return jni_entry(env, "samPeTailCollectJNI", jbyteArray(nullptr), [&]() -> jbyteArray {
   std::unique_ptr<TailCall> tc;
   {
     std::lock_guard<std::mutex> lk(g_tail_mu);
@@ -1339,10 +1286,7 @@ JNIEXPORT jbyteArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCo
   if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: samPeTailCollectJNI: ") + bpsw_last_error()); return nullptr; }
   if (!outOffArr || jni::GetArrayLength(env, outOffArr) < tc->n2 + 1) { throw_runtime(env, "bPSW: samPeTailCollectJNI: outOff needs 2*groupSize + 1 entries"); return nullptr; }
   return tail_result(env, "samPeTailCollectJNI", *tc, need, outOffArr);
-  } catch (const std::exception& e) {
-    throw_runtime(env, std::string("bPSW: samPeTailCollectJNI: ") + e.what());
-    return nullptr;
-  }
+  });
 }
 
 // A handle that will not be collected (the Spark task failed or was killed between submit and collect): wait for the group's ticket -- a
@@ -1351,7 +1295,7 @@ JNIEXPORT jbyteArray JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCo
 // of the executor JVM (advisor, round 5).  Unknown handles (collected already, never issued) are ignored; returns 1 when one was dropped.
 //   @native def samPeTailCancelJNI(handle: Long): Int
 JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCancelJNI(JNIEnv* env, jobject, jlong handle) {
-  try {
+  return jni_entry(env, "samPeTailCancelJNI", jint(0), [&]() -> jint {
   std::unique_ptr<TailCall> tc;
   {
     std::lock_guard<std::mutex> lk(g_tail_mu);
@@ -1363,10 +1307,7 @@ JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCancelJN
   size_t need = 0;
   (void)bpsw_tail_pool_wait(tc->pool, tc->ticket, &need, nullptr);  // (whatever it returns: the worker is done with the buffers afterwards)
   return 1;
-  } catch (const std::exception& e) {
-    throw_runtime(env, std::string("bPSW: samPeTailCancelJNI: ") + e.what());
-    return 0;
-  }
+  });
 }
 
 }  // extern "C"
