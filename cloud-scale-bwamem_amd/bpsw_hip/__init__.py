@@ -25,12 +25,12 @@ KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
 
 # every symbol include/bpsw.h declares (tests check the built library exports all of them)
 ABI_SYMBOLS = [
-    "bpsw_device_count", "bpsw_create", "bpsw_destroy", "bpsw_device_of", "bpsw_device_slots", "bpsw_device_for_partition", "bpsw_last_error", "bpsw_version",
+    "bpsw_device_count", "bpsw_create", "bpsw_destroy", "bpsw_device_of", "bpsw_device_cus", "bpsw_device_slots", "bpsw_device_for_partition", "bpsw_last_error", "bpsw_version",
     "bpsw_set_ext_scoring", "bpsw_set_ext_shortcuts", "bpsw_extend_batch", "bpsw_extend_stage", "bpsw_extend_commit", "bpsw_extend_batch_classify", "bpsw_extend_batch_device", "bpsw_wire_size", "bpsw_wire_pack", "bpsw_wire_coords_size", "bpsw_wire_coords_pack",
     "bpsw_opt_default", "bpsw_swalign2_batch", "bpsw_swalign2_batch_device", "bpsw_matesw_group", "bpsw_global_batch",
     "bpsw_get_stats", "bpsw_reset_stats", "bpsw_last_kernel_ms", "bpsw_ring_stats", "bpsw_sw_batches_in_flight", "bpsw_ring_integrity",
     "bpsw_ref_load", "bpsw_ref_unload", "bpsw_ref_length", "bpsw_ref_fetch", "bpsw_chain2aln_batch",
-    "bpsw_tail_opt_default", "bpsw_bns_load", "bpsw_reg2aln_batch", "bpsw_sam_pe_batch", "bpsw_worker2_batch", "bpsw_last_tail_times",
+    "bpsw_tail_opt_default", "bpsw_bns_load", "bpsw_reg2aln_batch", "bpsw_sam_pe_batch", "bpsw_worker2_batch", "bpsw_last_tail_times", "bpsw_last_tail_resubmitted",
     "bpsw_tail_pool_create", "bpsw_tail_pool_destroy", "bpsw_tail_pool_submit", "bpsw_tail_pool_wait", "bpsw_tail_pool_workers",
     "bpsw_mark_primary_se", "bpsw_approx_mapq_se", "bpsw_mem_pair", "bpsw_sort_dedup", "bpsw_pe_stat",
 ]
@@ -157,6 +157,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.bpsw_destroy.argtypes = [C.c_void_p]
     lib.bpsw_destroy.restype = None
     lib.bpsw_device_of.argtypes = [C.c_void_p]
+    lib.bpsw_device_cus.argtypes = [C.c_void_p]
     lib.bpsw_set_ext_scoring.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.bpsw_set_ext_shortcuts.argtypes = [C.c_void_p, C.c_int]
     lib.bpsw_extend_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -209,6 +210,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.bpsw_sort_dedup.argtypes = [C.c_int32, C.c_void_p, C.c_float, C.c_int]
     lib.bpsw_pe_stat.argtypes = [C.POINTER(Opt), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bpsw_last_tail_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p]
+    lib.bpsw_last_tail_resubmitted.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     if path is None:
         _lib = lib
     return lib
@@ -776,6 +778,13 @@ def _ctx_last_tail_kernel(self):
     return ms.value, n.value
 
 
+def _ctx_last_tail_resubmitted(self):
+    """jobs of the most recent tail call that were launched again with more room for their CIGAR / MD (once per extra launch)"""
+    n = C.c_int32(0)
+    _chk(self.lib, self.lib.bpsw_last_tail_resubmitted(self.h, C.byref(n)), "bpsw_last_tail_resubmitted")
+    return n.value
+
+
 def _ctx_last_tail_host_ms(self):
     """(plan, device round trip, emit) ms of the most recent bpsw_sam_pe_batch"""
     h = (C.c_double * 3)()
@@ -862,6 +871,8 @@ Context.sam_pe_batch = _ctx_sam_pe_batch
 Context.worker2_batch = _ctx_worker2_batch
 Context.last_tail_kernel = _ctx_last_tail_kernel
 Context.last_tail_host_ms = _ctx_last_tail_host_ms
+Context.last_tail_resubmitted = _ctx_last_tail_resubmitted
+Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute units of the context's device
 
 
 # ---- host-only pieces (no device): usable and testable on a CPU-only box -------------------------------------------------

@@ -56,7 +56,7 @@ __global__ void global_prepass_kernel(const GlobalJobsDev jobs, const unsigned l
     const int ql = jobs.q_len[j], tl = jobs.t_len[j], w = jobs.w[j];
     const long long qo = jobs.q_off[j], to = jobs.t_off[j];
     if (ql < 1 || tl < 1 || w < 0 || w > 0x3fffffff || qo < 0 || to < 0 || (unsigned long long)(qo + ql) > q_pool_bytes ||
-        (unsigned long long)(to + tl) > t_pool_bytes) {
+        (unsigned long long)(to + tl) > t_pool_bytes || w < (tl > ql ? tl - ql : ql - tl)) {  // (band rule: include/bpsw.h)
       err = 1;
       continue;
     }
@@ -100,9 +100,7 @@ hipError_t launch_global_kernel(const GlobalJobsDev& jobs, const SwScoring& sc, 
   const size_t per_wave = global_lds_per_wave(qcap);
   const size_t lds = per_wave * WAVES_PER_BLOCK;
   if (lds > 64 * 1024) return hipErrorInvalidValue;  // qLen <= BPSW_GLOBAL_MAX_QLEN keeps this below 64 KB
-  int blocks = (jobs.n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-  const int max_blocks = global_resident_waves(num_cu, qcap) / WAVES_PER_BLOCK;
-  if (blocks > max_blocks) blocks = max_blocks;
+  const int blocks = launch_waves(global_resident_waves(num_cu, qcap), jobs.n) / WAVES_PER_BLOCK;
   hipLaunchKernelGGL(global_kernel, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, jobs, sc, d_score, d_ncigar, d_cigar,
                      d_z, (unsigned long long)z_per_wave, qcap, (int)per_wave);
   return hipGetLastError();

@@ -204,6 +204,12 @@ struct GlobalPrepass {
   int error;
   unsigned long long max_z;  // max over jobs of nCol * tLen (bytes of backtrack matrix)
 };
+// The waves a launch of the global / reg2aln kernel over n jobs starts: whole blocks of four, at most the resident ones.  The z scratch
+// is sized for these and not for every resident wave.  (Inline: the host code needs nothing of the kernels' files but *_resident_waves.)
+inline int launch_waves(int resident, int n) {
+  const long long whole = ((long long)n + 3) / 4 * 4;
+  return whole < resident ? (int)whole : resident;
+}
 void launch_global_prepass(const GlobalJobsDev& jobs, size_t q_pool_bytes, size_t t_pool_bytes, GlobalPrepass* d_pre, hipStream_t s);
 int global_resident_waves(int num_cu, int qcap);
 hipError_t launch_global_kernel(const GlobalJobsDev& jobs, const SwScoring& sc, int max_qlen, size_t z_per_wave,

@@ -337,9 +337,7 @@ hipError_t launch_reg2aln_kernel(const Reg2AlnDev& J, const SwScoring& sc, int q
   const size_t per_wave = reg2aln_lds_per_wave(qcap, rcap, md_cap);
   const size_t lds = per_wave * WAVES_PER_BLOCK;
   if (lds > 64 * 1024) return hipErrorInvalidValue;
-  int blocks = (J.n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-  const int max_blocks = reg2aln_resident_waves(num_cu, qcap, rcap, md_cap) / WAVES_PER_BLOCK;
-  if (blocks > max_blocks) blocks = max_blocks;
+  const int blocks = launch_waves(reg2aln_resident_waves(num_cu, qcap, rcap, md_cap), J.n) / WAVES_PER_BLOCK;
   hipLaunchKernelGGL(reg2aln_kernel, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, J, sc, d_out, d_cigar, d_md, d_z,
                      (unsigned long long)z_per_wave, qcap, rcap, md_cap, (int)per_wave);
   return hipGetLastError();

@@ -474,6 +474,7 @@ void bpsw_destroy(bpsw_ctx_t* c) {
 }
 
 int bpsw_device_of(const bpsw_ctx_t* c) { return c ? c->device : -1; }
+int bpsw_device_cus(const bpsw_ctx_t* c) { return c ? c->num_cu : -1; }
 
 int bpsw_set_ext_shortcuts(bpsw_ctx_t* c, int mask) {
   if (!c) return fail(BPSW_ERR_ARG, "null context");

@@ -600,6 +600,9 @@ int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jo
         (unsigned long long)(to + tl) > j->t_pool_bytes)
       return fail(BPSW_ERR_ARG, "global: job sequence outside its pool (or empty)");
     if (ql > BPSW_GLOBAL_MAX_QLEN || tl > BPSW_GLOBAL_MAX_TLEN) return fail(BPSW_ERR_LIMIT, "global: sequence longer than the kernel limit");
+    // a band narrower than the length difference leaves the last cell outside it: the reference defines no alignment there
+    // (score -2^30, CIGAR by accident), and the backtrack would leave the row's nCol bytes
+    if (w < (tl > ql ? tl - ql : ql - tl)) return fail(BPSW_ERR_ARG, "global: band w narrower than |t_len - q_len|");
     const long long ncol = ql < 2ll * w + 1 ? ql : 2ll * w + 1;
     if ((size_t)(ncol * tl) > mz) mz = (size_t)(ncol * tl);
     if (ql > mq) mq = ql;
@@ -618,7 +621,7 @@ int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jo
   HIP_TRY(c->d_sw_in.reserve(total));
   HIP_TRY(c->h_stage_out.reserve(out_bytes));
   HIP_TRY(c->d_sw_out.reserve(out_bytes));
-  HIP_TRY(c->d_gl_z.reserve(z_per_wave * (size_t)global_resident_waves(c->num_cu, qcap)));
+  HIP_TRY(c->d_gl_z.reserve(z_per_wave * (size_t)launch_waves(global_resident_waves(c->num_cu, qcap), n)));
   uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
   memcpy(h + o_qlen, j->q_len, 4 * (size_t)n); memcpy(h + o_tlen, j->t_len, 4 * (size_t)n); memcpy(h + o_w, j->w, 4 * (size_t)n);
   memcpy(h + o_qoff, j->q_off, 8 * (size_t)n); memcpy(h + o_toff, j->t_off, 8 * (size_t)n);
@@ -638,7 +641,12 @@ int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jo
   const uint8_t* ho = (const uint8_t*)c->h_stage_out.ptr;
   memcpy(out_score, ho + o_score, 4 * (size_t)n);
   memcpy(out_ncigar, ho + o_nc, 4 * (size_t)n);
-  memcpy(out_cigar, ho + o_cig, 4 * (size_t)n * (size_t)j->max_cigar);
+  // a job's operations, and nothing else: the device block is not cleared between calls, so the words behind a job's count -- and the
+  // whole row of a job that did not fit -- hold what earlier launches left there, and stay out of the caller's array
+  const int32_t* nc = (const int32_t*)(ho + o_nc);
+  const uint32_t* hc = (const uint32_t*)(ho + o_cig);
+  for (int i = 0; i < n; ++i)
+    if (nc[i] > 0 && nc[i] <= j->max_cigar) memcpy(out_cigar + (size_t)i * (size_t)j->max_cigar, hc + (size_t)i * (size_t)j->max_cigar, 4 * (size_t)nc[i]);
   return BPSW_OK;
 }
 

@@ -126,7 +126,7 @@ int launch_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int fla
   HIP_TRY(c->d_sw_in.reserve(total));
   HIP_TRY(c->h_stage_out.reserve(out_bytes));
   HIP_TRY(c->d_sw_out.reserve(out_bytes));
-  HIP_TRY(c->d_gl_z.reserve(z_per_wave * (size_t)reg2aln_resident_waves(c->num_cu, qcap, rcap, md_cap)));
+  HIP_TRY(c->d_gl_z.reserve(z_per_wave * (size_t)launch_waves(reg2aln_resident_waves(c->num_cu, qcap, rcap, md_cap), n)));
   uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
   memcpy(h + o_len, read_len, 4 * (size_t)n);
   long long* ho = (long long*)(h + o_off);
@@ -1043,5 +1043,12 @@ int bpsw_last_tail_times(bpsw_ctx_t* c, float* kernel_ms, int32_t* n_jobs, doubl
   if (kernel_ms) *kernel_ms = c->have_tail_ev ? c->last_tail_ms : 0.f;
   if (n_jobs) *n_jobs = c->have_tail_ev ? c->last_tail_jobs - c->last_tail_resubmitted : 0;  // distinct (read, region) jobs
   if (host_ms) for (int i = 0; i < 3; ++i) host_ms[i] = c->tail_host_ms[i];
+  return BPSW_OK;
+}
+
+int bpsw_last_tail_resubmitted(bpsw_ctx_t* c, int32_t* n_resubmitted) {
+  if (!c || !n_resubmitted) return fail(BPSW_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> g(c->mu);
+  *n_resubmitted = c->have_tail_ev ? c->last_tail_resubmitted : 0;
   return BPSW_OK;
 }

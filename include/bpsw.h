@@ -67,6 +67,7 @@ int bpsw_device_count(void);
 int bpsw_create(int device, bpsw_ctx_t **out);
 void bpsw_destroy(bpsw_ctx_t *ctx);
 int bpsw_device_of(const bpsw_ctx_t *ctx);
+int bpsw_device_cus(const bpsw_ctx_t *ctx); /* compute units of its device: what the kernels' resident-wave counts are sized by */
 /* Spark partition -> device (the north_star's "Spark-partition -> device index"; reference: one accelerator per executor,
  * src/main/jni_fpga/sw_extend_fpga.c:116-193).  The devices contexts are spread over are the entries of BPSW_DEVICES
  * ("0,2,3"; an index may repeat; default: every visible device in order); partition p runs on entry p mod count. */
@@ -238,8 +239,16 @@ int bpsw_matesw_group(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_rescue_
  * directly), so this is an additional export for callers that want CIGARs from the device.
  * Job t aligns q_pool[q_off[t]..+q_len[t]) to t_pool[t_off[t]..+t_len[t]) globally inside the band w[t]
  * (the caller applies the band rule of MemRegToADAMSAM.scala:794-804 and the strand reversal of :764-781).
+ * Every job must have w[t] >= |t_len[t] - q_len[t]|: under a narrower band the last cell lies outside the band, neither the
+ * Scala nor ksw_global2 defines an alignment there (both return the score -2^30 and an accidental CIGAR), and the call is
+ * refused with BPSW_ERR_ARG.  (bwaGenCigar2 never asks for less than |t_len - q_len| + 3.)
+ * Scratch: the call reserves max_t(min(q_len, 2w+1) * t_len) bytes of device memory for every wavefront the launch starts
+ * (the jobs rounded up to a multiple of 4, at most the waves resident on the device), so one job at both limits takes
+ * 4 x 67 MB, and a batch of thousands of such jobs as many times 67 MB as there are resident waves (about two thousand).
  * out_score[t]; out_ncigar[t] = number of operations; out_cigar[t*max_cigar ..] = len<<4|op (0=M 1=I 2=D).
- * If out_ncigar[t] > max_cigar that job's operations were not written: resubmit it with a larger max_cigar (<= 512).
+ * If out_ncigar[t] > max_cigar that job's operations were not written: resubmit it with a larger max_cigar (<= 512); a job of
+ * more than 512 operations reports its count and cannot be produced.  Only out_ncigar[t] words of a job's row are written, and
+ * none of a job that did not fit: the rest of out_cigar is left as the caller passed it.
  */
 #define BPSW_GLOBAL_MAX_QLEN 1023
 #define BPSW_GLOBAL_MAX_TLEN 65535
@@ -333,6 +342,11 @@ int bpsw_chain2aln_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_chai
 #define BPSW_MEM_F_NO_MULTI 0x10
 #define BPSW_R2A_MAX_QLEN 1024 /* read length */
 #define BPSW_R2A_MAX_RLEN 4096 /* re - rb of a region */
+/* The two limits above are tested per job; together they are bounded by the kernel's staging of one job per wavefront in LDS.
+ * With Q = the longest read and R = the longest region (re - rb) of a launch, each rounded up to a multiple of 32, a launch
+ * passes when 16 Q + 2 R + 2096 <= 16384, i.e. 8 Q + R <= 7144, and is refused with BPSW_ERR_LIMIT otherwise (one long job
+ * refuses its whole call).  So: reads up to 352 bases go with regions up to 4096; 512 with 3040; 640 with 2016; 768 with 992;
+ * 864 with 224; reads of 865 bases and more are always refused, BPSW_R2A_MAX_QLEN notwithstanding. */
 
 typedef struct { /* the MemOptType fields only the tail reads (datatype/MemOptType.scala:47-52) */
   float mask_level, mapq_coef_len;
@@ -438,6 +452,9 @@ int bpsw_tail_pool_workers(const bpsw_tail_pool_t *pool);
 /* the most recent tail call on this context: kernel_ms = reg2aln_kernel launches (hipEvents on the launch stream), n_jobs =
  * jobs they carried, host_ms = {plan, device round trip (staging, copies, kernel), emit} of bpsw_sam_pe_batch */
 int bpsw_last_tail_times(bpsw_ctx_t *ctx, float *kernel_ms, int32_t *n_jobs, double host_ms[3]);
+/* ... and how many of its jobs were launched again because their CIGAR or MD outgrew the room of the launch before (the tail gives
+ * every job room for 16 operations / 64 MD bytes first, then 128 / 512, then 514 / 4096; a job is counted once per extra launch) */
+int bpsw_last_tail_resubmitted(bpsw_ctx_t *ctx, int32_t *n_resubmitted);
 
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {

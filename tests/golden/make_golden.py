@@ -353,6 +353,34 @@ np.savez_compressed(os.path.join(HERE, "ref_extension_tasks.npz"), sets=np.array
                     note="ref_extend_batch: per set s<i>_*: ExtTaskSoA fields + out[n,7] = qBeg,qEnd,rBeg,rEnd,score,trueScore,width; "
                          "sets rows = read_len, sub permille, indel permille, w, zdrop, n; scoring 1/-4/6/1/6/1, clip 5/5, BWA z-drop parse")
 
+# ---- ksw_global2 at the edges (tests/global_cases.py: fixture_subset): query lengths at the 64-column chunk edges and at the length
+# limit, bands at |d| / 32 / 33 / 0 / 2000, homopolymers / tandem repeats / two letters / N, CIGARs of 500-700 operations -- each
+# under five scorings, the scoring stored per entry.  The generator draws from default_rng instances of its own (fixed seeds), so the
+# stream of the sections above does not move.  Entry e aligns job[e]'s sequences under gaps[e] = (o_del, e_del, o_ins, e_ins), mat[e].
+sys.path.insert(0, os.path.dirname(HERE))
+import global_cases  # noqa: E402
+
+picked = global_cases.fixture_subset()
+uniq, job_of = [], {}
+for jb, _ in picked:
+    if id(jb) not in job_of:
+        job_of[id(jb)] = len(uniq)
+        uniq.append(jb)
+scores, cigs = [], []
+for jb, si in picked:
+    s = global_cases.SCORINGS[si]
+    sc, cg = ref.ksw_global2(jb.q, jb.t, s.mat, s.o_del, s.e_del, s.o_ins, s.e_ins, jb.w)
+    scores.append(sc); cigs.append(cg)
+qo, qp = pack([jb.q for jb in uniq]); to, tp = pack([jb.t for jb in uniq])
+co = np.zeros(len(cigs) + 1, np.int64)
+co[1:] = np.cumsum([len(c) for c in cigs])
+np.savez_compressed(os.path.join(HERE, "ksw_global2_edges.npz"), q_off=qo, q_pool=qp, t_off=to, t_pool=tp,
+                    w=np.array([jb.w for jb in uniq], np.int32), job=np.array([job_of[id(jb)] for jb, _ in picked], np.int32),
+                    gaps=np.array([[global_cases.SCORINGS[si][k] for k in (2, 3, 4, 5)] for _, si in picked], np.int32),
+                    mat=np.array([global_cases.SCORINGS[si].mat for _, si in picked], np.int8),
+                    score=np.array(scores, np.int32), cig_off=co, cig_pool=np.concatenate(cigs).astype(np.uint32),
+                    note="ksw_global2(native/ksw.c:501-584) on tests/global_cases.py fixture_subset(); cigar = len<<4|op, op 0=M 1=I 2=D")
+
 if CHECK:
     if _mismatch:
         print("golden fixtures differ from what this script generates now:", ", ".join(_mismatch))

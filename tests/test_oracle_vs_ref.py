@@ -2,6 +2,7 @@
 seeded samples than the committed fixtures.  Skipped where oracle/_ref/libbwaref.so is absent."""
 import numpy as np
 
+import global_cases
 import pyoracle as po
 from bpsw_hip import synth
 from conftest import region_fields_equal
@@ -76,3 +77,49 @@ def test_chain2aln_live(orc, ref):
         for f in regs.dtype.names:
             assert np.array_equal(regs[f], rregs[f]), (L, f)
         assert n_ext > 1000
+
+
+def _global_both(orc, ref, job, s):
+    got = orc.sw_global(job.q, job.t, s.mat, s.o_del, s.e_del, s.o_ins, s.e_ins, job.w)
+    want = ref.ksw_global2(job.q, job.t, s.mat, s.o_del, s.e_del, s.o_ins, s.e_ins, job.w)
+    return got, want
+
+
+def test_sw_global_on_generated_cases(orc, ref):
+    """Every group of tests/global_cases.py but `many` (chunk-edge lengths and bands, up to 12 edits with indels of 40, tie-rich input,
+    CIGARs of 500-700 operations) under its five scorings: the oracle's SWGlobal against the reference's ksw_global2, score and every
+    CIGAR word.  (test_sw_global_on_the_fixture_subset below is the part of it that became tests/golden/ksw_global2_edges.npz.)"""
+    compared = 0
+    for name, make in global_cases.GROUPS.items():
+        jobs = make()
+        for s in global_cases.SCORINGS:
+            for i, job in enumerate(jobs):
+                assert job.w >= abs(len(job.t) - len(job.q)), (name, i)      # in-domain, all of them: nothing is filtered
+                (gs, gc), (ws, wc) = _global_both(orc, ref, job, s)
+                assert gs == ws and gs > global_cases.MINUS_INF // 2, (name, s.name, i, gs, ws)
+                assert np.array_equal(gc, wc), (name, s.name, i, gc, wc)
+                compared += 1
+    print(f"sw_global vs ksw_global2: {compared} jobs compared")
+    assert compared >= 5 * 2000
+
+
+def test_sw_global_on_the_fixture_subset(orc, ref):
+    """the jobs of tests/golden/ksw_global2_edges.npz (a fifth of them, to keep the recording small) through the same comparison"""
+    picked = global_cases.fixture_subset()[::5]
+    for job, si in picked:
+        (gs, gc), (ws, wc) = _global_both(orc, ref, job, global_cases.SCORINGS[si])
+        assert gs == ws and np.array_equal(gc, wc), (si, len(job.q), len(job.t), job.w)
+    assert len(picked) >= 250
+
+
+def test_sw_global_below_the_band_rule_agrees_on_the_score_only(orc, ref):
+    """w < |tLen - qLen|: the last cell is outside the band.  Reference and oracle both answer -2^30; the CIGAR either leaves is an
+    accident of its backtrack (they differ in about one job of eight, and the reference's own differs from run to run) and is NOT
+    compared.  For that reason this test has no recording and runs where the reference is built only.  bpsw_global_batch refuses
+    such jobs."""
+    jobs = global_cases.below_band()
+    for s in global_cases.SCORINGS:
+        for i, job in enumerate(jobs):
+            (gs, _), (ws, _) = _global_both(orc, ref, job, s)
+            assert gs == ws == global_cases.MINUS_INF, (s.name, i, gs, ws)
+    assert len(jobs) >= 400
