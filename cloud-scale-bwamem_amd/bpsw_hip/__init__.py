@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
     "bpsw_tail_opt_default", "bpsw_bns_load", "bpsw_reg2aln_batch", "bpsw_sam_pe_batch", "bpsw_worker2_batch", "bpsw_last_tail_times", "bpsw_last_tail_resubmitted",
     "bpsw_tail_pool_create", "bpsw_tail_pool_destroy", "bpsw_tail_pool_submit", "bpsw_tail_pool_wait", "bpsw_tail_pool_workers",
     "bpsw_mark_primary_se", "bpsw_approx_mapq_se", "bpsw_mem_pair", "bpsw_sort_dedup", "bpsw_pe_stat",
+    "bpsw_fmi_load", "bpsw_fmi_unload", "bpsw_fmi_length", "bpsw_seed_opt_default", "bpsw_seed_batch", "bpsw_chain_seeds",
+    "bpsw_worker1_batch", "bpsw_last_worker1_times", "bpsw_seed_set_resident_lanes",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -46,6 +48,8 @@ JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCollectJNI",
     "Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_samPeTailCancelJNI",    # drop a handle that will not be collected (round 6)
     "Java_cs_ucla_edu_bwaspark_jni_MateSWJNI_mateSWFlatJNI",         # boundary 1 with primitive arrays (round 4)
+    "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_loadFmiJNI",      # worker1 from reads
+    "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_worker1FlatJNI",
 ]
 
 
@@ -211,9 +215,32 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.bpsw_pe_stat.argtypes = [C.POINTER(Opt), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bpsw_last_tail_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p]
     lib.bpsw_last_tail_resubmitted.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    _bind_seeding(lib)
     if path is None:
         _lib = lib
     return lib
+
+
+def _bind_seeding(lib):
+    """The seeding entries (bpsw_seed.hip, bpsw_chain.cpp).  Bound only where the library has them: the host-only sanitizer builds
+    (tests/host_san) are made of the host sources that existed before them and go through this same function."""
+    sig = {
+        "bpsw_fmi_load": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p], C.c_int),
+        "bpsw_fmi_unload": ([C.c_void_p], C.c_int),
+        "bpsw_fmi_length": ([C.c_void_p], C.c_int64),
+        "bpsw_seed_opt_default": ([C.c_void_p], None),
+        "bpsw_seed_batch": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                             C.c_int64, C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_chain_seeds": ([C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
+        "bpsw_worker1_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_last_worker1_times": ([C.c_void_p], None),
+        "bpsw_seed_set_resident_lanes": ([C.c_int], None),
+    }
+    for name, (args, res) in sig.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = args, res
 
 
 def _ptr(a: np.ndarray | None):
@@ -509,6 +536,55 @@ class Context:
                                                     C.byref(total)), "bpsw_chain2aln_batch")
         return out_cnt[: b.n_reads], out[: total.value]
 
+    # worker1 from reads: the FM-index on the device, seeding, and reads -> regions (bpsw_hip/fmi.py has the records) -------------
+    def fmi_load(self, idx):
+        L2 = np.ascontiguousarray(idx.L2, np.int64)
+        bwt = np.ascontiguousarray(idx.bwt, np.uint32)
+        sa = np.ascontiguousarray(idx.sa, np.int64)
+        _chk(self.lib, self.lib.bpsw_fmi_load(self.h, int(idx.primary), _ptr(L2), int(idx.seq_len), _ptr(bwt), bwt.size, int(idx.sa_intv),
+                                             sa.size, _ptr(sa)), "bpsw_fmi_load")
+
+    def fmi_unload(self):
+        _chk(self.lib, self.lib.bpsw_fmi_unload(self.h), "bpsw_fmi_unload")
+
+    def fmi_length(self) -> int:
+        return int(self.lib.bpsw_fmi_length(self.h))
+
+    def seed_batch(self, sopt, reads):
+        """reads (fmi.ReadBatch) -> (intv_cnt[n], intervals (fmi.SMEM_DTYPE), seed_cnt[n], seeds (fmi.SEED_DTYPE))"""
+        from . import fmi
+        st = reads.as_struct()
+        n = reads.n_reads
+        icnt, scnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        icap, scap = 8 * n + 64, 16 * n + 64
+        while True:
+            iv, sv = np.zeros(icap, fmi.SMEM_DTYPE), np.zeros(scap, fmi.SEED_DTYPE)
+            it, stt = C.c_int64(0), C.c_int64(0)
+            rc = self.lib.bpsw_seed_batch(self.h, C.byref(sopt), C.byref(st), _ptr(icnt), _ptr(iv), icap, C.byref(it), _ptr(scnt), _ptr(sv),
+                                          scap, C.byref(stt))
+            if rc == -3 and (it.value > icap or stt.value > scap):   # BPSW_ERR_CAPACITY: the totals say what is needed
+                icap, scap = max(icap, it.value), max(scap, stt.value)
+                continue
+            _chk(self.lib, rc, "bpsw_seed_batch")
+            return icnt[:n], iv[: it.value], scnt[:n], sv[: stt.value]
+
+    def worker1_batch(self, opt: Opt, sopt, reads, zdrop_mode: int = ZDROP_SCALA, flags: int = 0):
+        """reads (fmi.ReadBatch) -> (out_cnt[n], regions), the shape of chain2aln_batch"""
+        st = reads.as_struct()
+        n = reads.n_reads
+        out_cnt = np.zeros(max(n, 1), np.int32)
+        cap = 4 * n + 64
+        while True:
+            out = np.empty(cap, dtype=ALNREG_DTYPE)
+            total = C.c_int64(0)
+            rc = self.lib.bpsw_worker1_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(st), zdrop_mode, flags, _ptr(out_cnt), _ptr(out), cap,
+                                             C.byref(total))
+            if rc == -3 and total.value > cap:
+                cap = total.value
+                continue
+            _chk(self.lib, rc, "bpsw_worker1_batch")
+            return out_cnt[:n], out[: total.value]
+
     def ring_stats(self):
         """(epochs, submitted, carried) of the device's submission ring (include/bpsw.h: bpsw_ring_stats)"""
         e, s, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -540,6 +616,34 @@ class Context:
         a, b = C.c_float(0), C.c_float(0)
         _chk(self.lib, self.lib.bpsw_last_kernel_ms(self.h, C.byref(a), C.byref(b)), "bpsw_last_kernel_ms")
         return a.value, b.value
+
+
+def default_seed_opt():
+    from . import fmi
+    o = fmi.SeedOpt()
+    load_library().bpsw_seed_opt_default(C.byref(o))
+    return o
+
+
+def chain_seeds(sopt, w: int, l_pac: int, seeds: np.ndarray, filter: bool = True):
+    """bpsw_chain_seeds (host only): one read's seeds (fmi.SEED_DTYPE) in emission order -> (seeds per chain, seeds in chain order)"""
+    from . import fmi
+    seeds = np.ascontiguousarray(seeds, fmi.SEED_DTYPE)
+    n = int(seeds.shape[0])
+    cnt = np.zeros(n + 1, np.int32)
+    out = np.zeros(n + 1, fmi.SEED_DTYPE)
+    lib = load_library()
+    nc = lib.bpsw_chain_seeds(C.byref(sopt), w, l_pac, n, _ptr(seeds), 1 if filter else 0, _ptr(cnt), n, _ptr(out))
+    if nc < 0:
+        _chk(lib, nc, "bpsw_chain_seeds")
+    return cnt[:nc].copy(), out[: int(cnt[:nc].sum())].copy()
+
+
+def last_worker1_times():
+    """(seeding call, host chaining, round loop call) in ms of this thread's last worker1_batch"""
+    ms = (C.c_double * 3)()
+    load_library().bpsw_last_worker1_times(ms)
+    return tuple(ms)
 
 
 @dataclass

@@ -34,6 +34,50 @@ def load_fake():
     return fake, lib
 
 
+FAKE_W1_SO = os.path.join(FAKE_DIR, "libfakejvm_worker1.so")
+
+
+def load_fake_worker1():
+    """the fake JVM with the driver of the seeding entries (tests/fake_jvm/fake_jni_worker1.cpp, which includes fake_jni.cpp)"""
+    srcs = [os.path.join(FAKE_DIR, "fake_jni_worker1.cpp"), os.path.join(FAKE_DIR, "fake_jni.cpp")]
+    if not os.path.exists(FAKE_W1_SO) or os.path.getmtime(FAKE_W1_SO) < max(os.path.getmtime(p) for p in srcs):
+        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "cloud-scale-bwamem_amd", "csrc"),
+                        "-o", FAKE_W1_SO, srcs[0], "-ldl"], check=True)
+    load_library()
+    fake = C.CDLL(FAKE_W1_SO)
+    fake.fake_jvm_worker1.restype = C.c_int
+    return fake
+
+
+def worker1_flat(fake, pac, l_pac, idx, opt, sopt, flags, reads, partition=-1):
+    """loadPacJNI + loadFmiJNI + worker1FlatJNI -> (rc, regions per read, the 8 longs per region, message); idx: fmi.FmIndex or None
+    (then neither loader is called: the device keeps what it holds), reads: fmi.ReadBatch with its reads back to back"""
+    oi = np.array([opt.a, opt.b, opt.o_del, opt.e_del, opt.o_ins, opt.e_ins, opt.pen_clip5, opt.pen_clip3, opt.w, opt.zdrop], np.int32)
+    mat = np.array(list(opt.mat), np.int8)
+    si = np.array([sopt.min_seed_len, sopt.max_occ, sopt.split_width, sopt.max_chain_gap, sopt.no_exact], np.int32)
+    sf = np.array([sopt.split_factor, sopt.chain_drop_ratio, sopt.mask_level, opt.mask_level_redun], np.float64)
+    n = reads.n_reads
+    cap = n + 8 * (64 * n + 64)
+    out = np.zeros(cap, np.int64)
+    out_n = C.c_int64(0)
+    err = C.create_string_buffer(512)
+    if idx is not None:
+        L2 = np.ascontiguousarray(idx.L2, np.int64)
+        bwt = np.ascontiguousarray(idx.bwt, np.uint32)
+        sa = np.ascontiguousarray(idx.sa, np.int64)
+        pac = np.ascontiguousarray(pac, np.uint8)
+        head = (_vp(pac), C.c_int64(l_pac), C.c_int64(idx.primary), _vp(L2), C.c_int64(idx.seq_len), _vp(bwt), C.c_int64(bwt.size),
+                C.c_int32(idx.sa_intv), _vp(sa), C.c_int64(sa.size))
+    else:
+        head = (None, C.c_int64(0), C.c_int64(0), None, C.c_int64(0), None, C.c_int64(0), C.c_int32(0), None, C.c_int64(0))
+    rc = fake.fake_jvm_worker1(LIB_PATH.encode(), partition, *head, _vp(oi), _vp(mat), _vp(si), _vp(sf), C.c_int32(flags), n,
+                               _vp(reads.read_len), _vp(reads.read_pool), C.c_int64(reads.read_pool.size), _vp(out), C.c_int64(cap),
+                               C.byref(out_n), err, 512)
+    if rc != 0:
+        return rc, None, None, err.value.decode()
+    return rc, out[:n].astype(np.int32), out[n: out_n.value].reshape(-1, 8), err.value.decode()
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 

@@ -185,6 +185,13 @@ RingRun ring_run(int device, int c_class, int num_cu, const void* payload, size_
 void ring_integrity_stats(uint64_t* checked, uint64_t* faults);
 void ring_pause(int device);   // close the device's open epochs, wait for their kernels, keep the rings locked ...
 void ring_resume(int device);  // ... until here (bpsw_ref_load / unload: a device-wide synchronisation in between)
+struct RingPause {  // RAII form of the two above
+  int d;
+  explicit RingPause(int dev) : d(dev) { ring_pause(d); }
+  ~RingPause() { ring_resume(d); }
+  RingPause(const RingPause&) = delete;
+  RingPause& operator=(const RingPause&) = delete;
+};
 void ring_get_stats(int device, uint64_t* epochs, uint64_t* submitted, uint64_t* carried, double* epochs_ms = nullptr, uint64_t* epochs_timed = nullptr);
 
 // ---- global alignment + CIGAR -------------------------------------------------
@@ -457,6 +464,7 @@ struct bpsw_ctx {
   bpsw::DeviceBuffer d_wire, d_out, d_pre, d_sw_in, d_sw_out, d_sw_scratch, d_gl_z, d_ext_lists;
   size_t staged_bytes = 0;    // what the last bpsw_extend_stage was asked for (0: nothing staged / already committed)
   bpsw::DeviceBuffer d_sift;  // the sift kernel's verdicts (bpsw_extend_sift.hip): [flag byte per task | two 16-byte records per task]
+  bpsw::DeviceBuffer d_seed[5];  // the seeding calls (bpsw_seed.hip): reads, interval records, list arena, occurrence table, seeds
   // asynchronous device entries: a launch whose table scan has not been read back yet (resolved by finish_pending)
   struct PendingExt { bool active = false; const void* d_wire = nullptr; size_t wire_bytes = 0; int n_tasks = 0; void* d_out = nullptr;
                       hipStream_t s = nullptr; int qcap = 0, rcap = 0; } pend_ext;

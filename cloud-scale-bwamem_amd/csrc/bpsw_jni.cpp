@@ -1043,6 +1043,111 @@ JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_chain
   });
 }
 
+// ---- worker1 from reads: the FM-index on the device, then reads -> regions in one call -----------------------------------------
+// The two C ABI entries live in bpsw_seed.hip.  They are referenced weakly so that a library made of the host sources alone (the
+// sanitizer builds of tests/host_san, which have no kernels) still loads; there the JNI entries below throw.
+#pragma weak bpsw_fmi_load
+#pragma weak bpsw_worker1_batch
+// Scala side (jni/SWExtendFPGAJNI.scala):
+//   @native def loadFmiJNI(primary: Long, l2: Array[Long], seqLen: Long, bwt: Array[Int], saIntv: Int, sa: Array[Long]): Int
+// The fields of BWTType as BWTType.load fills them (bwt.primary, bwt.L2, bwt.seqLen, bwt.bwt, bwt.saIntv, bwt.sa); call once per
+// executor JVM next to loadPacJNI; returns the number of devices that now hold the index.
+JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_loadFmiJNI(JNIEnv* env, jobject, jlong primary, jlongArray l2Arr,
+                                                                                jlong seqLen, jintArray bwtArr, jint saIntv, jlongArray saArr) {
+  return jni_entry(env, "loadFmiJNI", jint(0), [&]() -> jint {
+  if (!bpsw_fmi_load) { throw_runtime(env, "bPSW: loadFmiJNI: this build has no seeding kernels"); return 0; }
+  if (!l2Arr || !bwtArr || !saArr || jni::GetArrayLength(env, l2Arr) < 5) { throw_runtime(env, "bPSW: loadFmiJNI: bad arguments"); return 0; }
+  int64_t l2[5];
+  jni::GetLongArrayRegion(env, l2Arr, 0, 5, (jlong*)l2);
+  const jsize nb = jni::GetArrayLength(env, bwtArr), ns = jni::GetArrayLength(env, saArr);
+  std::vector<uint32_t> bwt((size_t)nb + 1);
+  std::vector<int64_t> sa((size_t)ns + 1);
+  if (nb) jni::GetIntArrayRegion(env, bwtArr, 0, nb, reinterpret_cast<jint*>(bwt.data()));
+  if (ns) jni::GetLongArrayRegion(env, saArr, 0, ns, (jlong*)sa.data());
+  return load_on_every_device(env, "loadFmiJNI", [&](bpsw_ctx_t* c) {
+    return bpsw_fmi_load(c, primary, l2, seqLen, bwt.data(), (int64_t)nb, saIntv, (int64_t)ns, sa.data());
+  });
+  });
+}
+
+// Scala side (jni/SWExtendFPGAJNI.scala):
+//   @native def worker1FlatJNI(optInts: Array[Int], mat: Array[Byte], seedInts: Array[Int], seedFloats: Array[Double], flags: Int,
+//                              readLen: Array[Int], reads: Array[Byte]): Array[Long]
+// optInts and mat as for chainToAlnJNI; seedInts = (minSeedLen, maxOcc, splitWidth, maxChainGap, noExact), seedFloats =
+// (splitFactor, chainDropRatio, maskLevel, maskLevelRedun); flags = BPSW_C2A_SORT_DEDUP | BPSW_C2A_DEDUP_SCALA; reads back to back
+// (codes 0..4).  Result: n longs (regions per read), then 8 longs per region as chainToAlnJNI returns them.  Needs loadPacJNI and
+// loadFmiJNI first; BPSW_ZDROP as for chainToAlnJNI.
+JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_worker1FlatJNI(
+    JNIEnv* env, jobject, jintArray optInts, jbyteArray matArr, jintArray seedInts, jdoubleArray seedFloats, jint flags, jintArray readLenArr,
+    jbyteArray readsArr) {
+  return jni_entry(env, "worker1FlatJNI", jlongArray(nullptr), [&]() -> jlongArray {
+  if (!bpsw_worker1_batch) { throw_runtime(env, "bPSW: worker1FlatJNI: this build has no seeding kernels"); return nullptr; }
+  if (!optInts || !matArr || !seedInts || !seedFloats || !readLenArr || !readsArr || jni::GetArrayLength(env, optInts) < 10 ||
+      jni::GetArrayLength(env, matArr) < 25 || jni::GetArrayLength(env, seedInts) < 5 || jni::GetArrayLength(env, seedFloats) < 4) {
+    throw_runtime(env, "bPSW: worker1FlatJNI: bad arguments");
+    return nullptr;
+  }
+  const double t0 = now_us();
+  bpsw_opt_t opt;
+  bpsw_opt_default(&opt);
+  jint oi[10], si[5];
+  jdouble sf[4];
+  jni::GetIntArrayRegion(env, optInts, 0, 10, oi);
+  jni::GetIntArrayRegion(env, seedInts, 0, 5, si);
+  jni::GetDoubleArrayRegion(env, seedFloats, 0, 4, sf);
+  opt.a = oi[0]; opt.b = oi[1]; opt.o_del = oi[2]; opt.e_del = oi[3]; opt.o_ins = oi[4]; opt.e_ins = oi[5];
+  opt.pen_clip5 = oi[6]; opt.pen_clip3 = oi[7]; opt.w = oi[8]; opt.zdrop = oi[9];
+  opt.mask_level_redun = (float)sf[3];
+  jni::GetByteArrayRegion(env, matArr, 0, 25, reinterpret_cast<jbyte*>(opt.mat));
+  bpsw_seed_opt_t so;
+  so.min_seed_len = si[0]; so.max_occ = si[1]; so.split_width = si[2]; so.max_chain_gap = si[3]; so.no_exact = si[4];
+  so.split_factor = (float)sf[0]; so.chain_drop_ratio = (float)sf[1]; so.mask_level = (float)sf[2];
+  const jsize n = jni::GetArrayLength(env, readLenArr);
+  std::vector<int32_t> read_len((size_t)n + 1);
+  if (n) jni::GetIntArrayRegion(env, readLenArr, 0, n, read_len.data());
+  std::vector<int64_t> read_off((size_t)n + 1);
+  int64_t at = 0;
+  for (jsize r = 0; r < n; ++r) {
+    if (read_len[(size_t)r] < 0) { throw_runtime(env, "bPSW: worker1FlatJNI: negative read length"); return nullptr; }
+    read_off[(size_t)r] = at; at += read_len[(size_t)r];
+  }
+  const jsize pool_bytes = jni::GetArrayLength(env, readsArr);
+  if ((int64_t)pool_bytes < at) { throw_runtime(env, "bPSW: worker1FlatJNI: reads shorter than the sum of readLen"); return nullptr; }
+  std::vector<uint8_t> pool((size_t)pool_bytes + 16);
+  if (pool_bytes) jni::GetByteArrayRegion(env, readsArr, 0, pool_bytes, reinterpret_cast<jbyte*>(pool.data()));
+  bpsw_reads_t R;
+  memset(&R, 0, sizeof R);
+  R.n_reads = n; R.read_len = read_len.data(); R.read_off = read_off.data(); R.read_pool = pool.data(); R.read_pool_bytes = (size_t)pool_bytes;
+  bpsw_ctx_t* ctx = thread_context(env);
+  if (!ctx) return nullptr;
+  const char* zd = getenv("BPSW_ZDROP");
+  const int zmode = (zd && strcmp(zd, "bwa") == 0) ? BPSW_ZDROP_BWA : BPSW_ZDROP_SCALA;
+  const double t1 = now_us();
+  std::vector<int32_t> out_cnt((size_t)n + 1);
+  std::vector<bpsw_alnreg_t> out((size_t)4 * (size_t)n + 64);
+  int64_t total = 0;
+  int rc = bpsw_worker1_batch(ctx, &opt, &so, &R, zmode, flags, out_cnt.data(), out.data(), (int64_t)out.size(), &total);
+  if (rc == BPSW_ERR_CAPACITY && total > (int64_t)out.size()) {  // more seeds than guessed: *out_total says how many regions can come
+    out.resize((size_t)total);
+    rc = bpsw_worker1_batch(ctx, &opt, &so, &R, zmode, flags, out_cnt.data(), out.data(), (int64_t)out.size(), &total);
+  }
+  if (rc != BPSW_OK) { throw_runtime(env, std::string("bPSW: worker1FlatJNI: ") + bpsw_last_error()); return nullptr; }
+  const double t2 = now_us();
+  std::vector<jlong> flat((size_t)n + 8 * (size_t)total);
+  for (jsize r = 0; r < n; ++r) flat[(size_t)r] = out_cnt[(size_t)r];
+  for (int64_t k = 0; k < total; ++k) {
+    jlong* o = flat.data() + (size_t)n + 8 * (size_t)k;
+    const bpsw_alnreg_t& g = out[(size_t)k];
+    o[0] = g.rb; o[1] = g.re; o[2] = g.qb; o[3] = g.qe; o[4] = g.score; o[5] = g.truesc; o[6] = g.w; o[7] = g.seedcov;
+  }
+  jlongArray ret = jni::NewLongArray(env, (jsize)flat.size());
+  if (!ret) return nullptr;  // OutOfMemoryError already pending
+  if (!flat.empty()) jni::SetLongArrayRegion(env, ret, 0, (jsize)flat.size(), flat.data());
+  t_times = {t1 - t0, t2 - t1, now_us() - t2, (double)total};
+  return ret;
+  });
+}
+
 // ---- worker2's tail -----------------------------------------------------------------------------
 // Scala side (jni/MateSWJNI.scala):
 //   @native def loadBnsJNI(offset: Array[Long], len: Array[Int], names: Array[Byte]): Int     // names NUL-terminated, back to back

@@ -356,7 +356,7 @@ double bpsw_diag_wait_est_update(double est, double took_ms, int polls, int napp
 int bpsw_diag_wait_naps(double est_ms) { return bpsw::wait_naps(est_ms) ? 1 : 0; }
 
 const char* bpsw_version(void) {
-  return "bPSW-hip 0.5 (gfx950)";  // 0.5 = round 5: bpsw_stats_t grew (sw_ring_calls, ext_ring_calls): rebuild callers against include/bpsw.h
+  return "bPSW-hip 0.6 (gfx950)";  // 0.5: bpsw_stats_t grew (sw_ring_calls, ext_ring_calls): rebuild callers against include/bpsw.h; 0.6: new entries only
 }
 
 int bpsw_device_count(void) {
@@ -465,6 +465,7 @@ void bpsw_destroy(bpsw_ctx_t* c) {
   RingPauseForFree paused_for_all;
   c->d_wire.release(); c->d_out.release(); c->d_pre.release();
   c->d_sw_in.release(); c->d_sw_out.release(); c->d_sw_scratch.release(); c->d_gl_z.release(); c->d_ext_lists.release(); c->d_sift.release();
+  for (bpsw::DeviceBuffer& b : c->d_seed) b.release();
   c->h_stage_in.release(); c->h_stage_out.release(); c->h_pre.release();
   rescue_scratch_free(c->rescue_scratch);
   for (int i = 0; i < 8; ++i)

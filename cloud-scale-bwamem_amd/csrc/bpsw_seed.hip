@@ -1,0 +1,631 @@
+// bpsw_seed.hip -- worker1's seeding on the device: the FM-index resident in HBM, SMEM search and suffix-array lookup.
+//
+// Replaces the interval side of mem_insert_seed (native/bwamem.c:207-228): smem_next2 (:117-156) over bwt_smem1 / bwt_extend
+// (native/bwt.c:261-347) and bwt_sa (:85-95), i.e. BWTSMem.scala / MemChain.scala's generateChains up to the seeds.  Integer only
+// and bit-exact: the kernels perform the reference's steps in the reference's order.
+//
+// Mapping: ONE READ PER LANE (seed_smem_kernel), one occurrence per lane (seed_sa_kernel).  The search is a chain of dependent
+// random reads -- each bwt_extend needs the 64-byte blocks of rows k - 1 and k - 1 + x2 before the next one can be addressed --
+// so the rate is set by the number of independent chains in flight, not by ALU work; a wavefront per read would keep one or two
+// loads in flight per wave.  Lanes diverge (reads differ in where their matches end); that costs issue slots the kernel has to spare.
+//
+// The per-lane interval lists (bwt_smem1's prev / curr, smem_next2's matches / sub) live in a global arena, interleaved by
+// lane: entry e of lane l of a list at e * 64 + l.  No list outgrows read_len + 1 entries: the forward sweep pushes at most one
+// interval per base, the backward sweep at most as many as it was given, and mem at most one per start position.
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+#include <chrono>
+
+#include "bpsw_internal.h"
+
+using namespace bpsw;
+
+namespace {
+
+typedef unsigned long long u64;
+
+struct FmiDev {  // by value to the kernels
+  const uint32_t* bwt;
+  const long long* sa;
+  u64 primary, seq_len;
+  u64 L2[5];
+  int sa_shift;  // log2(sa_intv)
+};
+
+struct Intv {  // bwtintv_t: info = qbeg << 32 | qend
+  u64 x0, x1, x2, info;
+};
+
+// ---- bwt_occ4 / bwt_occ with popcounts on the 2-bit words (__occ_aux's reduction, no byte table) ----------------------------
+// Bases of a block: eight words, base j of a word in bits 30 - 2 j.  Two words make the 64-bit y of __occ_aux (first word high).
+__device__ __forceinline__ u64 pair_mask(int i, int kk) {  // which of the 32 bases of pair i lie at or before base kk of the block
+  const int full = kk >> 5;
+  return i < full ? ~0ull : i == full ? ~((1ull << ((~kk & 31) << 1)) - 1) : 0ull;
+}
+__device__ __forceinline__ void occ4(const FmiDev& F, u64 k, u64 cnt[4]) {
+  if (k == ~0ull) { cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0; return; }
+  k = k > F.seq_len ? F.seq_len : k;  // (a valid index never asks beyond seq_len; this keeps a corrupt one inside the array)
+  k -= (k >= F.primary);
+  const uint4* blk = (const uint4*)(F.bwt + ((k >> 7) << 4));
+  const uint4 c0 = blk[0], c1 = blk[1], b0 = blk[2], b1 = blk[3];
+  const u64 y[4] = {(u64)b0.x << 32 | b0.y, (u64)b0.z << 32 | b0.w, (u64)b1.x << 32 | b1.y, (u64)b1.z << 32 | b1.w};
+  const int kk = (int)(k & 127);
+  unsigned n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u64 v = y[i] & pair_mask(i, kk), hi = v >> 1, m = 0x5555555555555555ull;
+    n0 += __popcll(~hi & ~v & m);
+    n1 += __popcll(~hi & v & m);
+    n2 += __popcll(hi & ~v & m);
+    n3 += __popcll(hi & v & m);
+  }
+  n0 -= (unsigned)(127 - kk);  // the masked-out bases read as A
+  cnt[0] = ((u64)c0.y << 32 | c0.x) + n0;
+  cnt[1] = ((u64)c0.w << 32 | c0.z) + n1;
+  cnt[2] = ((u64)c1.y << 32 | c1.x) + n2;
+  cnt[3] = ((u64)c1.w << 32 | c1.z) + n3;
+}
+__device__ __forceinline__ u64 occ1(const FmiDev& F, u64 k, int c) {  // bwt_occ
+  if (k == F.seq_len) return F.L2[c + 1] - F.L2[c];
+  u64 cnt[4];
+  occ4(F, k, cnt);
+  return cnt[c];
+}
+
+// bwt_extend, native/bwt.c:261-274.  (bwt_2occ4's same-block shortcut is an optimisation of two bwt_occ4: not restated.)
+__device__ __forceinline__ void extend(const FmiDev& F, const Intv& ik, Intv ok[4], int is_back) {
+  const u64 a = is_back ? ik.x0 : ik.x1, b = is_back ? ik.x1 : ik.x0;  // a = x[!is_back], the side that is extended; b = x[is_back]
+  u64 tk[4], tl[4];
+  occ4(F, a - 1, tk);
+  occ4(F, a - 1 + ik.x2, tl);
+  u64 na[4], nb[4], n2[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { na[i] = F.L2[i] + 1 + tk[i]; n2[i] = tl[i] - tk[i]; }
+  nb[3] = b + (a <= F.primary && a + ik.x2 - 1 >= F.primary);
+  nb[2] = nb[3] + n2[3];
+  nb[1] = nb[2] + n2[2];
+  nb[0] = nb[1] + n2[1];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ok[i].x0 = is_back ? na[i] : nb[i];
+    ok[i].x1 = is_back ? nb[i] : na[i];
+    ok[i].x2 = n2[i];
+    ok[i].info = 0;
+  }
+}
+
+struct List {  // one lane's list in the arena
+  Intv* base;  // entry e at base[e * 64]
+  int n, cap;
+  int* overflow;
+  __device__ __forceinline__ void push(const Intv& v) {
+    if (n < cap) base[(size_t)n++ * 64] = v;
+    else *overflow = 1;  // (never with cap = read_len + 1; the host turns it into an error)
+  }
+  __device__ __forceinline__ Intv get(int e) const { return base[(size_t)e * 64]; }
+  __device__ __forceinline__ void reverse() {
+    for (int j = 0; j < n >> 1; ++j) {
+      const Intv t = base[(size_t)(n - 1 - j) * 64];
+      base[(size_t)(n - 1 - j) * 64] = base[(size_t)j * 64];
+      base[(size_t)j * 64] = t;
+    }
+  }
+};
+
+// bwt_smem1, native/bwt.c:288-347.  t0 / t1: the two temporary lists (tmpvec); returns the reference's return value.
+__device__ int smem1(const FmiDev& F, int len, const uint8_t* q, int x, u64 min_intv, List& mem, List& t0, List& t1) {
+  mem.n = 0;
+  if (q[x] > 3) return x + 1;
+  if (min_intv < 1) min_intv = 1;
+  List* prev = &t0;
+  List* curr = &t1;
+  Intv ik, ok[4];
+  const int c0 = q[x];
+  ik.x0 = F.L2[c0] + 1; ik.x2 = F.L2[c0 + 1] - F.L2[c0]; ik.x1 = F.L2[3 - c0] + 1;  // bwt_set_intv
+  ik.info = (u64)(x + 1);
+  int i;
+  curr->n = 0;
+  for (i = x + 1; i < len; ++i) {  // forward search
+    if (q[i] < 4) {
+      const int c = 3 - q[i];
+      extend(F, ik, ok, 0);
+      if (ok[c].x2 != ik.x2) {
+        curr->push(ik);
+        if (ok[c].x2 < min_intv) break;
+      }
+      ik = ok[c]; ik.info = (u64)(i + 1);
+    } else {
+      curr->push(ik);
+      break;
+    }
+  }
+  if (i == len) curr->push(ik);
+  curr->reverse();
+  const int ret = (int)(unsigned)curr->get(0).info;
+  { List* s = curr; curr = prev; prev = s; }
+  for (i = x - 1; i >= -1; --i) {  // backward search for MEMs
+    const int c = i < 0 ? -1 : q[i] < 4 ? q[i] : -1;
+    curr->n = 0;
+    for (int j = 0; j < prev->n; ++j) {
+      const Intv p = prev->get(j);
+      bool small = c < 0;
+      if (!small) { extend(F, p, ok, 1); small = ok[c].x2 < min_intv; }
+      if (small) {
+        if (curr->n == 0) {
+          if (mem.n == 0 || (u64)(i + 1) < (mem.get(mem.n - 1).info >> 32)) {
+            ik = p; ik.info |= (u64)(i + 1) << 32;
+            mem.push(ik);
+          }
+        }
+      } else if (curr->n == 0 || ok[c].x2 != curr->get(curr->n - 1).x2) {
+        ok[c].info = p.info;
+        curr->push(ok[c]);
+      }
+    }
+    if (curr->n == 0) break;
+    { List* s = curr; curr = prev; prev = s; }
+  }
+  mem.reverse();
+  return ret;
+}
+
+struct SeedParams {
+  int min_seed_len, max_occ, split_width, start_width;
+  int split_len0;  // (int)(min_seed_len * split_factor + .499), before the per-read minimum with the read length
+};
+
+// smem_next2 until the read is used up (mem_insert_seed's loop, native/bwamem.c:207-219), one read per lane, grid-stride.
+// Item i is read todo[i] (read i when todo is null); its records go to out + row_base[i], room row_base[i + 1] - row_base[i] (rows of
+// `stride` records when row_base is null); cnt[i] = the number the read produced, which may exceed the room: the host then runs
+// those reads alone once more, each with exactly the room it asked for.
+__global__ __launch_bounds__(64) void seed_smem_kernel(FmiDev F, SeedParams P, int n_items, const int32_t* __restrict__ todo,
+                                                        const int32_t* __restrict__ read_len, const long long* __restrict__ read_off,
+                                                        const uint8_t* __restrict__ read_pool, Intv* arena, int list_cap, bpsw_smem_t* out,
+                                                        int stride, const long long* __restrict__ row_base, int32_t* cnt, int* overflow) {
+  const int lane = threadIdx.x;
+  Intv* mine = arena + (size_t)blockIdx.x * 4 * (size_t)list_cap * 64 + lane;
+  List M{mine, 0, list_cap, overflow}, S{mine + (size_t)list_cap * 64, 0, list_cap, overflow};
+  List T0{mine + 2 * (size_t)list_cap * 64, 0, list_cap, overflow}, T1{mine + 3 * (size_t)list_cap * 64, 0, list_cap, overflow};
+  for (long long it = (long long)blockIdx.x * 64 + lane; it < n_items; it += (long long)gridDim.x * 64) {
+    const long long r = todo ? todo[it] : it;
+    const int len = read_len[r];
+    const uint8_t* q = read_pool + read_off[r];
+    bpsw_smem_t* o = row_base ? out + row_base[it] : out + (size_t)it * (size_t)stride;
+    const int room = row_base ? (int)(row_base[it + 1] - row_base[it]) : stride;
+    int n_out = 0;
+    auto emit = [&](const Intv& v) {
+      if (n_out < room) {
+        bpsw_smem_t e;
+        e.x0 = (int64_t)v.x0; e.x1 = (int64_t)v.x1; e.x2 = (int64_t)v.x2;
+        e.qbeg = (int)(v.info >> 32); e.qend = (int)(unsigned)v.info;
+        e.kept = !(e.qend - e.qbeg < P.min_seed_len || v.x2 > (u64)P.max_occ);
+        e.pad_ = 0;
+        o[n_out] = e;
+      }
+      ++n_out;
+    };
+    if (len >= P.min_seed_len && len <= list_cap - 1) {  // mem_chain: a query shorter than the seed length has no match
+      const int split_len = P.split_len0 < len ? P.split_len0 : len;
+      int start = 0;
+      for (;;) {
+        while (start < len && q[start] > 3) ++start;  // skip ambiguous bases
+        if (start >= len) break;
+        const int ori_start = start;
+        start = smem1(F, len, q, ori_start, (u64)P.start_width, M, T0, T1);
+        if (M.n == 0) continue;
+        int max = 0, max_i = 0;
+        for (int i = 0; i < M.n; ++i) {
+          const Intv p = M.get(i);
+          const int l = (int)((unsigned)p.info - (unsigned)(p.info >> 32));
+          if (max < l) { max = l; max_i = i; }
+        }
+        const Intv best = M.get(max_i);
+        if (split_len > 0 && max >= split_len && best.x2 <= (u64)P.split_width) {  // re-seed from the middle of the longest SMEM
+          smem1(F, len, q, (int)(((unsigned)best.info + (unsigned)(best.info >> 32)) >> 1), best.x2 + 1, S, T0, T1);
+          int i = 0, j = 0;
+          auto sub_ok = [&](const Intv& s) {
+            return (int)((unsigned)s.info - (unsigned)(s.info >> 32)) >= (max >> 1) && (int)(unsigned)s.info > ori_start;
+          };
+          while (i < M.n && j < S.n) {  // ordered merge
+            const Intv a = M.get(i), b = S.get(j);
+            const long long xi = (long long)(a.info >> 32 << 32 | (u64)(len - (int)(unsigned)a.info));
+            const long long xj = (long long)(b.info >> 32 << 32 | (u64)(len - (int)(unsigned)b.info));
+            if (xi < xj) { emit(a); ++i; }
+            else { if (sub_ok(b)) emit(b); ++j; }
+          }
+          for (; i < M.n; ++i) emit(M.get(i));
+          for (; j < S.n; ++j) { const Intv b = S.get(j); if (sub_ok(b)) emit(b); }
+        } else {
+          for (int i = 0; i < M.n; ++i) emit(M.get(i));
+        }
+      }
+    }
+    cnt[it] = n_out;
+  }
+}
+
+// bwt_sa(x0 + k), native/bwt.c:85-95 with bwt_invPsi (:52-58), one occurrence per lane.  Occurrence t belongs to the kept
+// interval whose base (prefix sum of x2) is the last one <= t: a binary search over occ_base[0 .. n_kept].
+__global__ __launch_bounds__(256) void seed_sa_kernel(FmiDev F, long long n_occ, int n_kept, const long long* __restrict__ occ_base,
+                                                      const long long* __restrict__ kept_x0, const int2* __restrict__ kept_q,
+                                                      bpsw_seed_t* out) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_occ) return;
+  int lo = 0, hi = n_kept - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (occ_base[mid] <= t) lo = mid;
+    else hi = mid - 1;
+  }
+  u64 k = (u64)kept_x0[lo] + (u64)(t - occ_base[lo]);
+  const u64 mask = ((u64)1 << F.sa_shift) - 1;
+  u64 sa = 0;
+  while ((k & mask) && sa <= F.seq_len) {  // (a valid index reaches a sampled row within seq_len steps)
+    ++sa;
+    if (k == F.primary) { k = 0; continue; }
+    k = k > F.seq_len ? F.seq_len : k;
+    const u64 x = k - (k > F.primary);
+    const uint32_t w = F.bwt[((x >> 7) << 4) + 8 + ((x & 0x7f) >> 4)];
+    const int c = (int)(w >> ((~x & 0xf) << 1) & 3);
+    k = F.L2[c] + occ1(F, k, c);
+  }
+  const int2 qq = kept_q[lo];
+  bpsw_seed_t s;
+  s.rbeg = (int64_t)(sa + (u64)F.sa[k >> F.sa_shift]);
+  s.qbeg = qq.x;
+  s.len = qq.y - qq.x;
+  out[t] = s;
+}
+
+// ---- the index, per device --------------------------------------------------------------------------------------------
+struct DeviceFmi {
+  RefGate gate;
+  std::mutex mu;
+  DeviceBuffer bwt, sa;
+  FmiDev dev{};
+  long long seq_len = 0;
+};
+DeviceFmi& device_fmi(int device) {
+  static DeviceFmi table[64];
+  return table[device >= 0 && device < 64 ? device : 0];
+}
+
+int hip_fail(hipError_t e, const char* what) { return fail(BPSW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+#define HIP_TRY(expr)                                 \
+  do {                                                \
+    hipError_t e_ = (expr);                           \
+    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+  } while (0)
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// lanes of seed_smem_kernel resident at a time: four wavefronts per compute unit (one per SIMD), each lane with four lists of
+// read_len + 1 intervals of 32 bytes -- 32.9 KB a lane at 256 bases, 2.2 GB on 256 CUs; 1.3 GB at 150 bases.
+// bpsw_seed_set_resident_lanes (diagnostics, include/bpsw.h) overrides the count.
+std::atomic<int> g_seed_lanes{0};
+int seed_resident_waves(int num_cu, long long n_reads) {
+  const long long forced = g_seed_lanes.load(std::memory_order_relaxed) / 64;
+  long long waves = forced >= 1 ? forced : (long long)num_cu * 4;
+  const long long need = (n_reads + 63) / 64;
+  return (int)(need < waves ? need : waves);
+}
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+thread_local double t_w1_ms[3] = {0., 0., 0.};
+
+// seeding of a validated batch: per read the intervals and the seeds (bridging ones dropped), concatenated in read order
+int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std::vector<int32_t>* icnt, std::vector<bpsw_smem_t>* intv,
+             std::vector<int32_t>* scnt, std::vector<bpsw_seed_t>* seeds) {
+  const int n = R.n_reads;
+  int max_len = 1;
+  for (int r = 0; r < n; ++r) {
+    const int ql = R.read_len[r];
+    const long long qo = R.read_off[r];
+    if (ql < 0 || qo < 0 || (unsigned long long)(qo + ql) > R.read_pool_bytes) return fail(BPSW_ERR_ARG, "seed: read outside read_pool");
+    if (ql > BPSW_SEED_MAX_QLEN) return fail(BPSW_ERR_LIMIT, "seed: read longer than 256 bases");
+    if (ql > max_len) max_len = ql;
+  }
+  if (so.min_seed_len < 1 || so.max_occ < 0 || so.split_width < 0) return fail(BPSW_ERR_ARG, "seed: min_seed_len must be >= 1, max_occ and split_width >= 0");
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
+  DeviceFmi& fm = device_fmi(c->device);
+  const RefHold hold(&fm.gate);
+  FmiDev F;
+  { std::lock_guard<std::mutex> g(fm.mu); F = fm.dev; }
+  if (F.seq_len == 0) return fail(BPSW_ERR_ARG, "seed: no index is loaded (bpsw_fmi_load)");
+  const u64 l_pac = F.seq_len >> 1;
+
+  DeviceBuffer &d_in = c->d_seed[0], &d_out = c->d_seed[1], &d_arena = c->d_seed[2], &d_sa_in = c->d_seed[3], &d_sa_out = c->d_seed[4];
+  SeedParams P;
+  P.min_seed_len = so.min_seed_len; P.max_occ = so.max_occ; P.split_width = so.split_width;
+  P.start_width = so.no_exact ? 2 : 1;
+  P.split_len0 = (int)(so.min_seed_len * so.split_factor + .499);
+
+  // ---- intervals ----
+  const size_t o_len = 0, o_off = align16(4 * (size_t)n), o_pool = align16(o_off + 8 * (size_t)n);
+  const size_t in_total = align16(o_pool + R.read_pool_bytes + 16);
+  HIP_TRY(c->h_stage_in.reserve(in_total));
+  HIP_TRY(d_in.reserve(in_total));
+  uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
+  memcpy(h + o_len, R.read_len, 4 * (size_t)n);
+  memcpy(h + o_off, R.read_off, 8 * (size_t)n);
+  if (R.read_pool_bytes) memcpy(h + o_pool, R.read_pool, R.read_pool_bytes);
+  uint8_t* d = (uint8_t*)d_in.ptr;
+  HIP_TRY(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, c->stream));
+  const int waves = seed_resident_waves(c->num_cu, n);
+  const int list_cap = max_len + 1;
+  HIP_TRY(d_arena.reserve((size_t)waves * 4 * (size_t)list_cap * 64 * sizeof(Intv)));
+  // first pass: rows of 16 records (a read of 150 bases has about five intervals); the reads that produced more are run once more
+  // by themselves, each with exactly the room its count asks for -- so the records of a batch never take more than
+  // 16 n + (the intervals of the overflowing reads), whatever one repeat-rich read produces
+  const int stride = 16;
+  {
+    const size_t o_cnt = 0, o_ovf = align16(4 * (size_t)n), o_rec = align16(o_ovf + 16);
+    const size_t out_total = o_rec + sizeof(bpsw_smem_t) * (size_t)n * (size_t)stride;
+    HIP_TRY(d_out.reserve(out_total));
+    HIP_TRY(c->h_stage_out.reserve(out_total));
+    uint8_t* dout = (uint8_t*)d_out.ptr;
+    HIP_TRY(hipMemsetAsync(dout + o_ovf, 0, 16, c->stream));
+    hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves), dim3(64), 0, c->stream, F, P, n, (const int32_t*)nullptr,
+                       (const int32_t*)(d + o_len), (const long long*)(d + o_off), (const uint8_t*)(d + o_pool), (Intv*)d_arena.ptr, list_cap,
+                       (bpsw_smem_t*)(dout + o_rec), stride, (const long long*)nullptr, (int32_t*)(dout + o_cnt), (int*)(dout + o_ovf));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, out_total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint8_t* ho = (const uint8_t*)c->h_stage_out.ptr;
+    if (*(const int*)(ho + o_ovf)) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
+    const int32_t* cnt = (const int32_t*)(ho + o_cnt);
+    icnt->assign(cnt, cnt + n);
+    std::vector<int32_t> todo;
+    std::vector<long long> base(1, 0);
+    for (int r = 0; r < n; ++r)
+      if (cnt[r] > stride) { todo.push_back(r); base.push_back(base.back() + cnt[r]); }
+    std::vector<bpsw_smem_t> first;  // the first pass's rows, taken out of the pinned block before the second pass reuses it
+    const bpsw_smem_t* rec = (const bpsw_smem_t*)(ho + o_rec);
+    const bpsw_smem_t* more = nullptr;
+    if (!todo.empty()) {
+      first.assign(rec, rec + (size_t)n * (size_t)stride);
+      rec = first.data();
+      const size_t m = todo.size();
+      const size_t t_todo = 0, t_base = align16(4 * m), t_total = align16(t_base + 8 * (m + 1));
+      const size_t r_cnt = 0, r_ovf = align16(4 * m), r_rec = align16(r_ovf + 16), r_total = r_rec + sizeof(bpsw_smem_t) * (size_t)base.back();
+      HIP_TRY(c->h_stage_in.reserve(t_total));
+      HIP_TRY(d_sa_in.reserve(t_total));
+      HIP_TRY(d_out.reserve(r_total));
+      HIP_TRY(c->h_stage_out.reserve(r_total));
+      uint8_t* ht = (uint8_t*)c->h_stage_in.ptr;
+      memcpy(ht + t_todo, todo.data(), 4 * m);
+      memcpy(ht + t_base, base.data(), 8 * (m + 1));
+      uint8_t* dt = (uint8_t*)d_sa_in.ptr;
+      dout = (uint8_t*)d_out.ptr;
+      HIP_TRY(hipMemcpyAsync(dt, ht, t_total, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemsetAsync(dout + r_ovf, 0, 16, c->stream));
+      const int waves2 = seed_resident_waves(c->num_cu, (long long)m);
+      hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves2), dim3(64), 0, c->stream, F, P, (int)m, (const int32_t*)(dt + t_todo),
+                         (const int32_t*)(d + o_len), (const long long*)(d + o_off), (const uint8_t*)(d + o_pool), (Intv*)d_arena.ptr, list_cap,
+                         (bpsw_smem_t*)(dout + r_rec), 0, (const long long*)(dt + t_base), (int32_t*)(dout + r_cnt), (int*)(dout + r_ovf));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, r_total, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const uint8_t* h2 = (const uint8_t*)c->h_stage_out.ptr;
+      const int32_t* cnt2 = (const int32_t*)(h2 + r_cnt);
+      for (size_t i = 0; i < m; ++i)
+        if (cnt2[i] != (*icnt)[(size_t)todo[i]]) return fail(BPSW_ERR_DEVICE, "seed: interval counts changed between two runs");
+      more = (const bpsw_smem_t*)(h2 + r_rec);
+    }
+    intv->clear();
+    size_t ti = 0;
+    for (int r = 0; r < n; ++r) {
+      const int m = (*icnt)[(size_t)r];
+      if (m <= stride) intv->insert(intv->end(), rec + (size_t)r * (size_t)stride, rec + (size_t)r * (size_t)stride + m);
+      else { intv->insert(intv->end(), more + base[ti], more + base[ti] + m); ++ti; }
+    }
+  }
+
+  // ---- seeds: one occurrence per lane, offsets from the prefix sum of the kept intervals' x2 ----
+  std::vector<long long> occ_base, kept_x0;
+  std::vector<int32_t> kept_q;
+  std::vector<long long> read_occ((size_t)n + 1, 0);
+  long long n_occ = 0;
+  {
+    size_t at = 0;
+    for (int r = 0; r < n; ++r) {
+      read_occ[(size_t)r] = n_occ;
+      for (int k = 0; k < (*icnt)[(size_t)r]; ++k, ++at) {
+        const bpsw_smem_t& e = (*intv)[at];
+        if (!e.kept) continue;
+        occ_base.push_back(n_occ); kept_x0.push_back(e.x0);
+        kept_q.push_back(e.qbeg); kept_q.push_back(e.qend);
+        n_occ += e.x2;
+      }
+    }
+    read_occ[(size_t)n] = n_occ;
+  }
+  scnt->assign((size_t)n, 0);
+  seeds->clear();
+  if (n_occ == 0) return BPSW_OK;
+  if (n_occ > 0x3fffffffll) return fail(BPSW_ERR_LIMIT, "seed: more than 2^30 seed occurrences in one batch");
+  const size_t nk = occ_base.size();
+  occ_base.push_back(n_occ);
+  const size_t s_base = 0, s_x0 = align16(8 * (nk + 1)), s_q = align16(s_x0 + 8 * nk), s_total = align16(s_q + 8 * nk);
+  HIP_TRY(c->h_stage_in.reserve(s_total));
+  HIP_TRY(d_sa_in.reserve(s_total));
+  HIP_TRY(d_sa_out.reserve(sizeof(bpsw_seed_t) * (size_t)n_occ));
+  HIP_TRY(c->h_stage_out.reserve(sizeof(bpsw_seed_t) * (size_t)n_occ));
+  h = (uint8_t*)c->h_stage_in.ptr;
+  memcpy(h + s_base, occ_base.data(), 8 * (nk + 1));
+  memcpy(h + s_x0, kept_x0.data(), 8 * nk);
+  memcpy(h + s_q, kept_q.data(), 8 * nk);
+  uint8_t* ds = (uint8_t*)d_sa_in.ptr;
+  HIP_TRY(hipMemcpyAsync(ds, h, s_total, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(seed_sa_kernel, dim3((unsigned)((n_occ + 255) / 256)), dim3(256), 0, c->stream, F, n_occ, (int)nk,
+                     (const long long*)(ds + s_base), (const long long*)(ds + s_x0), (const int2*)(ds + s_q), (bpsw_seed_t*)d_sa_out.ptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, d_sa_out.ptr, sizeof(bpsw_seed_t) * (size_t)n_occ, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const bpsw_seed_t* all = (const bpsw_seed_t*)c->h_stage_out.ptr;
+  seeds->reserve((size_t)n_occ);
+  for (int r = 0; r < n; ++r) {
+    int m = 0;
+    for (long long t = read_occ[(size_t)r]; t < read_occ[(size_t)r + 1]; ++t) {
+      const bpsw_seed_t& s = all[t];
+      if ((u64)s.rbeg < l_pac && l_pac < (u64)s.rbeg + (u64)s.len) continue;  // bridging the strands, native/bwamem.c:228
+      seeds->push_back(s);
+      ++m;
+    }
+    (*scnt)[(size_t)r] = m;
+  }
+  return BPSW_OK;
+}
+
+int check_reads(const char* who, const bpsw_reads_t* R) {
+  if (!R || R->n_reads < 0 || (R->n_reads > 0 && (!R->read_len || !R->read_off || (!R->read_pool && R->read_pool_bytes))))
+    return fail(BPSW_ERR_ARG, std::string(who) + ": null read arrays");
+  return BPSW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpsw_fmi_load(bpsw_ctx_t* c, int64_t primary, const int64_t L2[5], int64_t seq_len, const uint32_t* bwt, int64_t bwt_size,
+                  int32_t sa_intv, int64_t n_sa, const int64_t* sa) {
+  if (!c || !L2 || !bwt || !sa || seq_len < 1) return fail(BPSW_ERR_ARG, "fmi_load: null argument or empty index");
+  if (seq_len > (int64_t)1 << 41) return fail(BPSW_ERR_LIMIT, "fmi_load: index longer than 2^41 bases");
+  if (bwt_size != (seq_len + 15) / 16 + ((seq_len + 127) / 128 + 1) * 8) return fail(BPSW_ERR_ARG, "fmi_load: bwt_size does not fit seq_len");
+  if (sa_intv < 1 || (sa_intv & (sa_intv - 1))) return fail(BPSW_ERR_ARG, "fmi_load: sa_intv is not a power of two");
+  if (n_sa != (seq_len + sa_intv) / sa_intv) return fail(BPSW_ERR_ARG, "fmi_load: n_sa is not (seq_len + sa_intv) / sa_intv");
+  if (primary < 0 || primary > seq_len || L2[0] != 0 || L2[4] != seq_len) return fail(BPSW_ERR_ARG, "fmi_load: primary or L2 outside the index");
+  for (int i = 0; i < 4; ++i)
+    if (L2[i] > L2[i + 1]) return fail(BPSW_ERR_ARG, "fmi_load: L2 is not cumulative");
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
+  DeviceFmi& fm = device_fmi(c->device);
+  RefWriteHold wr(&fm.gate);
+  std::lock_guard<std::mutex> g(fm.mu);
+  RingPause ring_paused(c->device);
+  HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still read the previous index
+  fm.dev = FmiDev{};
+  fm.seq_len = 0;
+  const size_t bwt_bytes = 4 * (size_t)bwt_size;
+  HIP_TRY(fm.bwt.reserve(bwt_bytes + 64));  // a whole 64-byte block may be read where the array ends inside one
+  HIP_TRY(fm.sa.reserve(8 * (size_t)n_sa));
+  HIP_TRY(hipMemset((uint8_t*)fm.bwt.ptr + bwt_bytes, 0, 64));
+  HIP_TRY(hipMemcpy(fm.bwt.ptr, bwt, bwt_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(fm.sa.ptr, sa, 8 * (size_t)n_sa, hipMemcpyHostToDevice));
+  FmiDev F;
+  F.bwt = (const uint32_t*)fm.bwt.ptr; F.sa = (const long long*)fm.sa.ptr;
+  F.primary = (u64)primary; F.seq_len = (u64)seq_len;
+  for (int i = 0; i < 5; ++i) F.L2[i] = (u64)L2[i];
+  F.sa_shift = 0;
+  while ((1 << F.sa_shift) < sa_intv) ++F.sa_shift;
+  fm.dev = F;
+  fm.seq_len = seq_len;
+  return BPSW_OK;
+}
+
+int bpsw_fmi_unload(bpsw_ctx_t* c) {
+  if (!c) return fail(BPSW_ERR_ARG, "null context");
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
+  DeviceFmi& fm = device_fmi(c->device);
+  RefWriteHold wr(&fm.gate);
+  std::lock_guard<std::mutex> g(fm.mu);
+  RingPause ring_paused(c->device);
+  HIP_TRY(hipDeviceSynchronize());
+  fm.bwt.release();
+  fm.sa.release();
+  fm.dev = FmiDev{};
+  fm.seq_len = 0;
+  return BPSW_OK;
+}
+
+int64_t bpsw_fmi_length(const bpsw_ctx_t* c) {
+  if (!c) return 0;
+  DeviceFmi& fm = device_fmi(c->device);
+  const RefHold hold(&fm.gate);
+  std::lock_guard<std::mutex> g(fm.mu);
+  return (int64_t)fm.seq_len;
+}
+
+int bpsw_seed_batch(bpsw_ctx_t* c, const bpsw_seed_opt_t* sopt, const bpsw_reads_t* reads, int32_t* intv_cnt, bpsw_smem_t* intv,
+                    int64_t intv_cap, int64_t* intv_total, int32_t* seed_cnt, bpsw_seed_t* seeds, int64_t seed_cap, int64_t* seed_total) {
+  if (!c || !sopt || !intv_cnt || !intv_total || !seed_cnt || !seed_total) return fail(BPSW_ERR_ARG, "seed_batch: null argument");
+  int rc = check_reads("seed_batch", reads);
+  if (rc != BPSW_OK) return rc;
+  *intv_total = *seed_total = 0;
+  if (reads->n_reads == 0) return BPSW_OK;
+  std::vector<int32_t> ic, sc;
+  std::vector<bpsw_smem_t> iv;
+  std::vector<bpsw_seed_t> sv;
+  rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv);
+  if (rc != BPSW_OK) return rc;
+  *intv_total = (int64_t)iv.size();
+  *seed_total = (int64_t)sv.size();
+  if ((int64_t)iv.size() > intv_cap || (int64_t)sv.size() > seed_cap || (!iv.empty() && !intv) || (!sv.empty() && !seeds))
+    return fail(BPSW_ERR_CAPACITY, "seed_batch: intv / seeds too small (the totals say what is needed)");
+  memcpy(intv_cnt, ic.data(), 4 * ic.size());
+  memcpy(seed_cnt, sc.data(), 4 * sc.size());
+  if (!iv.empty()) memcpy(intv, iv.data(), sizeof(bpsw_smem_t) * iv.size());
+  if (!sv.empty()) memcpy(seeds, sv.data(), sizeof(bpsw_seed_t) * sv.size());
+  return BPSW_OK;
+}
+
+int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_reads_t* reads, int zdrop_mode,
+                       int flags, int32_t* out_cnt, bpsw_alnreg_t* out_regs, int64_t out_cap, int64_t* out_total) {
+  if (!c || !opt || !sopt || !out_cnt || !out_total) return fail(BPSW_ERR_ARG, "worker1: null argument");
+  int rc = check_reads("worker1", reads);
+  if (rc != BPSW_OK) return rc;
+  *out_total = 0;
+  const int n = reads->n_reads;
+  if (n == 0) return BPSW_OK;
+  const int64_t l_pac = bpsw_ref_length(c);
+  if (l_pac <= 0) return fail(BPSW_ERR_ARG, "worker1: no reference is loaded (bpsw_ref_load)");
+  if (bpsw_fmi_length(c) != 2 * l_pac) return fail(BPSW_ERR_ARG, "worker1: no index is loaded, or its seq_len is not 2 * l_pac (bpsw_fmi_load)");
+  for (int r = 0; r < n; ++r)
+    if (reads->read_len[r] < 1) return fail(BPSW_ERR_ARG, "worker1: empty read");
+  const double t0 = now_ms();
+  std::vector<int32_t> ic, sc;
+  std::vector<bpsw_smem_t> iv;
+  std::vector<bpsw_seed_t> sv;
+  rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv);
+  if (rc != BPSW_OK) return rc;
+  const double t1 = now_ms();
+  // chaining + filter per read (bpsw_chain.cpp), into the shape bpsw_chain2aln_batch takes
+  std::vector<int32_t> chain_cnt((size_t)n), seed_cnt, qbeg, len, cc;
+  std::vector<int64_t> rbeg;
+  std::vector<bpsw_seed_t> cs;
+  size_t at = 0;
+  for (int r = 0; r < n; ++r) {
+    const int m = sc[(size_t)r];
+    cc.resize((size_t)m + 1);
+    cs.resize((size_t)m + 1);
+    const int nc = bpsw_chain_seeds(sopt, opt->w, l_pac, m, sv.data() + at, 1, cc.data(), m, cs.data());
+    if (nc < 0) return nc;
+    at += (size_t)m;
+    chain_cnt[(size_t)r] = nc;
+    size_t k = 0;
+    for (int ch = 0; ch < nc; ++ch) {
+      seed_cnt.push_back(cc[(size_t)ch]);
+      for (int i = 0; i < cc[(size_t)ch]; ++i, ++k) { rbeg.push_back(cs[k].rbeg); qbeg.push_back(cs[k].qbeg); len.push_back(cs[k].len); }
+    }
+  }
+  const double t2 = now_ms();
+  bpsw_chains_t B;
+  B.n_reads = n;
+  B.read_len = reads->read_len; B.read_off = reads->read_off; B.read_pool = reads->read_pool; B.read_pool_bytes = reads->read_pool_bytes;
+  B.chain_cnt = chain_cnt.data(); B.seed_cnt = seed_cnt.data();
+  B.seed_rbeg = rbeg.data(); B.seed_qbeg = qbeg.data(); B.seed_len = len.data();
+  rc = bpsw_chain2aln_batch(c, opt, &B, zdrop_mode, flags, out_cnt, out_regs, out_cap, out_total);
+  t_w1_ms[0] = t1 - t0; t_w1_ms[1] = t2 - t1; t_w1_ms[2] = now_ms() - t2;
+  return rc;
+}
+
+void bpsw_seed_set_resident_lanes(int lanes) { g_seed_lanes.store(lanes > 0 ? lanes : 0, std::memory_order_relaxed); }
+
+void bpsw_last_worker1_times(double ms[3]) {
+  if (ms) memcpy(ms, t_w1_ms, sizeof t_w1_ms);
+}
+
+}  // extern "C"

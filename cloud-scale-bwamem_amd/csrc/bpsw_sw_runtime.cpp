@@ -373,7 +373,7 @@ int bpsw_ref_load(bpsw_ctx_t* c, const uint8_t* pac, int64_t l_pac) {
   const size_t bytes = (size_t)((l_pac + 3) >> 2);
   // the resident kernels of the submission rings end their epochs first (other threads' calls that do not read the reference could
   // keep one alive for as long as they keep coming); the rings are locked until the reference has been replaced
-  struct RingPause { int d; explicit RingPause(int dev) : d(dev) { ring_pause(d); } ~RingPause() { ring_resume(d); } } ring_paused(c->device);
+  RingPause ring_paused(c->device);
   HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still read the previous reference
   HIP_TRY(r.buf.reserve(bytes + 16));
   HIP_TRY(hipMemcpy(r.buf.ptr, pac, bytes, hipMemcpyHostToDevice));
@@ -388,7 +388,7 @@ int bpsw_ref_unload(bpsw_ctx_t* c) {
   DeviceRef& r = device_ref(c->device);
   RefWriteHold wr(&r.gate);
   std::lock_guard<std::mutex> gr(r.mu);
-  struct RingPause { int d; explicit RingPause(int dev) : d(dev) { ring_pause(d); } ~RingPause() { ring_resume(d); } } ring_paused(c->device);
+  RingPause ring_paused(c->device);
   HIP_TRY(hipDeviceSynchronize());
   r.buf.release();
   r.l_pac = 0;

@@ -75,7 +75,8 @@ int bpsw_device_slots(void);                  /* number of entries; 0 = no usabl
 int bpsw_device_for_partition(int partition); /* HIP device index of that entry, -1 = no usable device / negative partition */
 const char *bpsw_last_error(void); /* thread-local text of the last failing call */
 const char *bpsw_version(void); /* "bPSW-hip <major.minor> (gfx950)": structs of this header only ever grow at their end, and the minor
-                                   number changes when one does (0.4: bpsw_stats_t::ext_full_relaunches, bpsw_tail_opt_t::rg_id; 0.5: bpsw_stats_t::sw_ring_calls, ext_ring_calls) */
+                                   number changes when one does (0.4: bpsw_stats_t::ext_full_relaunches, bpsw_tail_opt_t::rg_id; 0.5: bpsw_stats_t::sw_ring_calls, ext_ring_calls;
+                                   0.6: no struct grew -- the FM-index, seeding and worker1 entries below are new) */
 
 /* ---- scoring that boundary 2 does not transmit (zdrop, mat) ------------------ */
 /* defaults: MemOptType (datatype/MemOptType.scala:28-73): a=1 b=4 N=-1, zdrop=100, Scala z-drop parse */
@@ -321,6 +322,80 @@ typedef struct {
 } bpsw_chains_t;
 int bpsw_chain2aln_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_chains_t *batch, int zdrop_mode, int flags,
                          int32_t *out_cnt, bpsw_alnreg_t *out_regs, int64_t out_cap, int64_t *out_total);
+
+/* ---- worker1 from reads: FM-index seeding on the device, chaining and chain filtering on the host ---------------------------
+ *
+ * generateChains + memChainFilter (worker1/MemChain.scala, BWTSMem.scala, MemChainFilter.scala); the pinned behaviour is the C
+ * they were transcribed from: bwt_smem1 / bwt_extend / bwt_sa (native/bwt.c:85-95, 261-347), smem_next2, mem_insert_seed,
+ * mem_chain, mem_chain_flt (native/bwamem.c:117-379).  DESIGN.md lists where the Scala differs in result.
+ *
+ * The index is what the aligner's .bwt and .sa files hold and BWTType loads: primary, L2[5] (L2[0] == 0), seq_len == L2[4], the
+ * uint32 BWT array in the interleaved form of bwt_occ_intv (native/bwt.h: every 128 bases four 64-bit occurrence counts, then eight
+ * words of 2-bit bases; bwt_size == (seq_len + 15) / 16 + ((seq_len + 127) / 128 + 1) * 8 words), sa_intv (a power of two), n_sa ==
+ * (seq_len + sa_intv) / sa_intv and the sampled suffix array with sa[0] == -1.  Like the reference of bpsw_ref_load it belongs to
+ * the DEVICE of the context it was loaded through, is seen by every context of that device, and must not be loaded or unloaded
+ * while calls are in flight on it.  It stays on the device until bpsw_fmi_unload (or the end of the process): bpsw_destroy of the
+ * loading context does not free it, as it does not free the reference.  BPSW_ERR_ARG for a bwt_size, sa_intv or n_sa that
+ * contradicts seq_len. */
+int bpsw_fmi_load(bpsw_ctx_t *ctx, int64_t primary, const int64_t L2[5], int64_t seq_len, const uint32_t *bwt, int64_t bwt_size,
+                  int32_t sa_intv, int64_t n_sa, const int64_t *sa);
+int bpsw_fmi_unload(bpsw_ctx_t *ctx);
+int64_t bpsw_fmi_length(const bpsw_ctx_t *ctx); /* seq_len of the loaded index, 0 if none */
+
+#define BPSW_MEM_F_NO_EXACT 0x40 /* native/bwamem.h:19: what bpsw_seed_opt_t.no_exact stands for */
+#define BPSW_SEED_MAX_QLEN 256   /* read length of the seeding entries: the round loop's limit (bpsw_chain2aln_batch) */
+typedef struct { /* the mem_opt_t fields seeding, chaining and the chain filter read (native/bwamem.h:21-47) */
+  int32_t min_seed_len, max_occ, split_width, max_chain_gap, no_exact;
+  float split_factor, chain_drop_ratio, mask_level;
+} bpsw_seed_opt_t;
+void bpsw_seed_opt_default(bpsw_seed_opt_t *s); /* == mem_opt_init, native/bwamem.c:45-74 */
+
+typedef struct { /* reads: codes 0..4 in read_pool, at most BPSW_SEED_MAX_QLEN bases each */
+  int32_t n_reads;
+  const int32_t *read_len;
+  const int64_t *read_off;
+  const uint8_t *read_pool;
+  size_t read_pool_bytes;
+} bpsw_reads_t;
+typedef struct { /* one bi-interval of smem_next2 (bwtintv_t: x[3], info = qbeg << 32 | qend), in the order the reference visits them */
+  int64_t x0, x1, x2;
+  int32_t qbeg, qend;
+  int32_t kept; /* 1: passes mem_insert_seed's filter (qend - qbeg >= min_seed_len and x2 <= max_occ), 0: skipped there */
+  int32_t pad_;
+} bpsw_smem_t; /* 40 bytes */
+typedef struct { /* mem_seed_t, native/bwamem.c:167-170 */
+  int64_t rbeg;
+  int32_t qbeg, len;
+} bpsw_seed_t; /* 16 bytes */
+
+/* The device part alone: per read the bi-intervals of every smem_next2 call until the read is used up (BEFORE the filter; `kept`
+ * records its verdict) and the seeds of the kept ones -- bwt_sa(x0 + k), interval order then k ascending, seeds bridging l_pac ==
+ * seq_len / 2 dropped (native/bwamem.c:228) -- both lists concatenated in read order.  A read shorter than min_seed_len has no
+ * intervals and no seeds (mem_chain returns before seeding).  BPSW_ERR_CAPACITY with *intv_total / *seed_total set to what is
+ * needed when a list does not fit; BPSW_ERR_LIMIT for a read longer than BPSW_SEED_MAX_QLEN; BPSW_ERR_ARG when no index is loaded. */
+int bpsw_seed_batch(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, const bpsw_reads_t *reads, int32_t *intv_cnt, bpsw_smem_t *intv,
+                    int64_t intv_cap, int64_t *intv_total, int32_t *seed_cnt, bpsw_seed_t *seeds, int64_t seed_cap,
+                    int64_t *seed_total);
+
+/* Host only (no context, no GPU), one read: its seeds in emission order -> chains.  Chaining is mem_insert_seed's tree side
+ * (test_and_merge against the chain with the largest pos <= rbeg, else a new chain; the chains come out in the B-tree's in-order
+ * traversal, chains of equal pos included, in the order kbtree.h leaves them); with `filter` != 0 mem_chain_flt follows.
+ * w is mem_opt_t.w (bpsw_opt_t.w).  Output in the shape of bpsw_chains_t: chain_seed_cnt[chain] and the seeds concatenated;
+ * chain_cap >= n_seeds and out_seeds of n_seeds entries always suffice.  Returns the number of chains or a negative error. */
+int bpsw_chain_seeds(const bpsw_seed_opt_t *sopt, int32_t w, int64_t l_pac, int32_t n_seeds, const bpsw_seed_t *seeds, int32_t filter,
+                     int32_t *chain_seed_cnt, int32_t chain_cap, bpsw_seed_t *out_seeds);
+
+/* worker1 from reads to regions: bpsw_seed_batch, bpsw_chain_seeds with the filter per read, then bpsw_chain2aln_batch as it is
+ * (zdrop_mode, flags, out_* exactly as there; *out_total is set to the needed out_cap on BPSW_ERR_CAPACITY).  Needs the reference
+ * (bpsw_ref_load) and an index with seq_len == 2 * l_pac on the context's device. */
+int bpsw_worker1_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_reads_t *reads, int zdrop_mode,
+                       int flags, int32_t *out_cnt, bpsw_alnreg_t *out_regs, int64_t out_cap, int64_t *out_total);
+/* Diagnostics: the number of lanes (reads in flight, a multiple of 64) seed_smem_kernel keeps resident, process-wide; 0 = the default,
+ * 256 per compute unit (bpsw_device_cus).  Each resident lane owns four lists of (longest read of the batch + 1) intervals of 32
+ * bytes in a per-context arena: 2.2 GB at 256 bases on 256 CUs.  The tests lower it to reach the grid-stride path with a small batch. */
+void bpsw_seed_set_resident_lanes(int lanes);
+/* wall time of the calling thread's most recent bpsw_worker1_batch (ms): seeding call, host chaining, round loop call */
+void bpsw_last_worker1_times(double ms[3]);
 
 /* ---- worker2's tail: everything after the rescue ------------------------------------------
  *

@@ -1,0 +1,172 @@
+#!/usr/bin/env python3
+"""Throughput of worker1 from reads (bpsw_seed_batch, the host chaining, bpsw_worker1_batch) on a synthetic genome, next to the
+reference's mem_chain on the same reads from oracle/_ref/libbwaref.so on 16 threads where that library is built.
+
+    python tools/seed_throughput.py [--genome-mb 50] [--reads 100000] [--read-len 150] [--sa-intv 32] [--reps 5] [--threads 16]
+
+The index is built here (numpy): a random genome has practically no repeated 27-mer, so the suffix array is one sort by the
+27-base prefix and a byte-wise comparison inside the few groups that tie.  After one warm-up call the median of --reps calls is
+reported, one JSON line.  The three stage times of a bpsw_worker1_batch call come from bpsw_last_worker1_times."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "cloud-scale-bwamem_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+import bpsw_hip  # noqa: E402
+import fmi_util as fu  # noqa: E402
+import pyoracle  # noqa: E402
+from bpsw_hip import fmi  # noqa: E402
+
+K = 27  # 5^27 < 2^63: the prefix of K bases (digit = base + 1, 0 past the end) as one integer
+
+
+def suffix_array_random_text(text):
+    n = text.size
+    digits = np.zeros(n + K, np.int64)
+    digits[:n] = text.astype(np.int64) + 1
+    key = np.zeros(n, np.int64)
+    for j in range(K):
+        key *= 5
+        key += digits[j: j + n]
+    order = np.argsort(key, kind="stable")
+    ks = key[order]
+    ties = np.nonzero(ks[1:] == ks[:-1])[0]
+    if ties.size:
+        b = text.tobytes()
+        starts = ties[np.concatenate([[True], np.diff(ties) > 1])]
+        for s in starts:
+            e = s + 1
+            while e < n and ks[e] == ks[s]:
+                e += 1
+            grp = sorted(order[s:e].tolist(), key=lambda i: b[i:])
+            order[s:e] = grp
+    return np.concatenate([[n], order]).astype(np.int64), int(ties.size)
+
+
+def build_index(fwd, sa_intv):
+    text = fu.doubled(fwd)
+    n = text.size
+    sa, n_ties = suffix_array_random_text(text)
+    primary = int(np.nonzero(sa == 0)[0][0])
+    bwt = text[sa[sa != 0] - 1]
+    L2 = np.zeros(5, np.int64)
+    L2[1:] = np.cumsum(np.bincount(text, minlength=4))
+    n_words, n_blk = (n + 15) // 16, (n + 127) // 128
+    padded = np.zeros(n_blk * 128, np.uint32)
+    padded[:n] = bwt
+    words = np.zeros(n_blk * 8, np.uint32)
+    for j in range(16):
+        words |= padded[j::16] << np.uint32(30 - 2 * j)
+    cnt = np.zeros((n_blk + 1, 4), np.uint64)
+    for c in range(4):
+        per = (padded.reshape(n_blk, 128) == c).sum(axis=1).astype(np.uint64)
+        if c == 0:
+            per[-1] -= np.uint64(n_blk * 128 - n)   # the padding reads as A
+        cnt[1:, c] = np.cumsum(per)
+    arr = np.zeros((n_blk, 16), np.uint32)
+    arr[:, :8] = cnt[:n_blk].view(np.uint32).reshape(n_blk, 8)
+    arr[:, 8:] = words.reshape(n_blk, 8)
+    flat = arr.reshape(-1)[: (n_blk - 1) * 16 + 8 + (n_words - (n_blk - 1) * 8)]
+    flat = np.ascontiguousarray(np.concatenate([flat, cnt[n_blk].view(np.uint32)]))
+    assert flat.size == n_words + (n_blk + 1) * 8
+    samp = sa[::sa_intv].copy()
+    samp[0] = -1
+    return fmi.FmIndex(primary=primary, L2=L2, seq_len=n, bwt=flat, sa_intv=sa_intv, sa=samp), n_ties
+
+
+def make_reads(fwd, n, ln, rng):
+    pos = rng.integers(0, fwd.size - ln, n)
+    pool = fwd[(pos[:, None] + np.arange(ln)[None, :])].astype(np.uint8)
+    mut = rng.random((n, ln)) < 0.01
+    pool = np.where(mut, (pool + rng.integers(1, 4, (n, ln))) & 3, pool).astype(np.uint8)
+    rev = rng.random(n) < 0.5
+    pool[rev] = 3 - pool[rev, ::-1]
+    return fmi.ReadBatch(np.full(n, ln, np.int32), (np.arange(n, dtype=np.int64) * ln), np.ascontiguousarray(pool.reshape(-1)))
+
+
+def reference_mem_chain(idx, l_pac, rb, threads):
+    ref = fu.RefSeeding(pyoracle.REF_SO)
+    bwt = fu.ref_bwt(idx)
+    o = ref.opt()
+    n, ln = rb.n_reads, int(rb.read_len[0])
+    base = rb.read_pool.ctypes.data
+
+    def work(lo, hi):
+        for r in range(lo, hi):
+            v = ref.lib.mem_chain(o, C.addressof(bwt), l_pac, ln, C.c_void_p(base + r * ln))
+            for i in range(v.n):
+                ref.libc.free(v.a[i].seeds)
+            if v.a:
+                ref.libc.free(v.a)
+    cuts = np.linspace(0, n, threads + 1).astype(int)
+    ts = [threading.Thread(target=work, args=(cuts[i], cuts[i + 1])) for i in range(threads)]
+    t0 = time.perf_counter()
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    return n / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--genome-mb", type=float, default=50.0)
+    ap.add_argument("--reads", type=int, default=100_000)
+    ap.add_argument("--read-len", type=int, default=150)
+    ap.add_argument("--sa-intv", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--threads", type=int, default=16)
+    a = ap.parse_args()
+    rng = np.random.default_rng(20260101)
+    l_pac = int(a.genome_mb * 1e6) | 1
+    fwd = rng.integers(0, 4, l_pac).astype(np.uint8)
+    t0 = time.perf_counter()
+    idx, n_ties = build_index(fwd, a.sa_intv)
+    t_build = time.perf_counter() - t0
+    rb = make_reads(fwd, a.reads, a.read_len, rng)
+    ctx = bpsw_hip.Context(0)
+    ctx.ref_load(fu.pack_pac(fwd), l_pac)
+    ctx.fmi_load(idx)
+    opt, so = bpsw_hip.default_opt(), bpsw_hip.default_seed_opt()
+    seed_s, w1_s, stages = [], [], []
+    n_intv = n_seeds = n_regs = 0
+    for k in range(a.reps + 1):
+        t0 = time.perf_counter()
+        icnt, iv, scnt, sv = ctx.seed_batch(so, rb)
+        t1 = time.perf_counter()
+        cnt, regs = ctx.worker1_batch(opt, so, rb, flags=bpsw_hip.C2A_SORT_DEDUP)
+        t2 = time.perf_counter()
+        if k:
+            seed_s.append(t1 - t0); w1_s.append(t2 - t1); stages.append(bpsw_hip.last_worker1_times())
+        n_intv, n_seeds, n_regs = int(icnt.sum()), int(scnt.sum()), int(cnt.sum())
+    st = np.median(np.array(stages), axis=0)
+    res = {
+        "genome_bases": l_pac, "index_bytes": int(idx.bwt.nbytes + idx.sa.nbytes), "sa_intv": a.sa_intv, "index_build_s": round(t_build, 1),
+        "tied_27mers": n_ties, "reads": a.reads, "read_len": a.read_len, "reps": a.reps,
+        "intervals_per_read": round(n_intv / a.reads, 2), "seeds_per_read": round(n_seeds / a.reads, 2), "regions_per_read": round(n_regs / a.reads, 2),
+        "seed_batch_reads_per_s": round(a.reads / float(np.median(seed_s))),
+        "worker1_batch_reads_per_s": round(a.reads / float(np.median(w1_s))),
+        "worker1_stage_ms": {"seeding_call": round(float(st[0]), 2), "host_chaining": round(float(st[1]), 2), "round_loop_call": round(float(st[2]), 2)},
+        "seeding_stage_reads_per_s": round(a.reads / (float(st[0]) / 1e3)),
+        "host_chaining_reads_per_s": round(a.reads / max(float(st[1]) / 1e3, 1e-9)),
+        "round_loop_reads_per_s": round(a.reads / max(float(st[2]) / 1e3, 1e-9)),
+    }
+    res["bound_by"] = ("seeding_call", "host_chaining", "round_loop_call")[int(np.argmax(st))]
+    if os.path.exists(pyoracle.REF_SO):
+        res["reference_mem_chain_reads_per_s"] = round(reference_mem_chain(idx, l_pac, rb, a.threads))
+        res["reference_threads"] = a.threads
+    ctx.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
