@@ -106,6 +106,8 @@ struct SwScoring {
   int a, b, o_del, e_del, o_ins, e_ins;
   int xtra;
 };
+// validates opt into *sc: a >= 1, gap opens >= 0, gap extensions >= min_gap_ext (0 or 1); errors are reported as "<who>: ..."
+int make_scoring(const char* who, const bpsw_opt_t* opt, int xtra, int min_gap_ext, SwScoring* sc);
 
 struct SwJobsDev {  // all device pointers
   int n;
@@ -281,6 +283,13 @@ void rescue_scratch_free(void* p);
 // ---- error text -----------------------------------------------------------------------------------
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+inline int hip_fail(hipError_t e, const char* what) { return fail(BPSW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+#define HIP_TRY(expr)                                         \
+  do {                                                        \
+    hipError_t e_ = (expr);                                   \
+    if (e_ != hipSuccess) return ::bpsw::hip_fail(e_, #expr); \
+  } while (0)
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // ---- context ----------------------------------------------------------------------------------------
 struct DeviceBuffer {
@@ -295,6 +304,9 @@ struct PinnedBuffer {
   hipError_t reserve(size_t bytes);
   void release();
 };
+}  // namespace bpsw
+#include "bpsw_stage.h"  // StageLayout, StageIn, StageOut: one staged block over the two buffer types above
+namespace bpsw {
 
 // The 2-bit reference (bpsw_ref_load) is shared by every context of a device: the JNI shim keeps one context per
 // Spark task thread, and 20 copies of a 0.8 GB genome would be pointless.
@@ -405,7 +417,7 @@ struct CopyLane {
   hipEvent_t ev = nullptr;
 };
 CopyLane& copy_lane(int device);
-double wall_ms();
+double wall_ms();  // the monotonic clock, in ms
 void ext_call_mark(int device);      // an extension call of the device begins / ends now (bpsw_runtime.cpp)
 double ext_call_age_ms(int device);  // ms since the last such mark (huge: never)
 double stat_ms();  // wall_ms, or the thread CPU clock with BPSW_STATS_CLOCK=cpu (bpsw_runtime.cpp)

@@ -255,8 +255,6 @@ bool replay_pair(Group& G, int k, size_t ti, std::vector<Reg> v[2], std::vector<
   return true;
 }
 
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 namespace bpsw {

@@ -23,14 +23,6 @@ int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-static int hip_fail(hipError_t e, const char* what) {
-  return fail(BPSW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                   \
-  do {                                                  \
-    hipError_t e_ = (expr);                             \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr);   \
-  } while (0)
 
 // hipFree / hipHostFree wait for everything on the device -- which, with a resident kernel of the submission ring that other threads keep
 // feeding, is for as long as they keep coming: the open epochs are closed first (a few hundred microseconds) and the rings held until
@@ -83,6 +75,18 @@ MatRows pack_mat(const int8_t mat[25]) {
     m.row[k] = r;
   }
   return m;
+}
+
+int make_scoring(const char* who, const bpsw_opt_t* opt, int xtra, int min_gap_ext, SwScoring* sc) {
+  if (!opt) return fail(BPSW_ERR_ARG, std::string(who) + ": null options");
+  if (opt->a < 1 || opt->o_del < 0 || opt->e_del < min_gap_ext || opt->o_ins < 0 || opt->e_ins < min_gap_ext)
+    return fail(BPSW_ERR_ARG, std::string(who) + (min_gap_ext > 0 ? ": scoring must have a >= 1, non-negative gap opens and gap extensions >= 1"
+                                                                  : ": scoring must have a >= 1 and non-negative gap penalties"));
+  sc->mat = pack_mat(opt->mat);
+  sc->a = opt->a; sc->b = opt->b;
+  sc->o_del = opt->o_del; sc->e_del = opt->e_del; sc->o_ins = opt->o_ins; sc->e_ins = opt->e_ins;
+  sc->xtra = xtra;
+  return BPSW_OK;
 }
 
 // The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), round robin, and streams that

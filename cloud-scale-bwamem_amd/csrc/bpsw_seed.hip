@@ -16,7 +16,6 @@
 #include <string.h>
 
 #include <atomic>
-#include <chrono>
 
 #include "bpsw_internal.h"
 
@@ -292,14 +291,6 @@ DeviceFmi& device_fmi(int device) {
   return table[device >= 0 && device < 64 ? device : 0];
 }
 
-int hip_fail(hipError_t e, const char* what) { return fail(BPSW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // lanes of seed_smem_kernel resident at a time: four wavefronts per compute unit (one per SIMD), each lane with four lists of
 // read_len + 1 intervals of 32 bytes -- 32.9 KB a lane at 256 bases, 2.2 GB on 256 CUs; 1.3 GB at 150 bases.
 // bpsw_seed_set_resident_lanes (diagnostics, include/bpsw.h) overrides the count.
@@ -311,7 +302,6 @@ int seed_resident_waves(int num_cu, long long n_reads) {
   return (int)(need < waves ? need : waves);
 }
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 thread_local double t_w1_ms[3] = {0., 0., 0.};
 
 // seeding of a validated batch: per read the intervals and the seeds (bridging ones dropped), concatenated in read order
@@ -343,16 +333,11 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   P.split_len0 = (int)(so.min_seed_len * so.split_factor + .499);
 
   // ---- intervals ----
-  const size_t o_len = 0, o_off = align16(4 * (size_t)n), o_pool = align16(o_off + 8 * (size_t)n);
-  const size_t in_total = align16(o_pool + R.read_pool_bytes + 16);
-  HIP_TRY(c->h_stage_in.reserve(in_total));
-  HIP_TRY(d_in.reserve(in_total));
-  uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
-  memcpy(h + o_len, R.read_len, 4 * (size_t)n);
-  memcpy(h + o_off, R.read_off, 8 * (size_t)n);
-  if (R.read_pool_bytes) memcpy(h + o_pool, R.read_pool, R.read_pool_bytes);
-  uint8_t* d = (uint8_t*)d_in.ptr;
-  HIP_TRY(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, c->stream));
+  StageIn in;
+  const int i_len = in.add(R.read_len, 4 * (size_t)n), i_off = in.add(R.read_off, 8 * (size_t)n);
+  const int i_pool = in.add(R.read_pool, R.read_pool_bytes);
+  in.add(nullptr, 16);  // room behind the pool
+  HIP_TRY(in.stage(c->h_stage_in, d_in, c->stream));
   const int waves = seed_resident_waves(c->num_cu, n);
   const int list_cap = max_len + 1;
   HIP_TRY(d_arena.reserve((size_t)waves * 4 * (size_t)list_cap * 64 * sizeof(Intv)));
@@ -361,58 +346,48 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   // 16 n + (the intervals of the overflowing reads), whatever one repeat-rich read produces
   const int stride = 16;
   {
-    const size_t o_cnt = 0, o_ovf = align16(4 * (size_t)n), o_rec = align16(o_ovf + 16);
-    const size_t out_total = o_rec + sizeof(bpsw_smem_t) * (size_t)n * (size_t)stride;
-    HIP_TRY(d_out.reserve(out_total));
-    HIP_TRY(c->h_stage_out.reserve(out_total));
-    uint8_t* dout = (uint8_t*)d_out.ptr;
-    HIP_TRY(hipMemsetAsync(dout + o_ovf, 0, 16, c->stream));
+    StageOut out;
+    const int r_cnt = out.add(4 * (size_t)n), r_ovf = out.add(16), r_rec = out.add(sizeof(bpsw_smem_t) * (size_t)n * (size_t)stride);
+    HIP_TRY(out.reserve(c->h_stage_out, d_out));
+    HIP_TRY(hipMemsetAsync(out.dev<int>(r_ovf), 0, 16, c->stream));
     hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves), dim3(64), 0, c->stream, F, P, n, (const int32_t*)nullptr,
-                       (const int32_t*)(d + o_len), (const long long*)(d + o_off), (const uint8_t*)(d + o_pool), (Intv*)d_arena.ptr, list_cap,
-                       (bpsw_smem_t*)(dout + o_rec), stride, (const long long*)nullptr, (int32_t*)(dout + o_cnt), (int*)(dout + o_ovf));
+                       in.dev<int32_t>(i_len), in.dev<long long>(i_off), in.dev<uint8_t>(i_pool), (Intv*)d_arena.ptr, list_cap,
+                       out.dev<bpsw_smem_t>(r_rec), stride, (const long long*)nullptr, out.dev<int32_t>(r_cnt), out.dev<int>(r_ovf));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, out_total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(out.fetch(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint8_t* ho = (const uint8_t*)c->h_stage_out.ptr;
-    if (*(const int*)(ho + o_ovf)) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
-    const int32_t* cnt = (const int32_t*)(ho + o_cnt);
+    if (*out.host<int>(r_ovf)) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
+    const int32_t* cnt = out.host<int32_t>(r_cnt);
     icnt->assign(cnt, cnt + n);
     std::vector<int32_t> todo;
     std::vector<long long> base(1, 0);
     for (int r = 0; r < n; ++r)
       if (cnt[r] > stride) { todo.push_back(r); base.push_back(base.back() + cnt[r]); }
     std::vector<bpsw_smem_t> first;  // the first pass's rows, taken out of the pinned block before the second pass reuses it
-    const bpsw_smem_t* rec = (const bpsw_smem_t*)(ho + o_rec);
+    const bpsw_smem_t* rec = out.host<bpsw_smem_t>(r_rec);
     const bpsw_smem_t* more = nullptr;
     if (!todo.empty()) {
       first.assign(rec, rec + (size_t)n * (size_t)stride);
       rec = first.data();
       const size_t m = todo.size();
-      const size_t t_todo = 0, t_base = align16(4 * m), t_total = align16(t_base + 8 * (m + 1));
-      const size_t r_cnt = 0, r_ovf = align16(4 * m), r_rec = align16(r_ovf + 16), r_total = r_rec + sizeof(bpsw_smem_t) * (size_t)base.back();
-      HIP_TRY(c->h_stage_in.reserve(t_total));
-      HIP_TRY(d_sa_in.reserve(t_total));
-      HIP_TRY(d_out.reserve(r_total));
-      HIP_TRY(c->h_stage_out.reserve(r_total));
-      uint8_t* ht = (uint8_t*)c->h_stage_in.ptr;
-      memcpy(ht + t_todo, todo.data(), 4 * m);
-      memcpy(ht + t_base, base.data(), 8 * (m + 1));
-      uint8_t* dt = (uint8_t*)d_sa_in.ptr;
-      dout = (uint8_t*)d_out.ptr;
-      HIP_TRY(hipMemcpyAsync(dt, ht, t_total, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipMemsetAsync(dout + r_ovf, 0, 16, c->stream));
+      StageIn in2;
+      const int i_todo = in2.add(todo.data(), 4 * m), i_base = in2.add(base.data(), 8 * (m + 1));
+      StageOut out2;
+      const int r2_cnt = out2.add(4 * m), r2_ovf = out2.add(16), r2_rec = out2.add(sizeof(bpsw_smem_t) * (size_t)base.back());
+      HIP_TRY(out2.reserve(c->h_stage_out, d_out));
+      HIP_TRY(in2.stage(c->h_stage_in, d_sa_in, c->stream));
+      HIP_TRY(hipMemsetAsync(out2.dev<int>(r2_ovf), 0, 16, c->stream));
       const int waves2 = seed_resident_waves(c->num_cu, (long long)m);
-      hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves2), dim3(64), 0, c->stream, F, P, (int)m, (const int32_t*)(dt + t_todo),
-                         (const int32_t*)(d + o_len), (const long long*)(d + o_off), (const uint8_t*)(d + o_pool), (Intv*)d_arena.ptr, list_cap,
-                         (bpsw_smem_t*)(dout + r_rec), 0, (const long long*)(dt + t_base), (int32_t*)(dout + r_cnt), (int*)(dout + r_ovf));
+      hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves2), dim3(64), 0, c->stream, F, P, (int)m, in2.dev<int32_t>(i_todo),
+                         in.dev<int32_t>(i_len), in.dev<long long>(i_off), in.dev<uint8_t>(i_pool), (Intv*)d_arena.ptr, list_cap,
+                         out2.dev<bpsw_smem_t>(r2_rec), 0, in2.dev<long long>(i_base), out2.dev<int32_t>(r2_cnt), out2.dev<int>(r2_ovf));
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, r_total, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(out2.fetch(c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
-      const uint8_t* h2 = (const uint8_t*)c->h_stage_out.ptr;
-      const int32_t* cnt2 = (const int32_t*)(h2 + r_cnt);
+      const int32_t* cnt2 = out2.host<int32_t>(r2_cnt);
       for (size_t i = 0; i < m; ++i)
         if (cnt2[i] != (*icnt)[(size_t)todo[i]]) return fail(BPSW_ERR_DEVICE, "seed: interval counts changed between two runs");
-      more = (const bpsw_smem_t*)(h2 + r_rec);
+      more = out2.host<bpsw_smem_t>(r2_rec);
     }
     intv->clear();
     size_t ti = 0;
@@ -448,23 +423,18 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   if (n_occ > 0x3fffffffll) return fail(BPSW_ERR_LIMIT, "seed: more than 2^30 seed occurrences in one batch");
   const size_t nk = occ_base.size();
   occ_base.push_back(n_occ);
-  const size_t s_base = 0, s_x0 = align16(8 * (nk + 1)), s_q = align16(s_x0 + 8 * nk), s_total = align16(s_q + 8 * nk);
-  HIP_TRY(c->h_stage_in.reserve(s_total));
-  HIP_TRY(d_sa_in.reserve(s_total));
-  HIP_TRY(d_sa_out.reserve(sizeof(bpsw_seed_t) * (size_t)n_occ));
-  HIP_TRY(c->h_stage_out.reserve(sizeof(bpsw_seed_t) * (size_t)n_occ));
-  h = (uint8_t*)c->h_stage_in.ptr;
-  memcpy(h + s_base, occ_base.data(), 8 * (nk + 1));
-  memcpy(h + s_x0, kept_x0.data(), 8 * nk);
-  memcpy(h + s_q, kept_q.data(), 8 * nk);
-  uint8_t* ds = (uint8_t*)d_sa_in.ptr;
-  HIP_TRY(hipMemcpyAsync(ds, h, s_total, hipMemcpyHostToDevice, c->stream));
+  StageIn sin;
+  const int i_base = sin.add(occ_base.data(), 8 * (nk + 1)), i_x0 = sin.add(kept_x0.data(), 8 * nk), i_q = sin.add(kept_q.data(), 8 * nk);
+  StageOut sout;
+  const int r_seeds = sout.add(sizeof(bpsw_seed_t) * (size_t)n_occ);
+  HIP_TRY(sout.reserve(c->h_stage_out, d_sa_out));
+  HIP_TRY(sin.stage(c->h_stage_in, d_sa_in, c->stream));
   hipLaunchKernelGGL(seed_sa_kernel, dim3((unsigned)((n_occ + 255) / 256)), dim3(256), 0, c->stream, F, n_occ, (int)nk,
-                     (const long long*)(ds + s_base), (const long long*)(ds + s_x0), (const int2*)(ds + s_q), (bpsw_seed_t*)d_sa_out.ptr);
+                     sin.dev<long long>(i_base), sin.dev<long long>(i_x0), sin.dev<int2>(i_q), sout.dev<bpsw_seed_t>(r_seeds));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, d_sa_out.ptr, sizeof(bpsw_seed_t) * (size_t)n_occ, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(sout.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const bpsw_seed_t* all = (const bpsw_seed_t*)c->h_stage_out.ptr;
+  const bpsw_seed_t* all = sout.host<bpsw_seed_t>(r_seeds);
   seeds->reserve((size_t)n_occ);
   for (int r = 0; r < n; ++r) {
     int m = 0;
@@ -585,13 +555,13 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
   if (bpsw_fmi_length(c) != 2 * l_pac) return fail(BPSW_ERR_ARG, "worker1: no index is loaded, or its seq_len is not 2 * l_pac (bpsw_fmi_load)");
   for (int r = 0; r < n; ++r)
     if (reads->read_len[r] < 1) return fail(BPSW_ERR_ARG, "worker1: empty read");
-  const double t0 = now_ms();
+  const double t0 = wall_ms();
   std::vector<int32_t> ic, sc;
   std::vector<bpsw_smem_t> iv;
   std::vector<bpsw_seed_t> sv;
   rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv);
   if (rc != BPSW_OK) return rc;
-  const double t1 = now_ms();
+  const double t1 = wall_ms();
   // chaining + filter per read (bpsw_chain.cpp), into the shape bpsw_chain2aln_batch takes
   std::vector<int32_t> chain_cnt((size_t)n), seed_cnt, qbeg, len, cc;
   std::vector<int64_t> rbeg;
@@ -611,14 +581,14 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
       for (int i = 0; i < cc[(size_t)ch]; ++i, ++k) { rbeg.push_back(cs[k].rbeg); qbeg.push_back(cs[k].qbeg); len.push_back(cs[k].len); }
     }
   }
-  const double t2 = now_ms();
+  const double t2 = wall_ms();
   bpsw_chains_t B;
   B.n_reads = n;
   B.read_len = reads->read_len; B.read_off = reads->read_off; B.read_pool = reads->read_pool; B.read_pool_bytes = reads->read_pool_bytes;
   B.chain_cnt = chain_cnt.data(); B.seed_cnt = seed_cnt.data();
   B.seed_rbeg = rbeg.data(); B.seed_qbeg = qbeg.data(); B.seed_len = len.data();
   rc = bpsw_chain2aln_batch(c, opt, &B, zdrop_mode, flags, out_cnt, out_regs, out_cap, out_total);
-  t_w1_ms[0] = t1 - t0; t_w1_ms[1] = t2 - t1; t_w1_ms[2] = now_ms() - t2;
+  t_w1_ms[0] = t1 - t0; t_w1_ms[1] = t2 - t1; t_w1_ms[2] = wall_ms() - t2;
   return rc;
 }
 

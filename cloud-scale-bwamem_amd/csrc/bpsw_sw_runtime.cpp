@@ -8,32 +8,6 @@
 
 using namespace bpsw;
 
-namespace {
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(BPSW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-int make_scoring(const bpsw_opt_t* opt, int xtra, SwScoring* sc) {
-  if (!opt) return fail(BPSW_ERR_ARG, "swalign: null options");
-  if (opt->a < 1 || opt->o_del < 0 || opt->e_del < 0 || opt->o_ins < 0 || opt->e_ins < 0)
-    return fail(BPSW_ERR_ARG, "swalign: scoring must have a >= 1 and non-negative gap penalties");
-  sc->mat = pack_mat(opt->mat);
-  sc->a = opt->a; sc->b = opt->b;
-  sc->o_del = opt->o_del; sc->e_del = opt->e_del; sc->o_ins = opt->o_ins; sc->e_ins = opt->e_ins;
-  sc->xtra = xtra;
-  return BPSW_OK;
-}
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-}  // namespace
-
 namespace bpsw {
 
 DeviceRef& device_ref(int device) {
@@ -53,11 +27,13 @@ RefHold ref_snapshot(const bpsw_ctx* c, const uint8_t** pac, long long* l_pac) {
 int sw_stage_begin(bpsw_ctx* c, int n, size_t q_pool_bytes, size_t t_pool_bytes, SwStage* st) {
   st->n = n;
   st->q_pool_bytes = q_pool_bytes; st->t_pool_bytes = t_pool_bytes;
-  st->o_qlen = 0; st->o_tlen = align16(st->o_qlen + 4 * (size_t)n); st->o_qoff = align16(st->o_tlen + 4 * (size_t)n);
-  st->o_toff = align16(st->o_qoff + 8 * (size_t)n); st->o_qrev = align16(st->o_toff + 8 * (size_t)n);
-  st->o_qpool = align16(st->o_qrev + (size_t)n); st->o_tpool = align16(st->o_qpool + q_pool_bytes);
-  st->o_packed = (st->o_tpool + t_pool_bytes + 63) & ~(size_t)63;  // job records for the packed kernel (sw_stage_run)
-  st->total = align16(st->o_packed + 32 * (size_t)n);
+  StageLayout lay;
+  st->o_qlen = lay.add(4 * (size_t)n); st->o_tlen = lay.add(4 * (size_t)n);
+  st->o_qoff = lay.add(8 * (size_t)n); st->o_toff = lay.add(8 * (size_t)n);
+  st->o_qrev = lay.add((size_t)n);
+  st->o_qpool = lay.add(q_pool_bytes); st->o_tpool = lay.add(t_pool_bytes);
+  st->o_packed = lay.add(32 * (size_t)n, 64);  // job records for the packed kernel (sw_stage_run)
+  st->total = lay.total();
   HIP_TRY(c->h_stage_in.reserve(st->total));
   HIP_TRY(c->h_stage_out.reserve(28 * (size_t)n));
   st->base = (uint8_t*)c->h_stage_in.ptr;
@@ -72,7 +48,7 @@ void sw_launch_in_flight(int device, int delta) { g_sw_in_flight[device >= 0 && 
 
 int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st, int mq, int mt, bool pac_mode, const int32_t** results) {
   SwScoring sc;
-  int rc = make_scoring(opt, xtra, &sc);
+  int rc = make_scoring("swalign", opt, xtra, 0, &sc);
   if (rc != BPSW_OK) return rc;
   const int n = st.n;
   const uint8_t* d_pac = nullptr;
@@ -205,7 +181,7 @@ int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st
 // Jobs whose arrays live in host memory: validate, stage the job table + pools in one pinned block, run.
 int run_sw_jobs_host(bpsw_ctx* c, const bpsw_opt_t* opt, const bpsw_sw_jobs_t* j, int32_t* out) {
   SwScoring sc;
-  int rc = make_scoring(opt, j->xtra, &sc);
+  int rc = make_scoring("swalign", opt, j->xtra, 0, &sc);
   if (rc != BPSW_OK) return rc;
   const int n = j->n;
   if (n == 0) return BPSW_OK;
@@ -275,7 +251,7 @@ int finish_pending_sw(bpsw_ctx* c) {
   c->sw_geom_qlen = h_pre->max_qlen; c->sw_geom_tlen = h_pre->max_tlen;
   if (h_pre->max_qlen > p.cap_qlen || h_pre->max_tlen > p.cap_tlen) {  // the kernel left the jobs untouched: launch for the real geometry
     SwScoring sc;
-    int rc = make_scoring(&p.opt, p.jobs.xtra, &sc);
+    int rc = make_scoring("swalign", &p.opt, p.jobs.xtra, 0, &sc);
     if (rc != BPSW_OK) return rc;
     const uint8_t* d_pac = nullptr;
     long long l_pac = 0;
@@ -299,7 +275,7 @@ int finish_pending_sw(bpsw_ctx* c) {
 int bpsw_swalign2_batch_device(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_sw_jobs_t* j, void* d_out, void* hip_stream) {
   if (!c || !j || !d_out) return fail(BPSW_ERR_ARG, "swalign_device: null argument");
   SwScoring sc;
-  int rc = make_scoring(opt, j->xtra, &sc);
+  int rc = make_scoring("swalign", opt, j->xtra, 0, &sc);
   if (rc != BPSW_OK) return rc;
   if (j->n == 0) return BPSW_OK;
   if (j->n < 0 || !j->q_len || !j->t_len || !j->q_off || !j->t_off || !j->q_rev || !j->q_pool)
@@ -414,30 +390,21 @@ int bpsw_ref_fetch(bpsw_ctx_t* c, int32_t n, const int64_t* beg, const int64_t* 
   long long l_pac = 0;
   const RefHold ref_hold = ref_snapshot(c, &d_pac, &l_pac);
   if (l_pac <= 0) return fail(BPSW_ERR_ARG, "ref_fetch: no reference is loaded (bpsw_ref_load)");
-  const size_t o_beg = 0, o_end = align16(8 * (size_t)n), o_off = align16(o_end + 8 * (size_t)n);
-  const size_t in_total = align16(o_off + 8 * (size_t)n);
-  const size_t o_len = 0, o_err = align16(8 * (size_t)n), o_pool = align16(o_err + 16);
-  const size_t out_total = align16(o_pool + out_pool_bytes);
-  HIP_TRY(c->h_stage_in.reserve(in_total));
-  HIP_TRY(c->d_sw_in.reserve(in_total));
-  HIP_TRY(c->h_stage_out.reserve(out_total));
-  HIP_TRY(c->d_sw_out.reserve(out_total));
-  uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
-  memcpy(h + o_beg, beg, 8 * (size_t)n); memcpy(h + o_end, end, 8 * (size_t)n); memcpy(h + o_off, out_off, 8 * (size_t)n);
-  uint8_t* d = (uint8_t*)c->d_sw_in.ptr;
-  uint8_t* dout = (uint8_t*)c->d_sw_out.ptr;
-  HIP_TRY(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(dout + o_err, 0, 16, c->stream));
-  launch_ref_fetch(d_pac, l_pac, n, (const long long*)(d + o_beg), (const long long*)(d + o_end),
-                   dout + o_pool, out_pool_bytes, (const long long*)(d + o_off), (long long*)(dout + o_len),
-                   (int*)(dout + o_err), c->stream);
+  StageIn in;
+  const int i_beg = in.add(beg, 8 * (size_t)n), i_end = in.add(end, 8 * (size_t)n), i_off = in.add(out_off, 8 * (size_t)n);
+  StageOut out;
+  const int r_len = out.add(8 * (size_t)n), r_err = out.add(16), r_pool = out.add(out_pool_bytes);
+  HIP_TRY(out.reserve(c->h_stage_out, c->d_sw_out));
+  HIP_TRY(in.stage(c->h_stage_in, c->d_sw_in, c->stream));
+  HIP_TRY(hipMemsetAsync(out.dev<int>(r_err), 0, 16, c->stream));
+  launch_ref_fetch(d_pac, l_pac, n, in.dev<long long>(i_beg), in.dev<long long>(i_end), out.dev<uint8_t>(r_pool), out_pool_bytes,
+                   in.dev<long long>(i_off), out.dev<long long>(r_len), out.dev<int>(r_err), c->stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, out_total, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(out.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const uint8_t* ho = (const uint8_t*)c->h_stage_out.ptr;
-  memcpy(out_len, ho + o_len, 8 * (size_t)n);
-  if (*(const int*)(ho + o_err)) return fail(BPSW_ERR_CAPACITY, "ref_fetch: a window does not fit in out_pool at its out_off");
-  if (out_pool_bytes) memcpy(out_pool, ho + o_pool, out_pool_bytes);
+  memcpy(out_len, out.host<long long>(r_len), 8 * (size_t)n);
+  if (*out.host<int>(r_err)) return fail(BPSW_ERR_CAPACITY, "ref_fetch: a window does not fit in out_pool at its out_off");
+  if (out_pool_bytes) memcpy(out_pool, out.host<uint8_t>(r_pool), out_pool_bytes);
   return BPSW_OK;
 }
 
@@ -503,39 +470,26 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   if (nseeds > out_cap || (nseeds > 0 && !out_regs)) return fail(BPSW_ERR_CAPACITY, "chain2aln: out_regs must hold one region per seed");
 
   // ---- one staging block, one H2D copy ----
-  const size_t o_rlen = 0, o_roff = align16(4 * (size_t)n), o_ccnt = align16(o_roff + 8 * (size_t)n);
-  const size_t o_cbase = align16(o_ccnt + 4 * (size_t)n), o_rbase = align16(o_cbase + 4 * (size_t)n);
-  const size_t o_scnt = align16(o_rbase + 8 * (size_t)n), o_sbase = align16(o_scnt + 4 * (size_t)nchains);
-  const size_t o_srb = align16(o_sbase + 8 * (size_t)nchains), o_sqb = align16(o_srb + 8 * (size_t)nseeds);
-  const size_t o_sln = align16(o_sqb + 4 * (size_t)nseeds), o_pool = align16(o_sln + 4 * (size_t)nseeds);
-  const size_t total = align16(o_pool + b->read_pool_bytes);
-  const size_t o_cnt = 0, o_regs = align16(4 * (size_t)n);
-  const size_t out_bytes = o_regs + sizeof(bpsw_alnreg_t) * (size_t)(nseeds > 0 ? nseeds : 1);
+  StageIn in;
+  const int i_rlen = in.add(b->read_len, 4 * (size_t)n), i_roff = in.add(b->read_off, 8 * (size_t)n);
+  const int i_ccnt = in.add(b->chain_cnt, 4 * (size_t)n), i_cbase = in.add(chain_base.data(), 4 * (size_t)n);
+  const int i_rbase = in.add(reg_base.data(), 8 * (size_t)n);
+  const int i_scnt = in.add(b->seed_cnt, 4 * (size_t)nchains), i_sbase = in.add(seed_base.data(), 8 * (size_t)nchains);
+  const int i_srb = in.add(b->seed_rbeg, 8 * (size_t)nseeds), i_sqb = in.add(b->seed_qbeg, 4 * (size_t)nseeds);
+  const int i_sln = in.add(b->seed_len, 4 * (size_t)nseeds), i_pool = in.add(b->read_pool, b->read_pool_bytes);
+  StageOut out;
+  const int r_cnt = out.add(4 * (size_t)n), r_regs = out.add(sizeof(bpsw_alnreg_t) * (size_t)(nseeds > 0 ? nseeds : 1));
   const int srt_per_wave = (max_seeds + 15) & ~15;
-  HIP_TRY(c->h_stage_in.reserve(total));
-  HIP_TRY(c->d_sw_in.reserve(total));
-  HIP_TRY(c->h_stage_out.reserve(out_bytes));
-  HIP_TRY(c->d_sw_out.reserve(out_bytes));
+  HIP_TRY(out.reserve(c->h_stage_out, c->d_sw_out));
   HIP_TRY(c->d_sw_scratch.reserve(4 * (size_t)srt_per_wave * (size_t)chain2aln_resident_waves(c->num_cu)));
-  uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
-  memcpy(h + o_rlen, b->read_len, 4 * (size_t)n); memcpy(h + o_roff, b->read_off, 8 * (size_t)n);
-  memcpy(h + o_ccnt, b->chain_cnt, 4 * (size_t)n); memcpy(h + o_cbase, chain_base.data(), 4 * (size_t)n);
-  memcpy(h + o_rbase, reg_base.data(), 8 * (size_t)n);
-  if (nchains) { memcpy(h + o_scnt, b->seed_cnt, 4 * (size_t)nchains); memcpy(h + o_sbase, seed_base.data(), 8 * (size_t)nchains); }
-  if (nseeds) {
-    memcpy(h + o_srb, b->seed_rbeg, 8 * (size_t)nseeds); memcpy(h + o_sqb, b->seed_qbeg, 4 * (size_t)nseeds);
-    memcpy(h + o_sln, b->seed_len, 4 * (size_t)nseeds);
-  }
-  memcpy(h + o_pool, b->read_pool, b->read_pool_bytes);
-  uint8_t* d = (uint8_t*)c->d_sw_in.ptr;
-  uint8_t* dout = (uint8_t*)c->d_sw_out.ptr;
+  HIP_TRY(in.pack(c->h_stage_in, c->d_sw_in));
   ChainBatchDev B;
   B.n_reads = n;
-  B.read_len = (const int32_t*)(d + o_rlen); B.read_off = (const long long*)(d + o_roff); B.read_pool = d + o_pool;
-  B.chain_cnt = (const int32_t*)(d + o_ccnt); B.chain_base = (const int32_t*)(d + o_cbase);
-  B.seed_cnt = (const int32_t*)(d + o_scnt); B.seed_base = (const long long*)(d + o_sbase);
-  B.seed_rbeg = (const long long*)(d + o_srb); B.seed_qbeg = (const int32_t*)(d + o_sqb); B.seed_len = (const int32_t*)(d + o_sln);
-  B.reg_base = (const long long*)(d + o_rbase);
+  B.read_len = in.dev<int32_t>(i_rlen); B.read_off = in.dev<long long>(i_roff); B.read_pool = in.dev<uint8_t>(i_pool);
+  B.chain_cnt = in.dev<int32_t>(i_ccnt); B.chain_base = in.dev<int32_t>(i_cbase);
+  B.seed_cnt = in.dev<int32_t>(i_scnt); B.seed_base = in.dev<long long>(i_sbase);
+  B.seed_rbeg = in.dev<long long>(i_srb); B.seed_qbeg = in.dev<int32_t>(i_sqb); B.seed_len = in.dev<int32_t>(i_sln);
+  B.reg_base = in.dev<long long>(i_rbase);
   B.pac = d_pac; B.l_pac = l_pac;
   ChainParams P;
   P.mat = pack_mat(opt->mat);
@@ -546,12 +500,12 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   apply_shortcuts(c->shortcut_mask, opt->mat, &P.exact_a, &P.certify, &P.tail_bound);
 
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(in.send(c->stream));
   HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-  HIP_TRY(launch_chain2aln_kernel(B, P, (bpsw_alnreg_t*)(dout + o_regs), (int32_t*)(dout + o_cnt), (int32_t*)c->d_sw_scratch.ptr,
+  HIP_TRY(launch_chain2aln_kernel(B, P, out.dev<bpsw_alnreg_t>(r_regs), out.dev<int32_t>(r_cnt), (int32_t*)c->d_sw_scratch.ptr,
                                   srt_per_wave, c->num_cu, (int*)((char*)c->d_pre.ptr + 384), c->stream));  // its own queue head: +128 belongs to ext_kernel, which expects it zero
   HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(out.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   float ms = 0;
   (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
@@ -560,9 +514,8 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   c->stats.ext_calls++; c->stats.ext_tasks += (uint64_t)nseeds;
 
   // ---- compact (and optionally memSortAndDedup, as bwaMemWorker1Batched does right after, BWAMemWorker1Batched.scala:128-133) ----
-  const uint8_t* ho = (const uint8_t*)c->h_stage_out.ptr;
-  const int32_t* cnt = (const int32_t*)(ho + o_cnt);
-  const bpsw_alnreg_t* regs = (const bpsw_alnreg_t*)(ho + o_regs);
+  const int32_t* cnt = out.host<int32_t>(r_cnt);
+  const bpsw_alnreg_t* regs = out.host<bpsw_alnreg_t>(r_regs);
   int64_t at = 0;
   std::vector<bpsw_alnreg_t> v;
   for (int r = 0; r < n; ++r) {
@@ -584,7 +537,7 @@ int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jo
                       int32_t* out_ncigar, uint32_t* out_cigar) {
   if (!c || !j || !out_score || !out_ncigar || !out_cigar) return fail(BPSW_ERR_ARG, "global: null argument");
   SwScoring sc;
-  int rc = make_scoring(opt, 0, &sc);
+  int rc = make_scoring("swalign", opt, 0, 0, &sc);
   if (rc != BPSW_OK) return rc;
   const int n = j->n;
   if (n == 0) return BPSW_OK;
@@ -609,42 +562,32 @@ int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jo
   }
   ContextEntry entry(c);
   if (entry.rc != BPSW_OK) return entry.rc;
-  const size_t o_qlen = 0, o_tlen = align16(4 * (size_t)n), o_w = align16(o_tlen + 4 * (size_t)n);
-  const size_t o_qoff = align16(o_w + 4 * (size_t)n), o_toff = align16(o_qoff + 8 * (size_t)n);
-  const size_t o_qpool = align16(o_toff + 8 * (size_t)n), o_tpool = align16(o_qpool + j->q_pool_bytes);
-  const size_t total = align16(o_tpool + j->t_pool_bytes);
-  const size_t o_score = 0, o_nc = align16(4 * (size_t)n), o_cig = align16(o_nc + 4 * (size_t)n);
-  const size_t out_bytes = o_cig + 4 * (size_t)n * (size_t)j->max_cigar;
+  StageIn in;
+  const int i_qlen = in.add(j->q_len, 4 * (size_t)n), i_tlen = in.add(j->t_len, 4 * (size_t)n), i_w = in.add(j->w, 4 * (size_t)n);
+  const int i_qoff = in.add(j->q_off, 8 * (size_t)n), i_toff = in.add(j->t_off, 8 * (size_t)n);
+  const int i_qpool = in.add(j->q_pool, j->q_pool_bytes), i_tpool = in.add(j->t_pool, j->t_pool_bytes);
+  StageOut out;
+  const int r_score = out.add(4 * (size_t)n), r_nc = out.add(4 * (size_t)n), r_cig = out.add(4 * (size_t)n * (size_t)j->max_cigar);
   const size_t z_per_wave = (mz + 255) & ~(size_t)255;
   const int qcap = (mq + 31) & ~31;
-  HIP_TRY(c->h_stage_in.reserve(total));
-  HIP_TRY(c->d_sw_in.reserve(total));
-  HIP_TRY(c->h_stage_out.reserve(out_bytes));
-  HIP_TRY(c->d_sw_out.reserve(out_bytes));
+  HIP_TRY(out.reserve(c->h_stage_out, c->d_sw_out));
   HIP_TRY(c->d_gl_z.reserve(z_per_wave * (size_t)launch_waves(global_resident_waves(c->num_cu, qcap), n)));
-  uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
-  memcpy(h + o_qlen, j->q_len, 4 * (size_t)n); memcpy(h + o_tlen, j->t_len, 4 * (size_t)n); memcpy(h + o_w, j->w, 4 * (size_t)n);
-  memcpy(h + o_qoff, j->q_off, 8 * (size_t)n); memcpy(h + o_toff, j->t_off, 8 * (size_t)n);
-  memcpy(h + o_qpool, j->q_pool, j->q_pool_bytes); memcpy(h + o_tpool, j->t_pool, j->t_pool_bytes);
-  uint8_t* d = (uint8_t*)c->d_sw_in.ptr;
+  HIP_TRY(in.stage(c->h_stage_in, c->d_sw_in, c->stream));
   GlobalJobsDev dev;
   dev.n = n; dev.max_cigar = j->max_cigar;
-  dev.q_len = (const int32_t*)(d + o_qlen); dev.t_len = (const int32_t*)(d + o_tlen); dev.w = (const int32_t*)(d + o_w);
-  dev.q_off = (const int64_t*)(d + o_qoff); dev.t_off = (const int64_t*)(d + o_toff);
-  dev.q_pool = d + o_qpool; dev.t_pool = d + o_tpool;
-  uint8_t* dout = (uint8_t*)c->d_sw_out.ptr;
-  HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_global_kernel(dev, sc, mq, z_per_wave, (int32_t*)(dout + o_score), (int32_t*)(dout + o_nc),
-                               (uint32_t*)(dout + o_cig), (uint8_t*)c->d_gl_z.ptr, c->num_cu, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  dev.q_len = in.dev<int32_t>(i_qlen); dev.t_len = in.dev<int32_t>(i_tlen); dev.w = in.dev<int32_t>(i_w);
+  dev.q_off = in.dev<int64_t>(i_qoff); dev.t_off = in.dev<int64_t>(i_toff);
+  dev.q_pool = in.dev<uint8_t>(i_qpool); dev.t_pool = in.dev<uint8_t>(i_tpool);
+  HIP_TRY(launch_global_kernel(dev, sc, mq, z_per_wave, out.dev<int32_t>(r_score), out.dev<int32_t>(r_nc), out.dev<uint32_t>(r_cig),
+                               (uint8_t*)c->d_gl_z.ptr, c->num_cu, c->stream));
+  HIP_TRY(out.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const uint8_t* ho = (const uint8_t*)c->h_stage_out.ptr;
-  memcpy(out_score, ho + o_score, 4 * (size_t)n);
-  memcpy(out_ncigar, ho + o_nc, 4 * (size_t)n);
+  memcpy(out_score, out.host<int32_t>(r_score), 4 * (size_t)n);
+  memcpy(out_ncigar, out.host<int32_t>(r_nc), 4 * (size_t)n);
   // a job's operations, and nothing else: the device block is not cleared between calls, so the words behind a job's count -- and the
   // whole row of a job that did not fit -- hold what earlier launches left there, and stay out of the caller's array
-  const int32_t* nc = (const int32_t*)(ho + o_nc);
-  const uint32_t* hc = (const uint32_t*)(ho + o_cig);
+  const int32_t* nc = out.host<int32_t>(r_nc);
+  const uint32_t* hc = out.host<uint32_t>(r_cig);
   for (int i = 0; i < n; ++i)
     if (nc[i] > 0 && nc[i] <= j->max_cigar) memcpy(out_cigar + (size_t)i * (size_t)j->max_cigar, hc + (size_t)i * (size_t)j->max_cigar, 4 * (size_t)nc[i]);
   return BPSW_OK;

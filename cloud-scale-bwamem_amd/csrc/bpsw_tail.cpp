@@ -15,7 +15,6 @@
 #endif
 
 #include <algorithm>
-#include <chrono>
 #include <string>
 #include <utility>
 #include <vector>
@@ -25,18 +24,6 @@
 using namespace bpsw;
 
 namespace {
-
-int hip_fail(hipError_t e, const char* what) { return fail(BPSW_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-inline double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // the kernel stages at most this many CIGAR operations (CIG_LDS in bpsw_global_core.h)
 constexpr int KERNEL_CIG_CAP = 512;
@@ -65,17 +52,6 @@ int snapshot_bns(const bpsw_ctx* c, BnsView* v) {
   v->d_off = (const long long*)r.ann.ptr;
   v->d_len = (const int32_t*)((const char*)r.ann.ptr + 8 * r.ann_off.size());
   v->off = r.ann_off; v->len = r.ann_len; v->name = r.ann_name;
-  return BPSW_OK;
-}
-
-int make_sw_scoring(const bpsw_opt_t* opt, SwScoring* sc) {
-  if (!opt) return fail(BPSW_ERR_ARG, "tail: null options");
-  if (opt->a < 1 || opt->o_del < 0 || opt->e_del < 1 || opt->o_ins < 0 || opt->e_ins < 1)
-    return fail(BPSW_ERR_ARG, "tail: scoring must have a >= 1, non-negative gap opens and gap extensions >= 1");
-  sc->mat = pack_mat(opt->mat);
-  sc->a = opt->a; sc->b = opt->b;
-  sc->o_del = opt->o_del; sc->e_del = opt->e_del; sc->o_ins = opt->o_ins; sc->e_ins = opt->e_ins;
-  sc->xtra = 0;
   return BPSW_OK;
 }
 
@@ -112,50 +88,42 @@ int launch_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int fla
   const int qcap = (mq + 31) & ~31, rcap = (mr + 31) & ~31;
   const int md_cap = 2 * qcap + rcap + 32;  // every mismatch costs >= 2 bytes, every deleted base 1, plus the counts
   if (reg2aln_lds_per_wave(qcap, rcap, md_cap) * 4 > 64 * 1024) return fail(BPSW_ERR_LIMIT, "reg2aln: sequences too long for the LDS staging");
-  const size_t o_len = 0, o_off = align16(4 * (size_t)n), o_regs = align16(o_off + 8 * (size_t)n);
-  const size_t o_pool = align16(o_regs + sizeof(bpsw_alnreg_t) * (size_t)n);
   // ship only the bytes the jobs touch: reads are contiguous per job in the caller's pool, so copy the covering span
   long long lo = (long long)read_pool_bytes, hi = 0;
   for (int j = 0; j < n; ++j) { lo = std::min<long long>(lo, read_off[j]); hi = std::max<long long>(hi, read_off[j] + read_len[j]); }
   const size_t span = (size_t)(hi - lo);
-  const size_t total = align16(o_pool + span);
-  const size_t r_out = 0, r_cig = align16(sizeof(Reg2AlnOut) * (size_t)n), r_md = align16(r_cig + 4 * (size_t)n * (size_t)max_cigar);
-  const size_t out_bytes = align16(r_md + (size_t)n * (size_t)max_md);
+  StageIn in;
+  const int i_len = in.add(read_len, 4 * (size_t)n), i_off = in.add(nullptr, 8 * (size_t)n);  // (read_off is rebased below)
+  const int i_regs = in.add(regs, sizeof(bpsw_alnreg_t) * (size_t)n), i_pool = in.add(read_pool + lo, span);
+  StageOut res;
+  const int r_out = res.add(sizeof(Reg2AlnOut) * (size_t)n), r_cig = res.add(4 * (size_t)n * (size_t)max_cigar);
+  const int r_md = res.add((size_t)n * (size_t)max_md);
   const size_t z_per_wave = (mz + 255) & ~(size_t)255;
-  HIP_TRY(c->h_stage_in.reserve(total));
-  HIP_TRY(c->d_sw_in.reserve(total));
-  HIP_TRY(c->h_stage_out.reserve(out_bytes));
-  HIP_TRY(c->d_sw_out.reserve(out_bytes));
+  HIP_TRY(res.reserve(c->h_stage_out, c->d_sw_out));
   HIP_TRY(c->d_gl_z.reserve(z_per_wave * (size_t)launch_waves(reg2aln_resident_waves(c->num_cu, qcap, rcap, md_cap), n)));
-  uint8_t* h = (uint8_t*)c->h_stage_in.ptr;
-  memcpy(h + o_len, read_len, 4 * (size_t)n);
-  long long* ho = (long long*)(h + o_off);
+  HIP_TRY(in.pack(c->h_stage_in, c->d_sw_in));
+  long long* ho = in.host<long long>(i_off);
   for (int j = 0; j < n; ++j) ho[j] = read_off[j] - lo;
-  memcpy(h + o_regs, regs, sizeof(bpsw_alnreg_t) * (size_t)n);
-  memcpy(h + o_pool, read_pool + lo, span);
-  uint8_t* d = (uint8_t*)c->d_sw_in.ptr;
   Reg2AlnDev J;
   J.n = n; J.max_cigar = max_cigar; J.max_md = max_md; J.flavour = flavour; J.opt_w = opt->w; J.a = opt->a;
-  J.read_len = (const int32_t*)(d + o_len); J.read_off = (const long long*)(d + o_off); J.read_pool = d + o_pool;
-  J.regs = (const bpsw_alnreg_t*)(d + o_regs);
+  J.read_len = in.dev<int32_t>(i_len); J.read_off = in.dev<long long>(i_off); J.read_pool = in.dev<uint8_t>(i_pool);
+  J.regs = in.dev<bpsw_alnreg_t>(i_regs);
   J.pac = bns.d_pac; J.l_pac = bns.l_pac; J.n_seqs = bns.n_seqs; J.ann_off = bns.d_off; J.ann_len = bns.d_len;
-  uint8_t* dout = (uint8_t*)c->d_sw_out.ptr;
-  HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(in.send(c->stream));
   HIP_TRY(hipEventRecord(c->ev[6], c->stream));
-  HIP_TRY(launch_reg2aln_kernel(J, sc, qcap, rcap, md_cap, z_per_wave, (Reg2AlnOut*)(dout + r_out), (uint32_t*)(dout + r_cig),
-                                dout + r_md, (uint8_t*)c->d_gl_z.ptr, c->num_cu, c->stream));
+  HIP_TRY(launch_reg2aln_kernel(J, sc, qcap, rcap, md_cap, z_per_wave, res.dev<Reg2AlnOut>(r_out), res.dev<uint32_t>(r_cig),
+                                res.dev<uint8_t>(r_md), (uint8_t*)c->d_gl_z.ptr, c->num_cu, c->stream));
   HIP_TRY(hipEventRecord(c->ev[7], c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(res.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ev[6], c->ev[7]);
   c->last_tail_ms += ms;  // a call may launch twice (jobs whose CIGAR / MD outgrew the first, small, room)
   c->last_tail_jobs += n;  // distinct jobs = this minus last_tail_resubmitted
   c->have_tail_ev = true;
-  const uint8_t* r = (const uint8_t*)c->h_stage_out.ptr;
-  memcpy(out, r + r_out, sizeof(Reg2AlnOut) * (size_t)n);
-  memcpy(out_cigar, r + r_cig, 4 * (size_t)n * (size_t)max_cigar);
-  memcpy(out_md, r + r_md, (size_t)n * (size_t)max_md);
+  memcpy(out, res.host<Reg2AlnOut>(r_out), sizeof(Reg2AlnOut) * (size_t)n);
+  memcpy(out_cigar, res.host<uint32_t>(r_cig), 4 * (size_t)n * (size_t)max_cigar);
+  memcpy(out_md, res.host<uint8_t>(r_md), (size_t)n * (size_t)max_md);
   return BPSW_OK;
 }
 
@@ -637,7 +605,7 @@ int bpsw_reg2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt
                        uint32_t* out_cigar, uint8_t* out_md) {
   if (!c || !topt || !j || !out || !out_cigar || !out_md) return fail(BPSW_ERR_ARG, "reg2aln: null argument");
   SwScoring sc;
-  int rc = make_sw_scoring(opt, &sc);
+  int rc = make_scoring("tail", opt, 0, 1, &sc);
   if (rc != BPSW_OK) return rc;
   const int n = j->n;
   if (n == 0) return BPSW_OK;
@@ -684,7 +652,7 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
                       size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
   if (!c || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "sam_pe: null argument");
   SwScoring sc;
-  int rc = make_sw_scoring(opt, &sc);
+  int rc = make_scoring("tail", opt, 0, 1, &sc);
   if (rc != BPSW_OK) return rc;
   const int G = g->group_size;
   if (G < 0) return fail(BPSW_ERR_ARG, "sam_pe: negative group size");
@@ -708,7 +676,7 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
 
   // ---- plan -----------------------------------------------------------------------------------------------------------
   c->last_tail_ms = 0.f; c->last_tail_jobs = 0; c->last_tail_resubmitted = 0;
-  const double t_plan = now_ms();
+  const double t_plan = wall_ms();
   struct PlanScratch {
     std::vector<std::vector<bpsw_alnreg_t> > regs;
     std::vector<PairPlan> plan;
@@ -790,7 +758,7 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
   static thread_local JobResults results;  // (the scratch of a call is kept per calling thread: no allocation in the steady state)
   JobResults& R = results;
   std::vector<JobResult>& res = R.r;
-  const double t_dev = now_ms();
+  const double t_dev = wall_ms();
   rc = run_jobs(c, sc, opt, t.flavour, bns, job_len, job_off, g->read_pool, g->read_pool_bytes, job_reg, &R);
   if (rc != BPSW_OK) return rc;
   for (size_t j = 0; j < res.size(); ++j)
@@ -799,7 +767,7 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
                                                                    : "sam_pe: an alignment has more CIGAR operations than the kernel stages");
 
   // ---- emit ---------------------------------------------------------------------------------------------------------------
-  const double t_emit = now_ms();
+  const double t_emit = wall_ms();
   Text text(out_text, text_cap);
   for (int k = 0; k < G; ++k) {
     const PairPlan& P = plan[(size_t)k];
@@ -862,7 +830,7 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
     size_t w = 0;
     for (int r = 0; r < 2 * G; ++r) { if (!regs[(size_t)r].empty()) memcpy(out_regs + w, regs[(size_t)r].data(), sizeof(bpsw_alnreg_t) * regs[(size_t)r].size()); w += regs[(size_t)r].size(); }
   }
-  c->tail_host_ms[0] = t_dev - t_plan; c->tail_host_ms[1] = t_emit - t_dev; c->tail_host_ms[2] = now_ms() - t_emit;
+  c->tail_host_ms[0] = t_dev - t_plan; c->tail_host_ms[1] = t_emit - t_dev; c->tail_host_ms[2] = wall_ms() - t_emit;
   if (out_needed) *out_needed = text.size();
   if (!out_text || text.size() > text_cap) return fail(BPSW_ERR_CAPACITY, "sam_pe: text buffer too small (see *out_needed)");
   return BPSW_OK;
