@@ -381,6 +381,31 @@ np.savez_compressed(os.path.join(HERE, "ksw_global2_edges.npz"), q_off=qo, q_poo
                     score=np.array(scores, np.int32), cig_off=co, cig_pool=np.concatenate(cigs).astype(np.uint32),
                     note="ksw_global2(native/ksw.c:501-584) on tests/global_cases.py fixture_subset(); cigar = len<<4|op, op 0=M 1=I 2=D")
 
+# ---- mem_chain2aln at the limits the round-loop kernel names (tests/chain_cases.py: fixture_batches): more than 64 regions in a read,
+# chains of up to 200 seeds with tied lengths, checkOverlapping's boundaries, second band tries at w = 2 .. 127, 255-base flanks at
+# w = 254, windows cropped at 0 / l_pac / 2 l_pac, N, and heavy reads between light ones -- under the default options and one
+# other set, the numbers of each set stored with it.  Batch i is b<i>_*; its regions under option set k are b<i>_o<k>_cnt / _regs.
+import chain_cases  # noqa: E402
+
+pac_e = chain_cases.reference()[0]
+edge_kw = dict(l_pac=chain_cases.L_PAC, pac=pac_e, n_batches=len(chain_cases.fixture_batches()), n_options=len(chain_cases.FIXTURE_OPTIONS))
+for k, oi in enumerate(chain_cases.FIXTURE_OPTIONS):
+    o = chain_cases.OPTIONS[oi]
+    edge_kw[f"opt{k}_name"] = o.name
+    edge_kw[f"opt{k}_ints"] = np.array(o[1:10], np.int32)      # a b o_del e_del o_ins e_ins pen_clip5 pen_clip3 zdrop
+    edge_kw[f"opt{k}_mat"] = np.asarray(o.mat, np.int8)
+for i, (fam, w, cb_e) in enumerate(chain_cases.fixture_batches()):
+    edge_kw[f"b{i}_family"] = fam
+    edge_kw[f"b{i}_w"] = w
+    for f in ("read_len", "read_off", "read_pool", "chain_cnt", "seed_cnt", "seed_rbeg", "seed_qbeg", "seed_len"):
+        edge_kw[f"b{i}_{f}"] = getattr(cb_e, f)
+    for k, oi in enumerate(chain_cases.FIXTURE_OPTIONS):
+        c_e, r_e = ref.chain2aln_batch(chain_cases.apply(po.Opt(), chain_cases.OPTIONS[oi], w), pac_e, cb_e)
+        edge_kw[f"b{i}_o{k}_cnt"] = c_e
+        edge_kw[f"b{i}_o{k}_regs"] = r_e
+np.savez_compressed(os.path.join(HERE, "mem_chain2aln_edges.npz"), **edge_kw,
+                    note="mem_chain2aln(native/bwamem.c:552-700) per chain of every read on tests/chain_cases.py fixture_batches()")
+
 if CHECK:
     if _mismatch:
         print("golden fixtures differ from what this script generates now:", ", ".join(_mismatch))

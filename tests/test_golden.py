@@ -167,6 +167,23 @@ def test_chain2aln_vs_mem_chain2aln_golden(orc):
     assert n_ext > 300 and len(regs) < len(b.seed_len)       # extensions ran; contained seeds were skipped
 
 
+def test_chain2aln_vs_mem_chain2aln_edges_golden(orc):
+    """the families of tests/chain_cases.py as the fixture holds them (batches, option sets and mem_chain2aln's regions): the oracle in
+    the BWA z-drop parse against the reference C, where no reference build exists too"""
+    import chain_cases
+    z = np.load(os.path.join(G, "mem_chain2aln_edges.npz"))
+    regions = 0
+    for i in range(int(z["n_batches"])):
+        fam, w, b = chain_cases.fixture_batch(z, i)
+        for k in range(int(z["n_options"])):
+            opt = chain_cases.apply(orc.default_opt(), chain_cases.fixture_options(z, k), w)
+            cnt, regs, _, _ = orc.chain2aln_batch(opt, z["pac"], b, po.ZDROP_BWA)
+            assert np.array_equal(cnt, z[f"b{i}_o{k}_cnt"]), (fam, w, k)
+            region_fields_equal(regs, z[f"b{i}_o{k}_regs"])
+            regions += len(regs)
+    assert regions > 4000
+
+
 def _ref_task_sets():
     z = np.load(os.path.join(G, "ref_extension_tasks.npz"))
     fields = ("left_qlen", "left_rlen", "right_qlen", "right_rlen", "left_q_off", "left_r_off", "right_q_off", "right_r_off",
