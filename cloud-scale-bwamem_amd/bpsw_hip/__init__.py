@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "bpsw_mark_primary_se", "bpsw_approx_mapq_se", "bpsw_mem_pair", "bpsw_sort_dedup", "bpsw_pe_stat",
     "bpsw_fmi_load", "bpsw_fmi_unload", "bpsw_fmi_length", "bpsw_seed_opt_default", "bpsw_seed_batch", "bpsw_chain_seeds",
     "bpsw_worker1_batch", "bpsw_last_worker1_times", "bpsw_seed_set_resident_lanes",
+    "bpsw_chain_batch", "bpsw_chain_set_arena_budget", "bpsw_chain_last_split",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -115,6 +116,7 @@ class Chains(C.Structure):  # bpsw_chains_t
 
 
 C2A_SORT_DEDUP, C2A_DEDUP_SCALA = 1, 2
+W1_CHAIN_DEVICE = 4   # worker1_batch only: chain and filter the seeds on the device (BPSW_W1_CHAIN_DEVICE)
 
 
 class RescueGroup(C.Structure):  # bpsw_rescue_group_t
@@ -236,6 +238,10 @@ def _bind_seeding(lib):
                                 C.POINTER(C.c_int64)], C.c_int),
         "bpsw_last_worker1_times": ([C.c_void_p], None),
         "bpsw_seed_set_resident_lanes": ([C.c_int], None),
+        "bpsw_chain_batch": ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                              C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_chain_set_arena_budget": ([C.c_int64], None),
+        "bpsw_chain_last_split": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -568,6 +574,27 @@ class Context:
             _chk(self.lib, rc, "bpsw_seed_batch")
             return icnt[:n], iv[: it.value], scnt[:n], sv[: stt.value]
 
+    def chain_batch(self, sopt, w: int, l_pac: int, seed_cnt, seeds, filter: bool = True):
+        """bpsw_chain_batch: per read its seeds (seed_cnt[n], fmi.SEED_DTYPE in emission order) -> (chain_cnt[n], seeds per chain,
+        seeds in chain order), per read what chain_seeds gives, concatenated in read order"""
+        from . import fmi
+        seed_cnt = np.ascontiguousarray(seed_cnt, np.int32)
+        seeds = np.ascontiguousarray(seeds, fmi.SEED_DTYPE)
+        n = int(seed_cnt.shape[0])
+        assert int(seed_cnt.sum()) == seeds.shape[0]
+        chain_cnt = np.zeros(max(n, 1), np.int32)
+        ccap, scap = n + 64, 2 * n + 64
+        while True:
+            cnt, out = np.zeros(ccap, np.int32), np.zeros(scap, fmi.SEED_DTYPE)
+            ct, st = C.c_int64(0), C.c_int64(0)
+            rc = self.lib.bpsw_chain_batch(self.h, C.byref(sopt), w, l_pac, n, _ptr(seed_cnt), _ptr(seeds), 1 if filter else 0, _ptr(chain_cnt),
+                                           _ptr(cnt), ccap, _ptr(out), scap, C.byref(ct), C.byref(st))
+            if rc == -3 and (ct.value > ccap or st.value > scap):   # BPSW_ERR_CAPACITY: the totals say what is needed
+                ccap, scap = max(ccap, ct.value), max(scap, st.value)
+                continue
+            _chk(self.lib, rc, "bpsw_chain_batch")
+            return chain_cnt[:n], cnt[: ct.value], out[: st.value]
+
     def worker1_batch(self, opt: Opt, sopt, reads, zdrop_mode: int = ZDROP_SCALA, flags: int = 0):
         """reads (fmi.ReadBatch) -> (out_cnt[n], regions), the shape of chain2aln_batch"""
         st = reads.as_struct()
@@ -639,8 +666,15 @@ def chain_seeds(sopt, w: int, l_pac: int, seeds: np.ndarray, filter: bool = True
     return cnt[:nc].copy(), out[: int(cnt[:nc].sum())].copy()
 
 
+def chain_last_split():
+    """(reads chained by the kernel, reads chained on the calling thread, slices, arena bytes) of this thread's last chain stage"""
+    st = (C.c_int64 * 4)()
+    load_library().bpsw_chain_last_split(st)
+    return tuple(st)
+
+
 def last_worker1_times():
-    """(seeding call, host chaining, round loop call) in ms of this thread's last worker1_batch"""
+    """(seeding call, chaining on the host or the device, round loop call) in ms of this thread's last worker1_batch"""
     ms = (C.c_double * 3)()
     load_library().bpsw_last_worker1_times(ms)
     return tuple(ms)

@@ -462,6 +462,24 @@ struct SwStage {
 int sw_stage_begin(bpsw_ctx* c, int n, size_t q_pool_bytes, size_t t_pool_bytes, SwStage* st);
 int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st, int mq, int mt, bool pac_mode, const int32_t** results);
 
+// ---- chaining + chain filter of a batch on the device (bpsw_chain_dev.hip) -------------------------------------------------------
+// Read r's seeds are [seed_beg[r], seed_beg[r + 1]) of one array: on the device already (d_seeds, e.g. seed_sa_kernel's output), or
+// in host memory (h_seeds; d_seeds null: staged here).  drop_bridging: seeds with rbeg < l_pac < rbeg + len are passed over first
+// (native/bwamem.c:228).  The result is bpsw_chain_seeds' per read, concatenated in read order.
+struct ChainDevJob {
+  int n_reads;
+  const long long* seed_beg;  // n_reads + 1, host
+  const bpsw_seed_t* d_seeds;
+  const bpsw_seed_t* h_seeds;
+  int filter, drop_bridging;
+};
+struct ChainDevResult {
+  std::vector<int32_t> chain_cnt, chain_seed_cnt;
+  std::vector<bpsw_seed_t> seeds;
+};
+// Caller holds c->mu and has set the device (ContextEntry).  Uses d_seed[0], [1], [3] and d_chain; leaves d_seed[4] alone.
+int chain_dev_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, int w, int64_t l_pac, const ChainDevJob& J, ChainDevResult* R);
+
 }  // namespace bpsw
 
 struct bpsw_ctx {
@@ -477,6 +495,7 @@ struct bpsw_ctx {
   size_t staged_bytes = 0;    // what the last bpsw_extend_stage was asked for (0: nothing staged / already committed)
   bpsw::DeviceBuffer d_sift;  // the sift kernel's verdicts (bpsw_extend_sift.hip): [flag byte per task | two 16-byte records per task]
   bpsw::DeviceBuffer d_seed[5];  // the seeding calls (bpsw_seed.hip): reads, interval records, list arena, occurrence table, seeds
+  bpsw::DeviceBuffer d_chain;    // the chain kernel's workspace arena (bpsw_chain_dev.hip): one slice per read of the running slice of a batch
   // asynchronous device entries: a launch whose table scan has not been read back yet (resolved by finish_pending)
   struct PendingExt { bool active = false; const void* d_wire = nullptr; size_t wire_bytes = 0; int n_tasks = 0; void* d_out = nullptr;
                       hipStream_t s = nullptr; int qcap = 0, rcap = 0; } pend_ext;

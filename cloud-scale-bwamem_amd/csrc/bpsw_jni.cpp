@@ -1074,8 +1074,8 @@ JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_loadFmiJNI(
 //   @native def worker1FlatJNI(optInts: Array[Int], mat: Array[Byte], seedInts: Array[Int], seedFloats: Array[Double], flags: Int,
 //                              readLen: Array[Int], reads: Array[Byte]): Array[Long]
 // optInts and mat as for chainToAlnJNI; seedInts = (minSeedLen, maxOcc, splitWidth, maxChainGap, noExact), seedFloats =
-// (splitFactor, chainDropRatio, maskLevel, maskLevelRedun); flags = BPSW_C2A_SORT_DEDUP | BPSW_C2A_DEDUP_SCALA; reads back to back
-// (codes 0..4).  Result: n longs (regions per read), then 8 longs per region as chainToAlnJNI returns them.  Needs loadPacJNI and
+// (splitFactor, chainDropRatio, maskLevel, maskLevelRedun); flags = BPSW_C2A_SORT_DEDUP | BPSW_C2A_DEDUP_SCALA | BPSW_W1_CHAIN_DEVICE
+// (the last: chaining and chain filter on the device, bpsw_chain_dev.hip); reads back to back (codes 0..4).  Result: n longs (regions per read), then 8 longs per region as chainToAlnJNI returns them.  Needs loadPacJNI and
 // loadFmiJNI first; BPSW_ZDROP as for chainToAlnJNI.
 JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_worker1FlatJNI(
     JNIEnv* env, jobject, jintArray optInts, jbyteArray matArr, jintArray seedInts, jdoubleArray seedFloats, jint flags, jintArray readLenArr,

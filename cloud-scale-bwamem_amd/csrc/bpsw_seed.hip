@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <optional>
 
 #include "bpsw_internal.h"
 
@@ -304,9 +305,12 @@ int seed_resident_waves(int num_cu, long long n_reads) {
 
 thread_local double t_w1_ms[3] = {0., 0., 0.};
 
-// seeding of a validated batch: per read the intervals and the seeds (bridging ones dropped), concatenated in read order
+// seeding of a validated batch: per read the intervals and the seeds (bridging ones dropped), concatenated in read order.
+// With dev_read_occ (the caller then holds c->mu through a ContextEntry of its own): the seeds stay where seed_sa_kernel wrote them,
+// at the start of c->d_seed[4], bridging ones included -- read r's are [dev_read_occ[r], dev_read_occ[r + 1]) --, and scnt / seeds
+// come back empty.
 int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std::vector<int32_t>* icnt, std::vector<bpsw_smem_t>* intv,
-             std::vector<int32_t>* scnt, std::vector<bpsw_seed_t>* seeds) {
+             std::vector<int32_t>* scnt, std::vector<bpsw_seed_t>* seeds, std::vector<long long>* dev_read_occ = nullptr) {
   const int n = R.n_reads;
   int max_len = 1;
   for (int r = 0; r < n; ++r) {
@@ -317,8 +321,11 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
     if (ql > max_len) max_len = ql;
   }
   if (so.min_seed_len < 1 || so.max_occ < 0 || so.split_width < 0) return fail(BPSW_ERR_ARG, "seed: min_seed_len must be >= 1, max_occ and split_width >= 0");
-  ContextEntry entry(c);
-  if (entry.rc != BPSW_OK) return entry.rc;
+  std::optional<ContextEntry> entry;
+  if (!dev_read_occ) {
+    entry.emplace(c);
+    if (entry->rc != BPSW_OK) return entry->rc;
+  }
   DeviceFmi& fm = device_fmi(c->device);
   const RefHold hold(&fm.gate);
   FmiDev F;
@@ -419,6 +426,7 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   }
   scnt->assign((size_t)n, 0);
   seeds->clear();
+  if (dev_read_occ) *dev_read_occ = read_occ;
   if (n_occ == 0) return BPSW_OK;
   if (n_occ > 0x3fffffffll) return fail(BPSW_ERR_LIMIT, "seed: more than 2^30 seed occurrences in one batch");
   const size_t nk = occ_base.size();
@@ -427,13 +435,15 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   const int i_base = sin.add(occ_base.data(), 8 * (nk + 1)), i_x0 = sin.add(kept_x0.data(), 8 * nk), i_q = sin.add(kept_q.data(), 8 * nk);
   StageOut sout;
   const int r_seeds = sout.add(sizeof(bpsw_seed_t) * (size_t)n_occ);
-  HIP_TRY(sout.reserve(c->h_stage_out, d_sa_out));
+  if (dev_read_occ) HIP_TRY(d_sa_out.reserve(sout.total()));
+  else HIP_TRY(sout.reserve(c->h_stage_out, d_sa_out));
   HIP_TRY(sin.stage(c->h_stage_in, d_sa_in, c->stream));
   hipLaunchKernelGGL(seed_sa_kernel, dim3((unsigned)((n_occ + 255) / 256)), dim3(256), 0, c->stream, F, n_occ, (int)nk,
-                     sin.dev<long long>(i_base), sin.dev<long long>(i_x0), sin.dev<int2>(i_q), sout.dev<bpsw_seed_t>(r_seeds));
+                     sin.dev<long long>(i_base), sin.dev<long long>(i_x0), sin.dev<int2>(i_q), (bpsw_seed_t*)d_sa_out.ptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(sout.fetch(c->stream));
+  if (!dev_read_occ) HIP_TRY(sout.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (dev_read_occ) return BPSW_OK;
   const bpsw_seed_t* all = sout.host<bpsw_seed_t>(r_seeds);
   seeds->reserve((size_t)n_occ);
   for (int r = 0; r < n; ++r) {
@@ -555,30 +565,53 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
   if (bpsw_fmi_length(c) != 2 * l_pac) return fail(BPSW_ERR_ARG, "worker1: no index is loaded, or its seq_len is not 2 * l_pac (bpsw_fmi_load)");
   for (int r = 0; r < n; ++r)
     if (reads->read_len[r] < 1) return fail(BPSW_ERR_ARG, "worker1: empty read");
+  const bool chain_on_device = (flags & BPSW_W1_CHAIN_DEVICE) != 0;
+  flags &= ~BPSW_W1_CHAIN_DEVICE;
   const double t0 = wall_ms();
   std::vector<int32_t> ic, sc;
   std::vector<bpsw_smem_t> iv;
   std::vector<bpsw_seed_t> sv;
-  rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv);
-  if (rc != BPSW_OK) return rc;
-  const double t1 = wall_ms();
-  // chaining + filter per read (bpsw_chain.cpp), into the shape bpsw_chain2aln_batch takes
   std::vector<int32_t> chain_cnt((size_t)n), seed_cnt, qbeg, len, cc;
   std::vector<int64_t> rbeg;
   std::vector<bpsw_seed_t> cs;
-  size_t at = 0;
-  for (int r = 0; r < n; ++r) {
-    const int m = sc[(size_t)r];
-    cc.resize((size_t)m + 1);
-    cs.resize((size_t)m + 1);
-    const int nc = bpsw_chain_seeds(sopt, opt->w, l_pac, m, sv.data() + at, 1, cc.data(), m, cs.data());
-    if (nc < 0) return nc;
-    at += (size_t)m;
-    chain_cnt[(size_t)r] = nc;
-    size_t k = 0;
-    for (int ch = 0; ch < nc; ++ch) {
-      seed_cnt.push_back(cc[(size_t)ch]);
-      for (int i = 0; i < cc[(size_t)ch]; ++i, ++k) { rbeg.push_back(cs[k].rbeg); qbeg.push_back(cs[k].qbeg); len.push_back(cs[k].len); }
+  double t1;
+  if (chain_on_device) {
+    // the seeds stay in d_seed[4]; chaining + filter by chain_kernel (bpsw_chain_dev.hip), which drops the bridging ones itself
+    ContextEntry entry(c);
+    if (entry.rc != BPSW_OK) return entry.rc;
+    std::vector<long long> read_occ;
+    rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv, &read_occ);
+    if (rc != BPSW_OK) return rc;
+    t1 = wall_ms();
+    ChainDevJob J;
+    J.n_reads = n; J.seed_beg = read_occ.data(); J.d_seeds = (const bpsw_seed_t*)c->d_seed[4].ptr; J.h_seeds = nullptr;
+    J.filter = 1; J.drop_bridging = 1;
+    ChainDevResult R;
+    rc = chain_dev_run(c, *sopt, opt->w, l_pac, J, &R);
+    if (rc != BPSW_OK) return rc;
+    chain_cnt.swap(R.chain_cnt);
+    seed_cnt.swap(R.chain_seed_cnt);
+    rbeg.reserve(R.seeds.size()); qbeg.reserve(R.seeds.size()); len.reserve(R.seeds.size());
+    for (const bpsw_seed_t& s : R.seeds) { rbeg.push_back(s.rbeg); qbeg.push_back(s.qbeg); len.push_back(s.len); }
+  } else {
+    rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv);
+    if (rc != BPSW_OK) return rc;
+    t1 = wall_ms();
+    // chaining + filter per read (bpsw_chain.cpp), into the shape bpsw_chain2aln_batch takes
+    size_t at = 0;
+    for (int r = 0; r < n; ++r) {
+      const int m = sc[(size_t)r];
+      cc.resize((size_t)m + 1);
+      cs.resize((size_t)m + 1);
+      const int nc = bpsw_chain_seeds(sopt, opt->w, l_pac, m, sv.data() + at, 1, cc.data(), m, cs.data());
+      if (nc < 0) return nc;
+      at += (size_t)m;
+      chain_cnt[(size_t)r] = nc;
+      size_t k = 0;
+      for (int ch = 0; ch < nc; ++ch) {
+        seed_cnt.push_back(cc[(size_t)ch]);
+        for (int i = 0; i < cc[(size_t)ch]; ++i, ++k) { rbeg.push_back(cs[k].rbeg); qbeg.push_back(cs[k].qbeg); len.push_back(cs[k].len); }
+      }
     }
   }
   const double t2 = wall_ms();

@@ -309,6 +309,7 @@ int bpsw_ref_fetch(bpsw_ctx_t *ctx, int32_t n, const int64_t *beg, const int64_t
  */
 #define BPSW_C2A_SORT_DEDUP 1
 #define BPSW_C2A_DEDUP_SCALA 2
+#define BPSW_W1_CHAIN_DEVICE 4 /* bpsw_worker1_batch only: chain and filter the seeds on the device (bpsw_chain_batch's kernels) */
 typedef struct {
   int32_t n_reads;
   const int32_t *read_len;
@@ -385,16 +386,35 @@ int bpsw_seed_batch(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, const bpsw_rea
 int bpsw_chain_seeds(const bpsw_seed_opt_t *sopt, int32_t w, int64_t l_pac, int32_t n_seeds, const bpsw_seed_t *seeds, int32_t filter,
                      int32_t *chain_seed_cnt, int32_t chain_cap, bpsw_seed_t *out_seeds);
 
+/* The same for a batch, on the device (chain_kernel, one read per lane): read r's seeds are the next seed_cnt[r] of `seeds`.  Per
+ * read the result is exactly bpsw_chain_seeds', concatenated in read order: chain_cnt[read], chain_seed_cnt[chain], out_seeds.
+ * BPSW_ERR_CAPACITY with *chain_total / *seed_total set to what is needed when chain_cap or seed_cap is too small (the sum of
+ * seed_cnt always suffices for both); BPSW_ERR_ARG for a seed with len < 1 or qbeg < 0; n_reads == 0 and reads without seeds are
+ * fine.  Reads of more than BPSW_CHAIN_DEV_MAX_SEEDS seeds (environment, read once; default 128, 0 = no limit) are chained by
+ * bpsw_chain_seeds on the calling thread while the kernel runs. */
+int bpsw_chain_batch(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, int32_t w, int64_t l_pac, int32_t n_reads, const int32_t *seed_cnt,
+                     const bpsw_seed_t *seeds, int32_t filter, int32_t *chain_cnt, int32_t *chain_seed_cnt, int64_t chain_cap,
+                     bpsw_seed_t *out_seeds, int64_t seed_cap, int64_t *chain_total, int64_t *seed_total);
+/* Diagnostics.  The byte budget of the chain kernel's workspace arena, process-wide (0 = the default, 256 MB): a batch runs in
+ * slices of reads that fit it, a single read larger than the budget grows the arena to that read.  The tests lower it to reach
+ * both with small batches.  bpsw_chain_last_split: how the calling thread's most recent chain stage (bpsw_chain_batch, or
+ * bpsw_worker1_batch with BPSW_W1_CHAIN_DEVICE) was divided: reads chained by the kernel, reads chained on the calling thread,
+ * slices, bytes of arena asked for. */
+void bpsw_chain_set_arena_budget(int64_t bytes);
+void bpsw_chain_last_split(int64_t st[4]);
+
 /* worker1 from reads to regions: bpsw_seed_batch, bpsw_chain_seeds with the filter per read, then bpsw_chain2aln_batch as it is
  * (zdrop_mode, flags, out_* exactly as there; *out_total is set to the needed out_cap on BPSW_ERR_CAPACITY).  Needs the reference
- * (bpsw_ref_load) and an index with seq_len == 2 * l_pac on the context's device. */
+ * (bpsw_ref_load) and an index with seq_len == 2 * l_pac on the context's device.  With BPSW_W1_CHAIN_DEVICE in flags the seeds
+ * stay on the device and are chained and filtered there (as bpsw_chain_batch does; seeds bridging l_pac dropped by the kernel), and
+ * only the chains come back; the regions are the same. */
 int bpsw_worker1_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_reads_t *reads, int zdrop_mode,
                        int flags, int32_t *out_cnt, bpsw_alnreg_t *out_regs, int64_t out_cap, int64_t *out_total);
 /* Diagnostics: the number of lanes (reads in flight, a multiple of 64) seed_smem_kernel keeps resident, process-wide; 0 = the default,
  * 256 per compute unit (bpsw_device_cus).  Each resident lane owns four lists of (longest read of the batch + 1) intervals of 32
  * bytes in a per-context arena: 2.2 GB at 256 bases on 256 CUs.  The tests lower it to reach the grid-stride path with a small batch. */
 void bpsw_seed_set_resident_lanes(int lanes);
-/* wall time of the calling thread's most recent bpsw_worker1_batch (ms): seeding call, host chaining, round loop call */
+/* wall time of the calling thread's most recent bpsw_worker1_batch (ms): seeding call, chaining (host or device), round loop call */
 void bpsw_last_worker1_times(double ms[3]);
 
 /* ---- worker2's tail: everything after the rescue ------------------------------------------

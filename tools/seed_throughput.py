@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
-"""Throughput of worker1 from reads (bpsw_seed_batch, the host chaining, bpsw_worker1_batch) on a synthetic genome, next to the
-reference's mem_chain on the same reads from oracle/_ref/libbwaref.so on 16 threads where that library is built.
+"""Throughput of worker1 from reads (bpsw_seed_batch, the chain stage on the host and on the device, bpsw_worker1_batch) on a
+synthetic genome, next to the reference's mem_chain on the same reads from oracle/_ref/libbwaref.so on 16 threads where that
+library is built.
 
     python tools/seed_throughput.py [--genome-mb 50] [--reads 100000] [--read-len 150] [--sa-intv 32] [--reps 5] [--threads 16]
+                                    [--out profiles/seed_throughput.json]
+
+The chain stage both ways is slot 1 of bpsw_last_worker1_times without and with BPSW_W1_CHAIN_DEVICE on the same batch.  The
+long-read threshold (BPSW_CHAIN_DEV_MAX_SEEDS) is read once per process, and reads of a random genome have a handful of seeds,
+so its settings are measured in child processes on bpsw_chain_batch over the batch's own seeds plus --long-reads generated
+reads of L seeds each (tests/chain_lists.py), for every L of --long-seeds: at 0 the kernel chains them, at a threshold below L
+(2 048 for L above it) the calling thread does.
 
 The index is built here (numpy): a random genome has practically no repeated 27-mer, so the suffix array is one sort by the
 27-base prefix and a byte-wise comparison inside the few groups that tie.  After one warm-up call the median of --reps calls is
@@ -117,6 +125,48 @@ def reference_mem_chain(idx, l_pac, rb, threads):
     return n / (time.perf_counter() - t0)
 
 
+def chain_child(path, reps):
+    """bpsw_chain_batch over the seeds in `path` at this process's BPSW_CHAIN_DEV_MAX_SEEDS: median wall ms and the split"""
+    d = np.load(path)
+    ctx = bpsw_hip.Context(0)
+    so, w = bpsw_hip.default_seed_opt(), bpsw_hip.default_opt().w
+    ms = []
+    for k in range(reps + 1):
+        t0 = time.perf_counter()
+        ctx.chain_batch(so, w, int(d["l_pac"]), d["cnt"], d["seeds"], filter=True)
+        if k:
+            ms.append(1e3 * (time.perf_counter() - t0))
+    split = bpsw_hip.chain_last_split()
+    ctx.close()
+    print(json.dumps({"ms": round(float(np.median(ms)), 2), "reads_on_device": split[0], "reads_on_host": split[1], "slices": split[2],
+                      "arena_bytes": split[3]}))
+
+
+def threshold_runs(scnt, sv, l_pac, n_long, sizes, reps):
+    """per size L: the batch's seeds plus n_long generated reads of L seeds through bpsw_chain_batch in child processes, once with
+    BPSW_CHAIN_DEV_MAX_SEEDS=0 (the kernel chains them) and once with the threshold below L (the calling thread does; 2 048 where L
+    is above it)"""
+    import subprocess
+    import tempfile
+    import chain_lists as cl
+    rng = np.random.default_rng(7)
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for L in sizes:
+            longs = [cl.clustered(L, rng, l_pac=l_pac, spots=max(2, L // 8)) for _ in range(n_long)]
+            path = os.path.join(tmp, f"seeds_{L}.npz")
+            np.savez(path, cnt=np.concatenate([scnt, np.full(n_long, L, np.int32)]).astype(np.int32), seeds=np.concatenate([sv] + longs),
+                     l_pac=np.int64(l_pac))
+            res = {}
+            for limit in (0, min(2048, L - 1)):
+                env = dict(os.environ, BPSW_CHAIN_DEV_MAX_SEEDS=str(limit))
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--chain-child", path, "--reps", str(reps)], env=env,
+                                   capture_output=True, text=True, check=True)
+                res[f"max_seeds_{limit}"] = json.loads(p.stdout.strip().splitlines()[-1])
+            out[f"long_reads_of_{L}_seeds"] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=50.0)
@@ -125,7 +175,13 @@ def main():
     ap.add_argument("--sa-intv", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--long-reads", type=int, default=64)
+    ap.add_argument("--long-seeds", default="64,128,512,3000")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seed_throughput.json"))
+    ap.add_argument("--chain-child", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.chain_child:
+        return chain_child(a.chain_child, a.reps)
     rng = np.random.default_rng(20260101)
     l_pac = int(a.genome_mb * 1e6) | 1
     fwd = rng.integers(0, 4, l_pac).astype(np.uint8)
@@ -137,7 +193,7 @@ def main():
     ctx.ref_load(fu.pack_pac(fwd), l_pac)
     ctx.fmi_load(idx)
     opt, so = bpsw_hip.default_opt(), bpsw_hip.default_seed_opt()
-    seed_s, w1_s, stages = [], [], []
+    seed_s, w1_s, stages, w1d_s, stages_dev = [], [], [], [], []
     n_intv = n_seeds = n_regs = 0
     for k in range(a.reps + 1):
         t0 = time.perf_counter()
@@ -147,8 +203,16 @@ def main():
         t2 = time.perf_counter()
         if k:
             seed_s.append(t1 - t0); w1_s.append(t2 - t1); stages.append(bpsw_hip.last_worker1_times())
+        t2 = time.perf_counter()
+        dcnt, dregs = ctx.worker1_batch(opt, so, rb, flags=bpsw_hip.C2A_SORT_DEDUP | bpsw_hip.W1_CHAIN_DEVICE)
+        t3 = time.perf_counter()
+        if k:
+            w1d_s.append(t3 - t2); stages_dev.append(bpsw_hip.last_worker1_times())
+        split = bpsw_hip.chain_last_split()
+        assert np.array_equal(cnt, dcnt) and all(np.array_equal(regs[f], dregs[f]) for f in regs.dtype.names), "device chaining changed the regions"
         n_intv, n_seeds, n_regs = int(icnt.sum()), int(scnt.sum()), int(cnt.sum())
     st = np.median(np.array(stages), axis=0)
+    sd = np.median(np.array(stages_dev), axis=0)
     res = {
         "genome_bases": l_pac, "index_bytes": int(idx.bwt.nbytes + idx.sa.nbytes), "sa_intv": a.sa_intv, "index_build_s": round(t_build, 1),
         "tied_27mers": n_ties, "reads": a.reads, "read_len": a.read_len, "reps": a.reps,
@@ -161,11 +225,24 @@ def main():
         "round_loop_reads_per_s": round(a.reads / max(float(st[2]) / 1e3, 1e-9)),
     }
     res["bound_by"] = ("seeding_call", "host_chaining", "round_loop_call")[int(np.argmax(st))]
+    res["chain_stage_ms"] = {"host": round(float(st[1]), 2), "device": round(float(sd[1]), 2)}
+    res["device_chaining"] = {
+        "worker1_batch_reads_per_s": round(a.reads / float(np.median(w1d_s))),
+        "worker1_stage_ms": {"seeding_call": round(float(sd[0]), 2), "device_chaining": round(float(sd[1]), 2), "round_loop_call": round(float(sd[2]), 2)},
+        "reads_on_device": split[0], "reads_on_host": split[1], "slices": split[2], "arena_bytes": split[3],
+        "max_seeds_in_a_read": int(scnt.max()),
+    }
+    res["chain_batch_with_long_reads"] = dict(threshold_runs(scnt, sv, l_pac, a.long_reads, [int(x) for x in a.long_seeds.split(",")], a.reps),
+                                              long_reads=a.long_reads)
     if os.path.exists(pyoracle.REF_SO):
         res["reference_mem_chain_reads_per_s"] = round(reference_mem_chain(idx, l_pac, rb, a.threads))
         res["reference_threads"] = a.threads
     ctx.close()
     print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
