@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "bpsw_fmi_load", "bpsw_fmi_unload", "bpsw_fmi_length", "bpsw_seed_opt_default", "bpsw_seed_batch", "bpsw_chain_seeds",
     "bpsw_worker1_batch", "bpsw_last_worker1_times", "bpsw_seed_set_resident_lanes",
     "bpsw_chain_batch", "bpsw_chain_set_arena_budget", "bpsw_chain_last_split",
+    "bpsw_sam_se_batch", "bpsw_align_se_batch", "bpsw_last_sam_se_times",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -242,6 +243,12 @@ def _bind_seeding(lib):
                               C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
         "bpsw_chain_set_arena_budget": ([C.c_int64], None),
         "bpsw_chain_last_split": ([C.c_void_p], None),
+        # single-end reads to SAM (bpsw_sam_se.hip): as little part of the host-only sanitizer builds as the seeding entries
+        "bpsw_sam_se_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                               C.POINTER(C.c_size_t), C.c_void_p], C.c_int),
+        "bpsw_align_se_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                 C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)], C.c_int),
+        "bpsw_last_sam_se_times": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -930,6 +937,116 @@ def _ctx_last_tail_host_ms(self):
     return h[0], h[1], h[2]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# single-end reads to SAM (bpsw_sam_se.hip): bpsw_sam_se_batch, bpsw_align_se_batch
+SAM_TEXT_DEVICE = 1   # flags: the SAM text is written by sam_len_kernel / sam_write_kernel (BPSW_SAM_TEXT_DEVICE)
+
+
+class SeReads(C.Structure):  # bpsw_se_reads_t
+    _fields_ = [("n_reads", C.c_int32), ("id0", C.c_int64), ("id_step", C.c_int32), ("read_len", C.c_void_p), ("read_off", C.c_void_p),
+                ("read_pool", C.c_void_p), ("qual_pool", C.c_void_p), ("read_pool_bytes", C.c_size_t), ("name_off", C.c_void_p),
+                ("name_pool", C.c_void_p), ("reg_cnt", C.c_void_p), ("regs", C.c_void_p)]
+
+
+@dataclass
+class SeReadsSoA:
+    """Single-end reads with names and qualities, and (for sam_se_batch) worker1's region lists in read order."""
+    read_len: np.ndarray   # int32 [n]
+    read_off: np.ndarray   # int64 [n]
+    read_pool: np.ndarray  # uint8 codes 0..4
+    qual_pool: np.ndarray | None  # uint8 ASCII, same offsets as read_pool
+    name_off: np.ndarray   # int64 [n + 1]
+    name_pool: np.ndarray  # uint8
+    reg_cnt: np.ndarray | None = None   # int32 [n]
+    regs: np.ndarray | None = None      # ALNREG_DTYPE
+    id0: int = 0
+    id_step: int = 1       # read r is hashed as id0 + r * id_step
+
+    @property
+    def n_reads(self) -> int:
+        return int(np.asarray(self.read_len).shape[0])
+
+    @staticmethod
+    def from_lists(reads, names, quals=None, reg_cnt=None, regs=None, id0=0, id_step=1) -> "SeReadsSoA":
+        ln = np.array([len(r) for r in reads], np.int32)
+        off = np.zeros(len(reads), np.int64)
+        off[1:] = np.cumsum(ln)[:-1]
+        cat = lambda v, dt: np.concatenate([np.asarray(x, dt) for x in v] + [np.zeros(1, dt)])
+        bs = [n if isinstance(n, bytes) else n.encode() for n in names]
+        name_off = np.zeros(len(bs) + 1, np.int64)
+        name_off[1:] = np.cumsum([len(b) for b in bs])
+        return SeReadsSoA(read_len=ln, read_off=off, read_pool=cat(reads, np.uint8), qual_pool=None if quals is None else cat(quals, np.uint8),
+                          name_off=name_off, name_pool=np.frombuffer(b"".join(bs) + b"\0", np.uint8).copy(), reg_cnt=reg_cnt, regs=regs,
+                          id0=id0, id_step=id_step)
+
+
+def _se_struct(g: "SeReadsSoA", with_regs: bool):
+    st = SeReads()
+    st.n_reads, st.id0, st.id_step = g.n_reads, int(g.id0), int(g.id_step)
+    keep = []
+    for f, dt in (("read_len", np.int32), ("read_off", np.int64), ("read_pool", np.uint8), ("name_off", np.int64), ("name_pool", np.uint8)):
+        a = np.ascontiguousarray(getattr(g, f), dt)
+        keep.append(a)
+        setattr(st, f, a.ctypes.data)
+    if g.qual_pool is not None:
+        q = np.ascontiguousarray(g.qual_pool, np.uint8)
+        keep.append(q)
+        st.qual_pool = q.ctypes.data
+    st.read_pool_bytes = int(np.asarray(g.read_pool).size)
+    n_regs = 0
+    if with_regs:
+        cnt = np.ascontiguousarray(g.reg_cnt, np.int32)
+        regs = np.ascontiguousarray(g.regs)
+        assert regs.dtype == ALNREG_DTYPE and int(cnt.sum()) == regs.shape[0]
+        keep += [cnt, regs]
+        st.reg_cnt, st.regs, n_regs = cnt.ctypes.data, regs.ctypes.data, int(regs.shape[0])
+    return st, keep, n_regs
+
+
+def _se_text_call(lib, what, n, call, text_cap):
+    """the capacity protocol of the text entries: call(buf, cap, off, need) until it fits -> per-read byte strings"""
+    off = np.zeros(n + 1, np.int64)
+    need = C.c_size_t(0)
+    cap = 512 * max(1, n) if text_cap is None else int(text_cap)
+    while True:
+        buf = np.empty(max(cap, 1), np.uint8)
+        rc = call(_ptr(buf), cap, _ptr(off), C.byref(need))
+        if rc == -3 and need.value > cap and text_cap is None:   # BPSW_ERR_CAPACITY
+            cap = int(need.value)
+            continue
+        _chk(lib, rc, what)
+        break
+    text = buf[: int(off[-1])].tobytes()
+    return [text[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
+def _ctx_sam_se_batch(self, opt: Opt, topt: "TailOpt", g: "SeReadsSoA", flags: int = 0, text_cap: int | None = None):
+    """singleEndBwaMemWorker2 for a batch -> (list of n SAM texts (bytes), the region lists after mark-primary)"""
+    st, keep, n_regs = _se_struct(g, True)
+    out_regs = np.zeros(max(n_regs, 1), ALNREG_DTYPE)
+    texts = _se_text_call(self.lib, "bpsw_sam_se_batch", g.n_reads,
+                          lambda buf, cap, off, need: self.lib.bpsw_sam_se_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, buf, cap,
+                                                                                 off, need, _ptr(out_regs)), text_cap)
+    return texts, out_regs[:n_regs]
+
+
+def _ctx_align_se_batch(self, opt: Opt, sopt, topt: "TailOpt", g: "SeReadsSoA", zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0,
+                        flags: int = 0, text_cap: int | None = None):
+    """reads -> SAM texts (bytes) per read: worker1_batch with C2A_SORT_DEDUP, then sam_se_batch, in one call"""
+    st, keep, _ = _se_struct(g, False)
+    return _se_text_call(self.lib, "bpsw_align_se_batch", g.n_reads,
+                         lambda buf, cap, off, need: self.lib.bpsw_align_se_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
+                                                                                  zdrop_mode, w1_flags, flags, buf, cap, off, need), text_cap)
+
+
+def last_sam_se_times():
+    """(sam_len_kernel, sam_write_kernel, line table, text round trip, worker1 stage, tail stage) in ms of this thread's last
+    sam_se_batch / align_se_batch"""
+    ms = (C.c_double * 6)()
+    load_library().bpsw_last_sam_se_times(ms)
+    return tuple(ms)
+
+
 TAIL_POOL_TAIL_ONLY = -1
 
 
@@ -1010,6 +1127,8 @@ Context.worker2_batch = _ctx_worker2_batch
 Context.last_tail_kernel = _ctx_last_tail_kernel
 Context.last_tail_host_ms = _ctx_last_tail_host_ms
 Context.last_tail_resubmitted = _ctx_last_tail_resubmitted
+Context.sam_se_batch = _ctx_sam_se_batch
+Context.align_se_batch = _ctx_align_se_batch
 Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute units of the context's device
 
 

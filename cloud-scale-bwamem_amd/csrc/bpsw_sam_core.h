@@ -1,0 +1,238 @@
+// bpsw_sam_core.h -- the bytes of one SAM line without a mate, for the host and for the device.
+//
+// memAlnToSAM (worker2/MemRegToADAMSAM.scala:328-560 == mem_aln2sam, native/bwamem.c:726-838) with m == NULL, as aln_to_sam
+// (bpsw_tail.cpp) writes it on the calling thread; that function stays the yardstick.  Here the same line is a function of a
+// LINE RECORD (SamLine) and the batch's tables (SamBatch), so that a kernel can write it: sam_line_len counts the bytes,
+// sam_line_write stores them, both through one emitter (emit_line) over a sink that either counts or stores, so the two cannot
+// drift apart.  Every store is checked against `end`; a line that would pass it, or whose byte count differs from what the caller
+// expected, is reported through a status word and nothing is written past `end`.
+//
+// Numbers are formatted by counting their digits first and storing straight into the destination; the letter tables are packed
+// constants indexed by shifting.  No array of its own is indexed, so the kernels that compile this have no scratch.
+//
+// Compiled by hipcc for sam_len_kernel / sam_write_kernel (bpsw_sam_se.hip) and by g++ for tests/sam_host/sam_host.cpp.
+#pragma once
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define BPSW_SAM_HD __host__ __device__ inline
+#else
+#define BPSW_SAM_HD inline
+#endif
+
+namespace bpsw {
+namespace samcore {
+
+constexpr int FLAVOUR_SCALA = 0, FLAVOUR_C = 1;  // == BPSW_TAIL_SCALA / BPSW_TAIL_C
+constexpr int ST_OVERRUN = 1;   // a store would have passed `end` (nothing was written there)
+constexpr int ST_MISMATCH = 2;  // the line has another number of bytes than the caller expected
+
+struct SamLine {  // one line: the mem_aln_t of memRegToAln after memRegToSAMSe's bookkeeping (flag unfolded, no 0x4 / 0x10 yet)
+  long long pos;       // 0-based
+  long long cig_at;    // its CIGAR words in SamBatch::cig (n_cigar of them: len << 4 | op, op MIDSH = 01234)
+  long long md_at;     // its MD bytes in SamBatch::md (md_len of them)
+  int32_t read;        // the read it belongs to (SamBatch::reads)
+  int32_t first;       // the first line of that read in SamBatch::lines ...
+  int32_t n_list;      // ... and how many it has (the SA:Z list runs over them)
+  int32_t rid, flag, is_rev, mapq, NM, n_cigar, md_len, score, sub;
+  int32_t pad_;
+};
+static_assert(sizeof(SamLine) == 80, "the line record is staged as it is");
+
+struct SamRead {
+  long long seq_at;   // bases in SamBatch::seq (codes 0..4), qualities at the same place in SamBatch::qual
+  long long name_at;  // in SamBatch::names
+  int32_t len, name_len;
+};
+static_assert(sizeof(SamRead) == 24, "the read record is staged as it is");
+
+struct SamBatch {
+  const SamLine* lines;
+  const SamRead* reads;
+  const uint32_t* cig;
+  const char* md;
+  const uint8_t* seq;
+  const uint8_t* qual;     // null: '*'
+  const char* names;
+  const int32_t* ctg_at;   // n_ctg + 1 offsets into ctg_names; an empty name (or rid >= n_ctg) prints as ctg<rid + 1>
+  const char* ctg_names;
+  const char* rg;          // rg_len bytes; 0: no RG:Z tag
+  int32_t n_ctg, rg_len, flavour;
+};
+
+// ---- sinks ---------------------------------------------------------------------------------------------------------------
+struct CountSink {
+  long long n = 0;
+  BPSW_SAM_HD char* take(long long k) { n += k; return nullptr; }
+};
+struct WriteSink {
+  char* p;
+  char* end;
+  long long n = 0;
+  int over = 0;
+  BPSW_SAM_HD WriteSink(char* dst, char* e) : p(dst), end(e) {}
+  BPSW_SAM_HD char* take(long long k) {  // k more bytes for the caller to store, or null when they would pass `end` (they still count)
+    n += k;
+    if (over || end - p < k) { over = 1; return nullptr; }
+    char* d = p;
+    p += k;
+    return d;
+  }
+};
+
+BPSW_SAM_HD char op_letter(int c) { return (char)((0x485344494DULL >> (8 * (c > 4 ? 4 : c))) & 0xff); }       // "MIDSH"
+BPSW_SAM_HD char base_fwd(int c) { return (char)((0x4E54474341ULL >> (8 * (c > 4 ? 4 : c))) & 0xff); }       // "ACGTN"
+BPSW_SAM_HD char base_rev(int c) { return (char)((0x4E41434754ULL >> (8 * (c > 4 ? 4 : c))) & 0xff); }       // "TGCAN"
+
+template <class S> BPSW_SAM_HD void put_char(S& s, char c) {
+  char* d = s.take(1);
+  if (d) *d = c;
+}
+template <class S> BPSW_SAM_HD void put_bytes(S& s, const char* src, long long k) {
+  char* d = s.take(k);
+  if (d) for (long long i = 0; i < k; ++i) d[i] = src[i];
+}
+template <class S> BPSW_SAM_HD void put_num(S& s, long long v) {
+  const bool neg = v < 0;
+  unsigned long long x = neg ? 0ULL - (unsigned long long)v : (unsigned long long)v;
+  int digits = 1;
+  for (unsigned long long y = x; y >= 10; y /= 10) ++digits;
+  char* d = s.take(digits + (neg ? 1 : 0));
+  if (!d) return;
+  if (neg) *d++ = '-';
+  for (int i = digits - 1; i >= 0; --i) { d[i] = (char)('0' + (int)(x % 10)); x /= 10; }
+}
+template <class S> BPSW_SAM_HD void put_contig(S& s, const SamBatch& B, int rid) {
+  if (rid >= 0 && rid < B.n_ctg && B.ctg_at[rid + 1] > B.ctg_at[rid]) {
+    put_bytes(s, B.ctg_names + B.ctg_at[rid], B.ctg_at[rid + 1] - B.ctg_at[rid]);
+  } else {
+    put_bytes(s, "ctg", 3);
+    put_num(s, (long long)rid + 1);
+  }
+}
+
+BPSW_SAM_HD bool is_clip(uint32_t w) { return (w & 0xf) == 3 || (w & 0xf) == 4; }
+
+template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line) {
+  const SamLine& L = B.lines[line];
+  const SamRead& R = B.reads[L.read];
+  const int which = line - L.first;
+  const uint32_t* cig = B.cig + L.cig_at;
+  int flag = L.flag;
+  if (L.rid < 0) flag |= 0x4;
+  if (L.is_rev) flag |= 0x10;
+  put_bytes(s, B.names + R.name_at, R.name_len);
+  put_char(s, '\t');
+  const int folded = (flag & 0xffff) | ((flag & 0x10000) ? 0x100 : 0);
+  if (B.flavour == FLAVOUR_SCALA) flag = folded;  // the Scala assigns the folded flag, the C only prints it
+  put_num(s, folded);
+  put_char(s, '\t');
+  if (L.rid >= 0) {
+    put_contig(s, B, L.rid);
+    put_char(s, '\t');
+    put_num(s, L.pos + 1);
+    put_char(s, '\t');
+    put_num(s, L.mapq);
+    put_char(s, '\t');
+    if (L.n_cigar > 0) {
+      for (int i = 0; i < L.n_cigar; ++i) {
+        int c = (int)(cig[i] & 0xf);
+        if (c == 3 || c == 4) c = which ? 4 : 3;  // hard clipping on every line but the read's first
+        put_num(s, (long long)(cig[i] >> 4));
+        put_char(s, op_letter(c));
+      }
+    } else {
+      put_char(s, '*');
+    }
+  } else {
+    put_bytes(s, "*\t0\t0\t*", 7);
+  }
+  put_bytes(s, "\t*\t0\t0\t", 7);  // no mate
+  if (flag & 0x100) {
+    put_bytes(s, "*\t*", 3);
+  } else {
+    int qb = 0, qe = R.len;
+    const int nc = L.n_cigar;
+    const bool clip_first = nc > 0 && is_clip(cig[0]), clip_last = nc > 0 && is_clip(cig[nc - 1]);
+    const uint8_t* seq = B.seq + R.seq_at;
+    if (!L.is_rev) {
+      if (which && clip_first) qb += (int)(cig[0] >> 4);
+      if (which && clip_last) qe -= (int)(cig[nc - 1] >> 4);
+    } else {
+      if (which && clip_first) qe -= (int)(cig[0] >> 4);
+      if (which && clip_last) qb += (int)(cig[nc - 1] >> 4);
+    }
+    const long long n = qe > qb ? qe - qb : 0;
+    char* d = s.take(n + 1 + (B.qual ? n : 1));  // bases, tab, qualities
+    if (d) {
+      if (!L.is_rev) for (long long i = 0; i < n; ++i) d[i] = base_fwd(seq[qb + i]);
+      else for (long long i = 0; i < n; ++i) d[i] = base_rev(seq[qe - 1 - i]);
+      d[n] = '\t';
+      if (!B.qual) {
+        d[n + 1] = '*';
+      } else {
+        const uint8_t* q = B.qual + R.seq_at;
+        if (!L.is_rev) for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qb + i];
+        else for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qe - 1 - i];
+      }
+    }
+  }
+  if (L.n_cigar > 0) {
+    put_bytes(s, "\tNM:i:", 6);
+    put_num(s, L.NM);
+    put_bytes(s, "\tMD:Z:", 6);
+    if (L.md_len > 0) put_bytes(s, B.md + L.md_at, L.md_len);
+  }
+  if (L.score >= 0) { put_bytes(s, "\tAS:i:", 6); put_num(s, L.score); }
+  if (L.sub >= 0) { put_bytes(s, "\tXS:i:", 6); put_num(s, L.sub); }
+  if (B.rg_len > 0) { put_bytes(s, "\tRG:Z:", 6); put_bytes(s, B.rg, B.rg_len); }
+  if (!(flag & 0x100)) {
+    bool others = false;
+    for (int i = 0; i < L.n_list; ++i)
+      if (i != which && !(B.lines[L.first + i].flag & 0x100)) { others = true; break; }
+    if (others) {
+      put_bytes(s, "\tSA:Z:", 6);
+      for (int i = 0; i < L.n_list; ++i) {
+        const SamLine& r = B.lines[L.first + i];
+        if (i == which || (r.flag & 0x100)) continue;
+        put_contig(s, B, r.rid);
+        put_char(s, ',');
+        put_num(s, r.pos + 1);
+        put_char(s, ',');
+        put_char(s, r.is_rev ? '-' : '+');
+        put_char(s, ',');
+        const uint32_t* rc = B.cig + r.cig_at;
+        for (int k = 0; k < r.n_cigar; ++k) { put_num(s, (long long)(rc[k] >> 4)); put_char(s, op_letter((int)(rc[k] & 0xf))); }
+        put_char(s, ',');
+        put_num(s, r.mapq);
+        put_char(s, ',');
+        put_num(s, r.NM);
+        put_char(s, ';');
+      }
+    }
+  }
+  put_char(s, '\n');
+}
+
+// the number of bytes of line `line`
+BPSW_SAM_HD long long sam_line_len(const SamBatch& B, int line) {
+  CountSink s;
+  emit_line(s, B, line);
+  return s.n;
+}
+
+// Writes line `line` at dst and never at or past `end`.  Returns the line's number of bytes (written or not); *status gets
+// ST_OVERRUN when the line did not fit [dst, end), and ST_MISMATCH when expected >= 0 and the line has another number of bytes.
+BPSW_SAM_HD long long sam_line_write(char* dst, char* end, const SamBatch& B, int line, long long expected, int* status) {
+  WriteSink s(dst, end);
+  emit_line(s, B, line);
+  int st = 0;
+  if (s.over) st |= ST_OVERRUN;
+  if (expected >= 0 && s.n != expected) st |= ST_MISMATCH;
+  *status = st;
+  return s.n;
+}
+
+}  // namespace samcore
+}  // namespace bpsw

@@ -1,0 +1,326 @@
+// bpsw_sam_se.hip -- the single-end worker2 behind the C ABI: bpsw_sam_se_batch, bpsw_align_se_batch, and the SAM text written on
+// the device (BPSW_SAM_TEXT_DEVICE).
+//
+// singleEndBwaMemWorker2 (worker2/BWAMemWorker2.scala:49-58 == native/bwamem.c:1052-1056) for a batch: per read mem_mark_primary_se,
+// then mem_reg2sam_se with extra_flag = 0 and no mate (native/bwamem.c:879-892, R2S:67-118).  The pieces are bpsw_tail.cpp's
+// (bpsw_tail_internal.h): mark_primary, run_jobs over reg2aln_kernel, make_aln, and aln_to_sam for the text on the calling thread.
+//
+// With BPSW_SAM_TEXT_DEVICE the text is written by two kernels over bpsw_sam_core.h, the byte definition of a line without a mate:
+//   sam_len_kernel    one line per lane: the line's number of bytes; the host sums them to line offsets, per-read out_off and
+//                     the total (a total past text_cap ends the call there);
+//   sam_write_kernel  one line per lane: the line's bytes at its offset in one device block, which comes back with one copy.
+// A line depends on its read's lines only (the SA:Z list), so a lane needs nothing of another read.  Into the kernels go, as one
+// staged block, the line table built on the host from make_aln's results (fixed-size records, each line's CIGAR words and MD
+// bytes), the read records with the base, quality and name pools, the contig names and the read-group ID.
+#include <string.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "bpsw_tail_internal.h"
+#include "bpsw_sam_core.h"
+
+using namespace bpsw;
+namespace sc = bpsw::samcore;
+
+namespace {
+
+__global__ __launch_bounds__(64) void sam_len_kernel(sc::SamBatch B, int n_lines, int32_t* __restrict__ len) {
+  const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (i >= n_lines) return;
+  len[i] = (int32_t)sc::sam_line_len(B, i);
+}
+
+// line i goes to text[line_off[i] .. line_off[i + 1]); status: the OR of every line's sam_line_write status
+__global__ __launch_bounds__(64) void sam_write_kernel(sc::SamBatch B, int n_lines, const long long* __restrict__ line_off, char* text,
+                                                       int* status) {
+  const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (i >= n_lines) return;
+  const long long at = line_off[i], len = line_off[i + 1] - at;
+  int st = 0;
+  sc::sam_line_write(text + at, text + at + len, B, i, len, &st);
+  if (st) atomicOr(status, st);
+}
+
+thread_local double t_last[6] = {0., 0., 0., 0., 0., 0.};
+
+struct SePlan {  // per read: memRegToSAMSe's selection, (region index, job)
+  std::vector<std::pair<int, int> > jobs;
+};
+
+int check_reads(const char* who, const bpsw_se_reads_t* g, bool need_regs, size_t* n_regs) {
+  const int n = g->n_reads;
+  if (!g->read_len || !g->read_off || !g->read_pool || !g->name_off || !g->name_pool) return fail(BPSW_ERR_ARG, std::string(who) + ": null read arrays");
+  if (g->id_step < 0) return fail(BPSW_ERR_ARG, std::string(who) + ": negative id_step");
+  if (need_regs && !g->reg_cnt) return fail(BPSW_ERR_ARG, std::string(who) + ": null region counts");
+  *n_regs = 0;
+  for (int r = 0; r < n; ++r) {
+    if (need_regs && g->reg_cnt[r] < 0) return fail(BPSW_ERR_ARG, std::string(who) + ": negative region count");
+    if (g->read_len[r] < 1 || g->read_off[r] < 0 || (unsigned long long)(g->read_off[r] + g->read_len[r]) > g->read_pool_bytes)
+      return fail(BPSW_ERR_ARG, std::string(who) + ": read outside its pool (or empty)");
+    if (g->name_off[r] < 0 || g->name_off[r + 1] < g->name_off[r]) return fail(BPSW_ERR_ARG, std::string(who) + ": name offsets must ascend");
+    if (need_regs) *n_regs += (size_t)g->reg_cnt[r];
+  }
+  if (need_regs && *n_regs && !g->regs) return fail(BPSW_ERR_ARG, std::string(who) + ": null region array");
+  return BPSW_OK;
+}
+
+// The text of the lines in `lines` (per read: aa[read_first[r] .. read_first[r + 1])) through the two kernels.  Caller holds c->mu.
+int text_on_device(bpsw_ctx* c, const BnsView& bns, const bpsw_tail_opt_t& t, const bpsw_se_reads_t* g, const std::vector<Aln>& aa,
+                   const std::vector<int32_t>& line_read, const std::vector<int32_t>& read_first, const JobResults& R, char* out_text,
+                   size_t text_cap, int64_t* out_off, size_t* total_out) {
+  const int n = g->n_reads, n_lines = (int)aa.size();
+  const double t0 = wall_ms();
+  // ---- the line table -------------------------------------------------------------------------------------------------------
+  std::vector<sc::SamLine> lines((size_t)n_lines);
+  for (int i = 0; i < n_lines; ++i) {
+    const Aln& x = aa[(size_t)i];
+    sc::SamLine& L = lines[(size_t)i];
+    memset(&L, 0, sizeof L);
+    const int r = line_read[(size_t)i];
+    L.pos = x.a.pos;
+    L.cig_at = x.a.n_cigar > 0 ? (long long)(x.cigar - R.cig.data()) : 0;
+    L.md_at = x.a.md_len > 0 ? (long long)(x.md - R.md.data()) : 0;
+    L.read = r; L.first = read_first[(size_t)r]; L.n_list = read_first[(size_t)r + 1] - read_first[(size_t)r];
+    L.rid = x.a.rid; L.flag = x.a.flag; L.is_rev = x.a.is_rev; L.mapq = x.a.mapq; L.NM = x.a.NM; L.n_cigar = x.a.n_cigar;
+    L.md_len = x.a.md_len; L.score = x.a.score; L.sub = x.a.sub;
+  }
+  // the reads' bytes: the covering span of the base pool (and of the quality pool, same offsets), the names' span
+  long long lo = (long long)g->read_pool_bytes, hi = 0;
+  for (int r = 0; r < n; ++r) { lo = std::min<long long>(lo, g->read_off[r]); hi = std::max<long long>(hi, g->read_off[r] + g->read_len[r]); }
+  const long long name_lo = g->name_off[0], name_hi = g->name_off[n];
+  std::vector<sc::SamRead> reads((size_t)n);
+  for (int r = 0; r < n; ++r) {
+    reads[(size_t)r].seq_at = g->read_off[r] - lo;
+    reads[(size_t)r].name_at = g->name_off[r] - name_lo;
+    reads[(size_t)r].len = g->read_len[r];
+    reads[(size_t)r].name_len = (int32_t)(g->name_off[r + 1] - g->name_off[r]);
+  }
+  std::vector<int32_t> ctg_at(bns.name.size() + 1, 0);
+  std::vector<char> ctg_names;
+  for (size_t k = 0; k < bns.name.size(); ++k) {
+    ctg_names.insert(ctg_names.end(), bns.name[k].begin(), bns.name[k].end());
+    ctg_at[k + 1] = (int32_t)ctg_names.size();
+  }
+  const size_t rg_len = t.rg_id[0] ? strnlen(t.rg_id, sizeof t.rg_id) : 0;
+
+  StageIn in;
+  const int i_lines = in.add(lines.data(), sizeof(sc::SamLine) * (size_t)n_lines), i_reads = in.add(reads.data(), sizeof(sc::SamRead) * (size_t)n);
+  const int i_cig = in.add(R.cig.data(), 4 * R.cig.size()), i_md = in.add(R.md.data(), R.md.size());
+  const int i_seq = in.add(g->read_pool + lo, (size_t)(hi - lo));
+  const int i_qual = g->qual_pool ? in.add(g->qual_pool + lo, (size_t)(hi - lo)) : -1;
+  const int i_names = in.add(g->name_pool + name_lo, (size_t)(name_hi - name_lo));
+  const int i_cat = in.add(ctg_at.data(), 4 * ctg_at.size()), i_cnm = in.add(ctg_names.data(), ctg_names.size());
+  const int i_rg = in.add(t.rg_id, rg_len);
+  StageOut lens;
+  const int r_len = lens.add(4 * (size_t)n_lines);
+  HIP_TRY(lens.reserve(c->h_stage_out, c->d_sw_out));
+  HIP_TRY(in.stage(c->h_stage_in, c->d_sw_in, c->stream));
+  sc::SamBatch B;
+  B.lines = in.dev<sc::SamLine>(i_lines); B.reads = in.dev<sc::SamRead>(i_reads);
+  B.cig = in.dev<uint32_t>(i_cig); B.md = in.dev<char>(i_md);
+  B.seq = in.dev<uint8_t>(i_seq); B.qual = i_qual >= 0 ? in.dev<uint8_t>(i_qual) : nullptr;
+  B.names = in.dev<char>(i_names);
+  B.ctg_at = in.dev<int32_t>(i_cat); B.ctg_names = in.dev<char>(i_cnm);
+  B.rg = in.dev<char>(i_rg);
+  B.n_ctg = (int32_t)bns.name.size(); B.rg_len = (int32_t)rg_len; B.flavour = t.flavour;
+  const dim3 grid((unsigned)((n_lines + 63) / 64));
+  const double t1 = wall_ms();
+  // ---- lengths ---------------------------------------------------------------------------------------------------------------
+  HIP_TRY(hipEventRecord(c->ev[6], c->stream));
+  hipLaunchKernelGGL(sam_len_kernel, grid, dim3(64), 0, c->stream, B, n_lines, lens.dev<int32_t>(r_len));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev[7], c->stream));
+  HIP_TRY(lens.fetch(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  float ms_len = 0.f;
+  (void)hipEventElapsedTime(&ms_len, c->ev[6], c->ev[7]);
+  std::vector<long long> line_off((size_t)n_lines + 1, 0);
+  const int32_t* hl = lens.host<int32_t>(r_len);
+  for (int i = 0; i < n_lines; ++i) {
+    if (hl[i] < 1) return fail(BPSW_ERR_DEVICE, "sam_se: a line came back with no length");
+    line_off[(size_t)i + 1] = line_off[(size_t)i] + hl[i];
+  }
+  for (int r = 0; r <= n; ++r) out_off[r] = (int64_t)line_off[(size_t)read_first[(size_t)r]];
+  const size_t total = (size_t)line_off[(size_t)n_lines];
+  *total_out = total;
+  t_last[0] = ms_len; t_last[1] = 0.; t_last[2] = t1 - t0;
+  const double t2 = wall_ms();
+  if (!out_text || total > text_cap) { t_last[3] = t2 - t1; return BPSW_OK; }  // (the caller reports the capacity)
+  // ---- text ------------------------------------------------------------------------------------------------------------------
+  // (the pinned input block is free again: its copy has been waited for; the line table stays where it is on the device)
+  StageIn io;
+  const int i_off = io.add(line_off.data(), 8 * ((size_t)n_lines + 1));
+  StageOut txt;
+  const int r_text = txt.add(total), r_status = txt.add(16);
+  HIP_TRY(txt.reserve(c->h_stage_out, c->d_gl_z));  // (the backtrack scratch of run_jobs: free by now)
+  HIP_TRY(io.stage(c->h_stage_in, c->d_sw_out, c->stream));  // (the lengths have come back)
+  HIP_TRY(hipMemsetAsync(txt.dev<int>(r_status), 0, 16, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[6], c->stream));
+  hipLaunchKernelGGL(sam_write_kernel, grid, dim3(64), 0, c->stream, B, n_lines, io.dev<long long>(i_off), txt.dev<char>(r_text),
+                     txt.dev<int>(r_status));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev[7], c->stream));
+  HIP_TRY(txt.fetch(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  float ms_write = 0.f;
+  (void)hipEventElapsedTime(&ms_write, c->ev[6], c->ev[7]);
+  t_last[1] = ms_write;
+  if (*txt.host<int>(r_status)) return fail(BPSW_ERR_DEVICE, "sam_se: a line's bytes differ in number from its length (sam_line_write's status)");
+  memcpy(out_text, txt.host<char>(r_text), total);
+  t_last[3] = wall_ms() - t1;
+  return BPSW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpsw_sam_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g, int flags,
+                      char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
+  if (!c || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "sam_se: null argument");
+  if (flags & ~BPSW_SAM_TEXT_DEVICE) return fail(BPSW_ERR_ARG, "sam_se: unknown flag");
+  SwScoring sw;
+  int rc = make_scoring("tail", opt, 0, 1, &sw);
+  if (rc != BPSW_OK) return rc;
+  const int n = g->n_reads;
+  if (n < 0) return fail(BPSW_ERR_ARG, "sam_se: negative number of reads");
+  if (n == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
+  size_t n_regs = 0;
+  rc = check_reads("sam_se", g, true, &n_regs);
+  if (rc != BPSW_OK) return rc;
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
+  BnsView bns;
+  rc = snapshot_bns(c, &bns);
+  if (rc != BPSW_OK) return rc;
+  const bpsw_opt_t& o = *opt;
+  const bpsw_tail_opt_t& t = *topt;
+
+  // ---- plan: mem_mark_primary_se and mem_reg2sam_se's selection ---------------------------------------------------------------
+  c->last_tail_ms = 0.f; c->last_tail_jobs = 0; c->last_tail_resubmitted = 0;
+  memset(t_last, 0, sizeof t_last);
+  const double t_plan = wall_ms();
+  std::vector<bpsw_alnreg_t> regs(g->regs, g->regs + n_regs);  // sorted in place, read by read
+  std::vector<size_t> reg_at((size_t)n + 1, 0);
+  std::vector<SePlan> plan((size_t)n);
+  std::vector<int32_t> job_len;
+  std::vector<int64_t> job_off;
+  std::vector<bpsw_alnreg_t> job_reg;
+  std::vector<bpsw_alnreg_t> a;
+  for (int r = 0; r < n; ++r) {
+    reg_at[(size_t)r + 1] = reg_at[(size_t)r] + (size_t)g->reg_cnt[r];
+    a.assign(regs.begin() + (long)reg_at[(size_t)r], regs.begin() + (long)reg_at[(size_t)r + 1]);
+    mark_primary(o, t, a, g->id0 + (int64_t)r * g->id_step);
+    std::copy(a.begin(), a.end(), regs.begin() + (long)reg_at[(size_t)r]);
+    for (size_t j = 0; j < a.size(); ++j) {  // native/bwamem.c:879-892, R2S:67-118
+      const bpsw_alnreg_t& p = a[j];
+      if (p.score < o.T) continue;
+      if (p.secondary >= 0 && !(o.flag & BPSW_MEM_F_ALL)) continue;
+      if (p.secondary >= 0 && p.score < a[(size_t)p.secondary].score * .5) continue;
+      int job = -1;
+      if (p.rb >= 0 && p.re >= 0) {  // (else the unmapped record, R2S:175-180)
+        job_len.push_back(g->read_len[r]); job_off.push_back(g->read_off[r]); job_reg.push_back(p);
+        job = (int)job_reg.size() - 1;
+      }
+      plan[(size_t)r].jobs.push_back(std::make_pair((int)j, job));
+    }
+  }
+
+  // ---- device: memRegToAln ------------------------------------------------------------------------------------------------------
+  static thread_local JobResults results;  // (kept per calling thread: no allocation in the steady state)
+  JobResults& R = results;
+  const double t_dev = wall_ms();
+  rc = run_jobs(c, sw, opt, t.flavour, bns, job_len, job_off, g->read_pool, g->read_pool_bytes, job_reg, &R);
+  if (rc != BPSW_OK) return rc;
+  for (size_t j = 0; j < R.r.size(); ++j)
+    if (R.r[j].k.status == BPSW_ALN_XREF || R.r[j].k.status == BPSW_ALN_OVERFLOW)
+      return fail(BPSW_ERR_LIMIT, R.r[j].k.status == BPSW_ALN_XREF ? "sam_se: bwaFixXref2 could not repair a region (the reference aborts here)"
+                                                                   : "sam_se: an alignment has more CIGAR operations than the kernel stages");
+
+  // ---- emit ---------------------------------------------------------------------------------------------------------------------
+  const double t_emit = wall_ms();
+  std::vector<Aln> aa;
+  std::vector<int32_t> line_read, read_first((size_t)n + 1, 0);
+  for (int r = 0; r < n; ++r) {
+    const bpsw_alnreg_t* ar = regs.data() + reg_at[(size_t)r];
+    const size_t first = aa.size();
+    for (size_t x = 0; x < plan[(size_t)r].jobs.size(); ++x) {
+      const int j = plan[(size_t)r].jobs[x].first, jb = plan[(size_t)r].jobs[x].second;
+      const bpsw_alnreg_t& p = ar[j];
+      Aln q = make_aln(o, t, &p, jb >= 0 ? &R.r[(size_t)jb] : nullptr, R);
+      if (p.secondary >= 0) q.a.sub = -1;  // don't output the sub-optimal score
+      if (j && p.secondary < 0) q.a.flag |= (o.flag & BPSW_MEM_F_NO_MULTI) ? 0x10000 : 0x800;  // supplementary
+      if (j && aa.size() > first && q.a.mapq > aa[first].a.mapq) q.a.mapq = aa[first].a.mapq;
+      aa.push_back(q);
+    }
+    if (aa.size() == first) aa.push_back(make_aln(o, t, nullptr, nullptr, R));  // the unaligned record
+    line_read.resize(aa.size(), r);
+    read_first[(size_t)r + 1] = (int32_t)aa.size();
+  }
+  size_t total = 0;
+  if (flags & BPSW_SAM_TEXT_DEVICE) {
+    rc = text_on_device(c, bns, t, g, aa, line_read, read_first, R, out_text, text_cap, out_off, &total);
+    if (rc != BPSW_OK) return rc;
+  } else {
+    Text text(out_text, text_cap);
+    for (int r = 0; r < n; ++r) {
+      out_off[r] = (int64_t)text.size();
+      const char* name = g->name_pool + g->name_off[r];
+      const size_t name_len = (size_t)(g->name_off[r + 1] - g->name_off[r]);
+      const uint8_t* seq = g->read_pool + g->read_off[r];
+      const uint8_t* qual = g->qual_pool ? g->qual_pool + g->read_off[r] : nullptr;
+      const Aln* list = aa.data() + read_first[(size_t)r];
+      const size_t n_list = (size_t)(read_first[(size_t)r + 1] - read_first[(size_t)r]);
+      for (size_t x = 0; x < n_list; ++x)
+        aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[r], seq, qual, list, n_list, (int)x, nullptr, t.rg_id);
+    }
+    out_off[n] = (int64_t)text.size();
+    total = text.size();
+  }
+  if (out_regs && n_regs) memcpy(out_regs, regs.data(), sizeof(bpsw_alnreg_t) * n_regs);
+  c->tail_host_ms[0] = t_dev - t_plan; c->tail_host_ms[1] = t_emit - t_dev; c->tail_host_ms[2] = wall_ms() - t_emit;
+  if (out_needed) *out_needed = total;
+  if (!out_text || total > text_cap) return fail(BPSW_ERR_CAPACITY, "sam_se: text buffer too small (see *out_needed)");
+  return BPSW_OK;
+}
+
+int bpsw_align_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt,
+                        const bpsw_se_reads_t* g, int zdrop_mode, int w1_flags, int flags, char* out_text, size_t text_cap, int64_t* out_off,
+                        size_t* out_needed) {
+  if (!c || !opt || !sopt || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "align_se: null argument");
+  const int n = g->n_reads;
+  if (n < 0) return fail(BPSW_ERR_ARG, "align_se: negative number of reads");
+  if (n == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
+  size_t none = 0;
+  int rc = check_reads("align_se", g, false, &none);
+  if (rc != BPSW_OK) return rc;
+  // ---- worker1: reads -> region lists (FastMap.scala:624) ---------------------------------------------------------------------
+  const double t0 = wall_ms();
+  bpsw_reads_t rd;
+  rd.n_reads = n; rd.read_len = g->read_len; rd.read_off = g->read_off; rd.read_pool = g->read_pool; rd.read_pool_bytes = g->read_pool_bytes;
+  std::vector<int32_t> cnt((size_t)n, 0);
+  std::vector<bpsw_alnreg_t> regs((size_t)(4 * (int64_t)n + 64));
+  int64_t total = 0;
+  rc = bpsw_worker1_batch(c, opt, sopt, &rd, zdrop_mode, w1_flags | BPSW_C2A_SORT_DEDUP, cnt.data(), regs.data(), (int64_t)regs.size(), &total);
+  if (rc == BPSW_ERR_CAPACITY && total > (int64_t)regs.size()) {
+    regs.resize((size_t)total);
+    rc = bpsw_worker1_batch(c, opt, sopt, &rd, zdrop_mode, w1_flags | BPSW_C2A_SORT_DEDUP, cnt.data(), regs.data(), (int64_t)regs.size(), &total);
+  }
+  if (rc != BPSW_OK) return rc;
+  // ---- worker2: the lists -> text (FastMap.scala:625) ---------------------------------------------------------------------------
+  const double t1 = wall_ms();
+  bpsw_se_reads_t s = *g;
+  s.reg_cnt = cnt.data();
+  s.regs = regs.data();
+  rc = bpsw_sam_se_batch(c, opt, topt, &s, flags, out_text, text_cap, out_off, out_needed, nullptr);
+  t_last[4] = t1 - t0; t_last[5] = wall_ms() - t1;
+  return rc;
+}
+
+void bpsw_last_sam_se_times(double ms[6]) {
+  if (ms) memcpy(ms, t_last, sizeof t_last);
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@
 #include <utility>
 #include <vector>
 
-#include "bpsw_internal.h"
+#include "bpsw_tail_internal.h"  // (with bpsw_internal.h) what bpsw_sam_se.hip shares with this file
 
 using namespace bpsw;
 
@@ -28,19 +28,9 @@ namespace {
 // the kernel stages at most this many CIGAR operations (CIG_LDS in bpsw_global_core.h)
 constexpr int KERNEL_CIG_CAP = 512;
 
-struct BnsView {
-  long long l_pac = 0;
-  const uint8_t* d_pac = nullptr;
-  int n_seqs = 0;
-  const long long* d_off = nullptr;
-  const int32_t* d_len = nullptr;
-  std::vector<long long> off;
-  std::vector<int32_t> len;
-  std::vector<std::string> name;
-  RefHold hold;  // the reference and the contig table stay put while this view lives
-};
+}  // namespace
 
-int snapshot_bns(const bpsw_ctx* c, BnsView* v) {
+int bpsw::snapshot_bns(const bpsw_ctx* c, BnsView* v) {
   DeviceRef& r = device_ref(c->device);
   v->hold = RefHold(&r.gate);
   std::lock_guard<std::mutex> g(r.mu);
@@ -55,15 +45,7 @@ int snapshot_bns(const bpsw_ctx* c, BnsView* v) {
   return BPSW_OK;
 }
 
-struct JobResult {
-  Reg2AlnOut k;
-  size_t cig_at = 0, md_at = 0;  // its CIGAR words / MD bytes in JobResults::cig / ::md (k.n_cigar, k.md_len of them)
-};
-struct JobResults {  // one allocation per kind and call, not two per job
-  std::vector<JobResult> r;
-  std::vector<uint32_t> cig;
-  std::vector<char> md;
-};
+namespace {
 
 // One launch of reg2aln_kernel over `n` mapped jobs (regs[j] with rb, re >= 0); caller holds c->mu and has set the device.
 int launch_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int flavour, const BnsView& bns, int n, const int32_t* read_len,
@@ -127,8 +109,10 @@ int launch_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int fla
   return BPSW_OK;
 }
 
+}  // namespace
+
 // All jobs of a call, re-submitting the few whose CIGAR or MD did not fit the first, small, per-job room.
-int run_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int flavour, const BnsView& bns, const std::vector<int32_t>& read_len,
+int bpsw::run_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int flavour, const BnsView& bns, const std::vector<int32_t>& read_len,
              const std::vector<int64_t>& read_off, const uint8_t* read_pool, size_t read_pool_bytes,
              const std::vector<bpsw_alnreg_t>& regs, JobResults* res) {
   const int n = (int)regs.size();
@@ -171,6 +155,8 @@ int run_jobs(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, int flavou
   return BPSW_OK;
 }
 
+namespace {
+
 // ---- the scalar pieces of the tail -----------------------------------------------------------------------------------
 inline uint64_t hash64(uint64_t key) {  // MP:111-122
   key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
@@ -178,8 +164,10 @@ inline uint64_t hash64(uint64_t key) {  // MP:111-122
   return key;
 }
 
+}  // namespace
+
 // memMarkPrimarySe, MP:37-109 (C: native/bwamem.c:444-477): sorts `a` and fills sub / sub_n / secondary / hash
-void mark_primary(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, std::vector<bpsw_alnreg_t>& a, int64_t id) {
+void bpsw::mark_primary(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, std::vector<bpsw_alnreg_t>& a, int64_t id) {
   const int n = (int)a.size();
   if (n == 0) return;
   for (int i = 0; i < n; ++i) { a[(size_t)i].sub = 0; a[(size_t)i].secondary = -1; a[(size_t)i].hash = hash64((uint64_t)(id + i)); }
@@ -211,6 +199,8 @@ void mark_primary(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, std::vector<bps
     else a[(size_t)i].secondary = t.flavour == BPSW_TAIL_C ? prim[(size_t)k] : prim[(size_t)k + 1];  // MP:93-101 reads z(k) after k += 1
   }
 }
+
+namespace {
 
 // log(l) for the alignment lengths memApproxMapqSe meets (one call per alignment: the same doubles as log(), computed once)
 inline double log_of_len(int l) {
@@ -327,12 +317,6 @@ PairScore mem_pair(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, long long l_pa
 }
 
 // ---- plan / emit -------------------------------------------------------------------------------------------------------
-struct Aln {  // a mem_aln_t under construction
-  bpsw_aln_t a;
-  const uint32_t* cigar = nullptr;  // a.n_cigar words
-  const char* md = nullptr;         // a.md_len bytes
-};
-
 struct EndPlan {
   int h_job = -1;                             // the job behind h[i] (-1: the unmapped record)
   std::vector<std::pair<int, int> > se_jobs;  // memRegToSAMSe: (region index k, job)
@@ -341,24 +325,6 @@ struct PairPlan {
   bool paired = false;
   int z[2] = {0, 0}, q_se[2] = {0, 0}, extra_flag = 1;
   EndPlan end[2];
-};
-
-// The text of a call is written straight into the caller's buffer (round 3 built a std::string and copied it: push_back by
-// push_back, 2.3 GB/s and a 3 MB memcpy per 4 096 pairs).  Past the capacity it only counts, so that *out_needed comes out right.
-struct Text {
-  char* buf;
-  size_t cap, n = 0;
-  Text(char* b, size_t c) : buf(b), cap(b ? c : 0) {}
-  size_t size() const { return n; }
-  char* grow(size_t len) {  // len more bytes, to be written by the caller; nullptr when they do not fit (they still count)
-    char* p = n + len <= cap ? buf + n : nullptr;
-    n += len;
-    return p;
-  }
-  void push_back(char c) { if (n < cap) buf[n] = c; ++n; }
-  void append(const char* p, size_t len) { char* d = grow(len); if (d) memcpy(d, p, len); }
-  Text& operator+=(const char* z) { append(z, strlen(z)); return *this; }
-  Text& operator+=(const std::string& z) { append(z.data(), z.size()); return *this; }
 };
 
 const char kDigitPairs[201] =
@@ -437,8 +403,10 @@ inline void put_reversed(char* d, const uint8_t* q, size_t n) {
   put_reversed_scalar(d, q, n);
 }
 
+}  // namespace
+
 // memAlnToSAM, R2S:328-560 (C: native/bwamem.c:726-838; the Scala leaves the comment field out, R2S:546-556)
-void aln_to_sam(const BnsView& bns, int flavour, Text& s, const char* name, size_t name_len, int l_seq, const uint8_t* seq,
+void bpsw::aln_to_sam(const BnsView& bns, int flavour, Text& s, const char* name, size_t name_len, int l_seq, const uint8_t* seq,
                 const uint8_t* qual, const Aln* list, const size_t n_list, int which, const Aln* mate_in, const char* rg_id) {
   Aln p = list[(size_t)which];
   Aln m;
@@ -537,11 +505,15 @@ void aln_to_sam(const BnsView& bns, int flavour, Text& s, const char* name, size
   s.push_back('\n');
 }
 
+namespace {
+
 const uint32_t kNoCigar[1] = {0};
 const char kNoMd[1] = {0};
 
+}  // namespace
+
 // the mem_aln_t of memRegToAln: kernel result + the fields that need no sequence (R2S:188-192, :306-310)
-Aln make_aln(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, const bpsw_alnreg_t* ar, const JobResult* jr, const JobResults& R) {
+Aln bpsw::make_aln(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, const bpsw_alnreg_t* ar, const JobResult* jr, const JobResults& R) {
   Aln x;
   memset(&x.a, 0, sizeof x.a);
   x.cigar = kNoCigar; x.md = kNoMd;
@@ -557,8 +529,6 @@ Aln make_aln(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, const bpsw_alnreg_t*
   x.cigar = R.cig.data() + jr->cig_at; x.md = R.md.data() + jr->md_at;
   return x;
 }
-
-}  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------
 void bpsw_tail_opt_default(bpsw_tail_opt_t* t) {  // datatype/MemOptType.scala:47-52

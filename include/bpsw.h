@@ -551,6 +551,52 @@ int bpsw_last_tail_times(bpsw_ctx_t *ctx, float *kernel_ms, int32_t *n_jobs, dou
  * every job room for 16 operations / 64 MD bytes first, then 128 / 512, then 514 / 4096; a job is counted once per extra launch) */
 int bpsw_last_tail_resubmitted(bpsw_ctx_t *ctx, int32_t *n_resubmitted);
 
+/* ---- single-end reads to SAM (bpsw_sam_se.hip) ---------------------------------------------------------------------------
+ *
+ * bpsw_sam_se_batch is singleEndBwaMemWorker2 (worker2/BWAMemWorker2.scala:49-58 == native/bwamem.c:1052-1056) for a batch: per read
+ * mem_mark_primary_se with id = id0 + r * id_step, then mem_reg2sam_se with extra_flag = 0 and no mate (native/bwamem.c:879-892 ==
+ * memRegToSAMSe, worker2/MemRegToADAMSAM.scala:67-118): regions with score >= T, secondary hits only under BPSW_MEM_F_ALL and not
+ * below half their parent's score, one memRegToAln job each (on the GPU, as in the paired tail), 0x800 (0x10000 under
+ * BPSW_MEM_F_NO_MULTI) for later primaries, their mapQ capped at the first line's, the unaligned record for a read without a
+ * selected region, and the SAM lines without the mate's flag bits and with "*\t0\t0" for the mate columns.  id_step: 1 is the C
+ * (n_processed + i), 0 is what FastMap.scala:624-635 does (every read of a batch gets the same numProcessed); any value >= 0.
+ * Both flavours and topt->rg_id as in bpsw_sam_pe_batch; text, out_off (n_reads + 1), *out_needed and BPSW_ERR_CAPACITY as there
+ * (nothing is written past text_cap, out_off is complete); BPSW_ERR_LIMIT where the reference aborts (XREF) or an alignment
+ * outgrows the kernel's CIGAR staging; BPSW_ERR_ARG for a read outside its pool or an empty read; bpsw_reg2aln_batch's size limits;
+ * n_reads == 0 is fine.  out_regs (optional, same size as regs): the lists after mem_mark_primary_se.  Fills
+ * bpsw_last_tail_times as the paired tail does.
+ *
+ * flags: with BPSW_SAM_TEXT_DEVICE the text is written by two kernels (the length of every line, then its bytes, one line per
+ * lane) and comes back in one copy; the bytes are the same.  Default: on the calling thread, as in the paired tail.
+ *
+ * bpsw_align_se_batch is FastMap.scala:624-625 in one call: bpsw_worker1_batch with w1_flags | BPSW_C2A_SORT_DEDUP and zdrop_mode
+ * (its capacity retry handled inside), then bpsw_sam_se_batch on the lists it got (g->reg_cnt / g->regs are ignored).  Needs the
+ * reference, the contig table and the index on the context's device; reads of at most BPSW_SEED_MAX_QLEN bases. */
+#define BPSW_SAM_TEXT_DEVICE 1 /* flags: write the SAM text on the device; default: on the calling thread */
+typedef struct {
+  int32_t n_reads;
+  int64_t id0;
+  int32_t id_step; /* read r is hashed as id0 + r * id_step (mem_mark_primary_se's id) */
+  const int32_t *read_len;
+  const int64_t *read_off;
+  const uint8_t *read_pool; /* codes 0..4 */
+  const uint8_t *qual_pool; /* same offsets as read_pool, or NULL ('*') */
+  size_t read_pool_bytes;
+  const int64_t *name_off; /* n_reads + 1 offsets into name_pool */
+  const char *name_pool;
+  const int32_t *reg_cnt; /* worker1's lists, read order; ignored by bpsw_align_se_batch */
+  const bpsw_alnreg_t *regs;
+} bpsw_se_reads_t;
+int bpsw_sam_se_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_tail_opt_t *topt, const bpsw_se_reads_t *reads, int flags,
+                      char *out_text, size_t text_cap, int64_t *out_off, size_t *out_needed, bpsw_alnreg_t *out_regs);
+int bpsw_align_se_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                        const bpsw_se_reads_t *reads, int zdrop_mode, int w1_flags, int flags, char *out_text, size_t text_cap,
+                        int64_t *out_off, size_t *out_needed);
+/* Diagnostics, of the calling thread's most recent call of the two above (ms): sam_len_kernel, sam_write_kernel (0 without
+ * BPSW_SAM_TEXT_DEVICE), building and staging the line table, the round trip of the two kernels with the copies; and of
+ * bpsw_align_se_batch: its bpsw_worker1_batch stage, its bpsw_sam_se_batch stage. */
+void bpsw_last_sam_se_times(double ms[6]);
+
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {
   uint64_t ext_calls, ext_tasks, ext_wire_bytes;
