@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "bpsw_worker1_batch", "bpsw_last_worker1_times", "bpsw_seed_set_resident_lanes",
     "bpsw_chain_batch", "bpsw_chain_set_arena_budget", "bpsw_chain_last_split",
     "bpsw_sam_se_batch", "bpsw_align_se_batch", "bpsw_last_sam_se_times",
+    "bpsw_sam_pe_batch_ex", "bpsw_align_pe_batch", "bpsw_last_sam_pe_times",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -249,6 +250,12 @@ def _bind_seeding(lib):
         "bpsw_align_se_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                  C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)], C.c_int),
         "bpsw_last_sam_se_times": ([C.c_void_p], None),
+        # ... and the paired entries with a flags argument (bpsw_sam_pe.hip)
+        "bpsw_sam_pe_batch_ex": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.POINTER(C.c_size_t), C.c_void_p], C.c_int),
+        "bpsw_align_pe_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p], C.c_int),
+        "bpsw_last_sam_pe_times": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -851,7 +858,7 @@ def _ctx_reg2aln_batch(self, opt: Opt, topt: TailOpt, read_len, read_off, read_p
     return alns[: j.n], cig[: j.n], md[: j.n]
 
 
-def _pairs_struct(g):
+def _pairs_struct(g, with_regs: bool = True):
     st = Pairs()
     st.group_size, st.id0 = g.group_size, g.id0
     for r in range(4):
@@ -860,6 +867,8 @@ def _pairs_struct(g):
     keep = []
     for f, dt in (("read_len", np.int32), ("read_off", np.int64), ("read_pool", np.uint8), ("name_off", np.int64),
                   ("name_pool", np.uint8), ("reg_cnt", np.int32)):
+        if f == "reg_cnt" and not with_regs:
+            continue
         a = np.ascontiguousarray(getattr(g, f), dt)
         keep.append(a)
         setattr(st, f, a.ctypes.data)
@@ -868,6 +877,8 @@ def _pairs_struct(g):
         keep.append(q)
         st.qual_pool = q.ctypes.data
     st.read_pool_bytes = int(np.asarray(g.read_pool).size)
+    if not with_regs:
+        return st, keep, None
     regs = np.ascontiguousarray(g.regs)
     assert regs.dtype == ALNREG_DTYPE
     st.regs = regs.ctypes.data
@@ -875,8 +886,9 @@ def _pairs_struct(g):
     return st, keep, regs
 
 
-def _ctx_sam_pe_batch(self, opt: Opt, topt: TailOpt, g: "TailGroupSoA"):
-    """memSamPeGroupRest -> (list of 2G SAM texts (bytes), regions as the tail leaves them)"""
+def _ctx_sam_pe_batch(self, opt: Opt, topt: TailOpt, g: "TailGroupSoA", flags: int = 0):
+    """memSamPeGroupRest -> (list of 2G SAM texts (bytes), regions as the tail leaves them); flags: SAM_TEXT_DEVICE
+    (bpsw_sam_pe_batch_ex; without flags the call is bpsw_sam_pe_batch itself)"""
     st, keep, regs = _pairs_struct(g)
     off = np.zeros(2 * g.group_size + 1, np.int64)
     out_regs = np.zeros(max(regs.shape[0], 1), ALNREG_DTYPE)
@@ -884,8 +896,12 @@ def _ctx_sam_pe_batch(self, opt: Opt, topt: TailOpt, g: "TailGroupSoA"):
     cap = 1024 * max(1, 2 * g.group_size)
     while True:
         buf = np.empty(cap, np.uint8)   # the library writes off[-1] bytes
-        rc = self.lib.bpsw_sam_pe_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), _ptr(buf), cap, _ptr(off), C.byref(need),
-                                        _ptr(out_regs))
+        if flags:
+            rc = self.lib.bpsw_sam_pe_batch_ex(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, _ptr(buf), cap, _ptr(off), C.byref(need),
+                                               _ptr(out_regs))
+        else:
+            rc = self.lib.bpsw_sam_pe_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), _ptr(buf), cap, _ptr(off), C.byref(need),
+                                            _ptr(out_regs))
         if rc == -3 and need.value > cap:   # BPSW_ERR_CAPACITY
             cap = int(need.value) + 64
             continue
@@ -1047,6 +1063,34 @@ def last_sam_se_times():
     return tuple(ms)
 
 
+def _ctx_align_pe_batch(self, opt: Opt, sopt, topt: "TailOpt", g: "TailGroupSoA", pes0=None, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0,
+                        rescue_mode: int = RESCUE_C, flags: int = 0, text_cap: int | None = None):
+    """paired reads -> (SAM texts (bytes) per read, 2G of them; the insert-size statistics used, 4 x (low, high, failed, avg, std)):
+    worker1_batch with C2A_SORT_DEDUP on the 2G reads, pes0 or pe_stat over their lists, the rescue, the paired tail, in one call.
+    g.reg_cnt, g.regs and g.pes are ignored."""
+    st, keep, _ = _pairs_struct(g, False)
+    pes_in = None
+    if pes0 is not None:
+        pes_in = (PeStat * 4)()
+        for r in range(4):
+            lo, hi, failed, avg, std = pes0[r]
+            pes_in[r].low, pes_in[r].high, pes_in[r].failed, pes_in[r].avg, pes_in[r].std = int(lo), int(hi), int(failed), float(avg), float(std)
+    pes = (PeStat * 4)()
+    texts = _se_text_call(self.lib, "bpsw_align_pe_batch", 2 * g.group_size,
+                          lambda buf, cap, off, need: self.lib.bpsw_align_pe_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
+                                                                                   pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, cap, off,
+                                                                                   need, pes), text_cap)
+    return texts, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)]
+
+
+def last_sam_pe_times():
+    """(sam_len_kernel, sam_write_kernel, line table, text round trip, worker1 stage, statistics, rescue, tail) in ms of this
+    thread's last sam_pe_batch with flags / align_pe_batch"""
+    ms = (C.c_double * 8)()
+    load_library().bpsw_last_sam_pe_times(ms)
+    return tuple(ms)
+
+
 TAIL_POOL_TAIL_ONLY = -1
 
 
@@ -1129,6 +1173,7 @@ Context.last_tail_host_ms = _ctx_last_tail_host_ms
 Context.last_tail_resubmitted = _ctx_last_tail_resubmitted
 Context.sam_se_batch = _ctx_sam_se_batch
 Context.align_se_batch = _ctx_align_se_batch
+Context.align_pe_batch = _ctx_align_pe_batch
 Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute units of the context's device
 
 

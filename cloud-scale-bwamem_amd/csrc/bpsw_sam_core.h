@@ -1,7 +1,9 @@
-// bpsw_sam_core.h -- the bytes of one SAM line without a mate, for the host and for the device.
+// bpsw_sam_core.h -- the bytes of one SAM line, with or without a mate, for the host and for the device.
 //
-// memAlnToSAM (worker2/MemRegToADAMSAM.scala:328-560 == mem_aln2sam, native/bwamem.c:726-838) with m == NULL, as aln_to_sam
-// (bpsw_tail.cpp) writes it on the calling thread; that function stays the yardstick.  Here the same line is a function of a
+// memAlnToSAM (worker2/MemRegToADAMSAM.scala:328-560 == mem_aln2sam, native/bwamem.c:726-838), as aln_to_sam (bpsw_tail.cpp)
+// writes it on the calling thread; that function stays the yardstick.  A line names its mate by one index (SamLine::mate): the
+// FIRST line of the other read of its pair, which is what the paired tail hands memAlnToSAM as `m` in the five fields the line
+// reads of it (rid, pos, is_rev, n_cigar and the CIGAR words); 0 is a line without a mate (m == NULL).  Here the same line is a function of a
 // LINE RECORD (SamLine) and the batch's tables (SamBatch), so that a kernel can write it: sam_line_len counts the bytes,
 // sam_line_write stores them, both through one emitter (emit_line) over a sink that either counts or stores, so the two cannot
 // drift apart.  Every store is checked against `end`; a line that would pass it, or whose byte count differs from what the caller
@@ -10,7 +12,8 @@
 // Numbers are formatted by counting their digits first and storing straight into the destination; the letter tables are packed
 // constants indexed by shifting.  No array of its own is indexed, so the kernels that compile this have no scratch.
 //
-// Compiled by hipcc for sam_len_kernel / sam_write_kernel (bpsw_sam_se.hip) and by g++ for tests/sam_host/sam_host.cpp.
+// Compiled by hipcc for sam_len_kernel / sam_write_kernel (bpsw_sam_se.hip) and by g++ for tests/sam_host/sam_host.cpp and
+// tests/sam_pe_host/sam_pe_host.cpp.
 #pragma once
 
 #include <stdint.h>
@@ -36,7 +39,7 @@ struct SamLine {  // one line: the mem_aln_t of memRegToAln after memRegToSAMSe'
   int32_t first;       // the first line of that read in SamBatch::lines ...
   int32_t n_list;      // ... and how many it has (the SA:Z list runs over them)
   int32_t rid, flag, is_rev, mapq, NM, n_cigar, md_len, score, sub;
-  int32_t pad_;
+  int32_t mate;        // the first line of the other read of its pair in SamBatch::lines, + 1; 0: no mate
 };
 static_assert(sizeof(SamLine) == 80, "the line record is staged as it is");
 
@@ -113,6 +116,11 @@ template <class S> BPSW_SAM_HD void put_contig(S& s, const SamBatch& B, int rid)
 }
 
 BPSW_SAM_HD bool is_clip(uint32_t w) { return (w & 0xf) == 3 || (w & 0xf) == 4; }
+BPSW_SAM_HD int ref_len(const uint32_t* cig, int n) {  // getRlen: the bases of the reference under M and D
+  int l = 0;
+  for (int k = 0; k < n; ++k) { const int op = (int)(cig[k] & 0xf); if (op == 0 || op == 2) l += (int)(cig[k] >> 4); }
+  return l;
+}
 
 template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line) {
   const SamLine& L = B.lines[line];
@@ -120,23 +128,40 @@ template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line)
   const int which = line - L.first;
   const uint32_t* cig = B.cig + L.cig_at;
   int flag = L.flag;
-  if (L.rid < 0) flag |= 0x4;
-  if (L.is_rev) flag |= 0x10;
+  // the line's and the mate's place; an unmapped one of the two is put where the other is
+  int rid = L.rid, is_rev = L.is_rev, n_cigar = L.n_cigar;
+  long long pos = L.pos;
+  const bool has_m = L.mate > 0;
+  int m_rid = -1, m_is_rev = 0, m_n_cigar = 0;
+  long long m_pos = -1;
+  const uint32_t* m_cig = B.cig;
+  if (has_m) {
+    const SamLine& M = B.lines[L.mate - 1];
+    m_rid = M.rid; m_is_rev = M.is_rev; m_n_cigar = M.n_cigar; m_pos = M.pos;
+    m_cig = B.cig + M.cig_at;
+    flag |= 0x1;
+  }
+  if (rid < 0) flag |= 0x4;
+  if (has_m && m_rid < 0) flag |= 0x8;
+  if (rid < 0 && has_m && m_rid >= 0) { rid = m_rid; pos = m_pos; is_rev = m_is_rev; n_cigar = 0; }
+  if (has_m && m_rid < 0 && rid >= 0) { m_rid = rid; m_pos = pos; m_is_rev = is_rev; m_n_cigar = 0; }
+  if (is_rev) flag |= 0x10;
+  if (has_m && m_is_rev) flag |= 0x20;
   put_bytes(s, B.names + R.name_at, R.name_len);
   put_char(s, '\t');
   const int folded = (flag & 0xffff) | ((flag & 0x10000) ? 0x100 : 0);
   if (B.flavour == FLAVOUR_SCALA) flag = folded;  // the Scala assigns the folded flag, the C only prints it
   put_num(s, folded);
   put_char(s, '\t');
-  if (L.rid >= 0) {
-    put_contig(s, B, L.rid);
+  if (rid >= 0) {
+    put_contig(s, B, rid);
     put_char(s, '\t');
-    put_num(s, L.pos + 1);
+    put_num(s, pos + 1);
     put_char(s, '\t');
     put_num(s, L.mapq);
     put_char(s, '\t');
-    if (L.n_cigar > 0) {
-      for (int i = 0; i < L.n_cigar; ++i) {
+    if (n_cigar > 0) {
+      for (int i = 0; i < n_cigar; ++i) {
         int c = (int)(cig[i] & 0xf);
         if (c == 3 || c == 4) c = which ? 4 : 3;  // hard clipping on every line but the read's first
         put_num(s, (long long)(cig[i] >> 4));
@@ -148,15 +173,31 @@ template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line)
   } else {
     put_bytes(s, "*\t0\t0\t*", 7);
   }
-  put_bytes(s, "\t*\t0\t0\t", 7);  // no mate
+  put_char(s, '\t');
+  if (has_m && m_rid >= 0) {
+    if (rid == m_rid) put_char(s, '='); else put_contig(s, B, m_rid);
+    put_char(s, '\t');
+    put_num(s, m_pos + 1);
+    put_char(s, '\t');
+    if (rid == m_rid && m_n_cigar > 0 && n_cigar > 0) {  // the distance between the two 5' ends
+      const long long p0 = pos + (is_rev ? ref_len(cig, n_cigar) - 1 : 0);
+      const long long p1 = m_pos + (m_is_rev ? ref_len(m_cig, m_n_cigar) - 1 : 0);
+      put_num(s, -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
+    } else {
+      put_char(s, '0');
+    }
+  } else {
+    put_bytes(s, "*\t0\t0", 5);
+  }
+  put_char(s, '\t');
   if (flag & 0x100) {
     put_bytes(s, "*\t*", 3);
   } else {
     int qb = 0, qe = R.len;
-    const int nc = L.n_cigar;
+    const int nc = n_cigar;
     const bool clip_first = nc > 0 && is_clip(cig[0]), clip_last = nc > 0 && is_clip(cig[nc - 1]);
     const uint8_t* seq = B.seq + R.seq_at;
-    if (!L.is_rev) {
+    if (!is_rev) {
       if (which && clip_first) qb += (int)(cig[0] >> 4);
       if (which && clip_last) qe -= (int)(cig[nc - 1] >> 4);
     } else {
@@ -166,19 +207,19 @@ template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line)
     const long long n = qe > qb ? qe - qb : 0;
     char* d = s.take(n + 1 + (B.qual ? n : 1));  // bases, tab, qualities
     if (d) {
-      if (!L.is_rev) for (long long i = 0; i < n; ++i) d[i] = base_fwd(seq[qb + i]);
+      if (!is_rev) for (long long i = 0; i < n; ++i) d[i] = base_fwd(seq[qb + i]);
       else for (long long i = 0; i < n; ++i) d[i] = base_rev(seq[qe - 1 - i]);
       d[n] = '\t';
       if (!B.qual) {
         d[n + 1] = '*';
       } else {
         const uint8_t* q = B.qual + R.seq_at;
-        if (!L.is_rev) for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qb + i];
+        if (!is_rev) for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qb + i];
         else for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qe - 1 - i];
       }
     }
   }
-  if (L.n_cigar > 0) {
+  if (n_cigar > 0) {
     put_bytes(s, "\tNM:i:", 6);
     put_num(s, L.NM);
     put_bytes(s, "\tMD:Z:", 6);

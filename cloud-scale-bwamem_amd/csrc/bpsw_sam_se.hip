@@ -5,11 +5,12 @@
 // then mem_reg2sam_se with extra_flag = 0 and no mate (native/bwamem.c:879-892, R2S:67-118).  The pieces are bpsw_tail.cpp's
 // (bpsw_tail_internal.h): mark_primary, run_jobs over reg2aln_kernel, make_aln, and aln_to_sam for the text on the calling thread.
 //
-// With BPSW_SAM_TEXT_DEVICE the text is written by two kernels over bpsw_sam_core.h, the byte definition of a line without a mate:
+// With BPSW_SAM_TEXT_DEVICE the text is written by two kernels over bpsw_sam_core.h, the byte definition of a line (the paired
+// entries of bpsw_sam_pe.hip go through the same two, text_on_device, with every line naming its mate):
 //   sam_len_kernel    one line per lane: the line's number of bytes; the host sums them to line offsets, per-read out_off and
 //                     the total (a total past text_cap ends the call there);
 //   sam_write_kernel  one line per lane: the line's bytes at its offset in one device block, which comes back with one copy.
-// A line depends on its read's lines only (the SA:Z list), so a lane needs nothing of another read.  Into the kernels go, as one
+// A line depends on its read's lines (the SA:Z list) and, in a pair, on the first line of the other read; it reads both from the table.  Into the kernels go, as one
 // staged block, the line table built on the host from make_aln's results (fixed-size records, each line's CIGAR words and MD
 // bytes), the read records with the base, quality and name pools, the contig names and the read-group ID.
 #include <string.h>
@@ -66,11 +67,13 @@ int check_reads(const char* who, const bpsw_se_reads_t* g, bool need_regs, size_
   return BPSW_OK;
 }
 
-// The text of the lines in `lines` (per read: aa[read_first[r] .. read_first[r + 1])) through the two kernels.  Caller holds c->mu.
-int text_on_device(bpsw_ctx* c, const BnsView& bns, const bpsw_tail_opt_t& t, const bpsw_se_reads_t* g, const std::vector<Aln>& aa,
-                   const std::vector<int32_t>& line_read, const std::vector<int32_t>& read_first, const JobResults& R, char* out_text,
-                   size_t text_cap, int64_t* out_off, size_t* total_out) {
-  const int n = g->n_reads, n_lines = (int)aa.size();
+}  // namespace
+
+int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const std::vector<Aln>& aa,
+                         const std::vector<int32_t>& line_read, const std::vector<int32_t>& read_first, const Aln* mate, const JobResults& R,
+                         char* out_text, size_t text_cap, int64_t* out_off, size_t* total_out, double times[4]) {
+  const int n = g.n, n_lines = (int)aa.size(), n_names = g.n >> g.name_shift;
+  const std::string w(who);
   const double t0 = wall_ms();
   // ---- the line table -------------------------------------------------------------------------------------------------------
   std::vector<sc::SamLine> lines((size_t)n_lines);
@@ -85,17 +88,28 @@ int text_on_device(bpsw_ctx* c, const BnsView& bns, const bpsw_tail_opt_t& t, co
     L.read = r; L.first = read_first[(size_t)r]; L.n_list = read_first[(size_t)r + 1] - read_first[(size_t)r];
     L.rid = x.a.rid; L.flag = x.a.flag; L.is_rev = x.a.is_rev; L.mapq = x.a.mapq; L.NM = x.a.NM; L.n_cigar = x.a.n_cigar;
     L.md_len = x.a.md_len; L.score = x.a.score; L.sub = x.a.sub;
+    if (mate) L.mate = read_first[(size_t)(r ^ 1)] + 1;
+  }
+  if (mate) {  // a line finds its mate as the first line of the other read: what it reads of it must be what the tail would hand over
+    for (int r = 0; r < n; ++r) {
+      const Aln& m = mate[r];
+      const Aln& f = aa[(size_t)read_first[(size_t)(r ^ 1)]];
+      const bool same_cigar = m.a.n_cigar == f.a.n_cigar && (m.a.n_cigar <= 0 || m.cigar == f.cigar || !memcmp(m.cigar, f.cigar, 4 * (size_t)m.a.n_cigar));
+      if (m.a.rid != f.a.rid || m.a.pos != f.a.pos || m.a.is_rev != f.a.is_rev || !same_cigar)
+        return fail(BPSW_ERR_DEVICE, w + ": a read's mate record is not the first line of the other read");
+    }
   }
   // the reads' bytes: the covering span of the base pool (and of the quality pool, same offsets), the names' span
-  long long lo = (long long)g->read_pool_bytes, hi = 0;
-  for (int r = 0; r < n; ++r) { lo = std::min<long long>(lo, g->read_off[r]); hi = std::max<long long>(hi, g->read_off[r] + g->read_len[r]); }
-  const long long name_lo = g->name_off[0], name_hi = g->name_off[n];
+  long long lo = (long long)g.read_pool_bytes, hi = 0;
+  for (int r = 0; r < n; ++r) { lo = std::min<long long>(lo, g.read_off[r]); hi = std::max<long long>(hi, g.read_off[r] + g.read_len[r]); }
+  const long long name_lo = g.name_off[0], name_hi = g.name_off[n_names];
   std::vector<sc::SamRead> reads((size_t)n);
   for (int r = 0; r < n; ++r) {
-    reads[(size_t)r].seq_at = g->read_off[r] - lo;
-    reads[(size_t)r].name_at = g->name_off[r] - name_lo;
-    reads[(size_t)r].len = g->read_len[r];
-    reads[(size_t)r].name_len = (int32_t)(g->name_off[r + 1] - g->name_off[r]);
+    const int k = r >> g.name_shift;
+    reads[(size_t)r].seq_at = g.read_off[r] - lo;
+    reads[(size_t)r].name_at = g.name_off[k] - name_lo;
+    reads[(size_t)r].len = g.read_len[r];
+    reads[(size_t)r].name_len = (int32_t)(g.name_off[k + 1] - g.name_off[k]);
   }
   std::vector<int32_t> ctg_at(bns.name.size() + 1, 0);
   std::vector<char> ctg_names;
@@ -108,9 +122,9 @@ int text_on_device(bpsw_ctx* c, const BnsView& bns, const bpsw_tail_opt_t& t, co
   StageIn in;
   const int i_lines = in.add(lines.data(), sizeof(sc::SamLine) * (size_t)n_lines), i_reads = in.add(reads.data(), sizeof(sc::SamRead) * (size_t)n);
   const int i_cig = in.add(R.cig.data(), 4 * R.cig.size()), i_md = in.add(R.md.data(), R.md.size());
-  const int i_seq = in.add(g->read_pool + lo, (size_t)(hi - lo));
-  const int i_qual = g->qual_pool ? in.add(g->qual_pool + lo, (size_t)(hi - lo)) : -1;
-  const int i_names = in.add(g->name_pool + name_lo, (size_t)(name_hi - name_lo));
+  const int i_seq = in.add(g.read_pool + lo, (size_t)(hi - lo));
+  const int i_qual = g.qual_pool ? in.add(g.qual_pool + lo, (size_t)(hi - lo)) : -1;
+  const int i_names = in.add(g.name_pool + name_lo, (size_t)(name_hi - name_lo));
   const int i_cat = in.add(ctg_at.data(), 4 * ctg_at.size()), i_cnm = in.add(ctg_names.data(), ctg_names.size());
   const int i_rg = in.add(t.rg_id, rg_len);
   StageOut lens;
@@ -139,15 +153,15 @@ int text_on_device(bpsw_ctx* c, const BnsView& bns, const bpsw_tail_opt_t& t, co
   std::vector<long long> line_off((size_t)n_lines + 1, 0);
   const int32_t* hl = lens.host<int32_t>(r_len);
   for (int i = 0; i < n_lines; ++i) {
-    if (hl[i] < 1) return fail(BPSW_ERR_DEVICE, "sam_se: a line came back with no length");
+    if (hl[i] < 1) return fail(BPSW_ERR_DEVICE, w + ": a line came back with no length");
     line_off[(size_t)i + 1] = line_off[(size_t)i] + hl[i];
   }
   for (int r = 0; r <= n; ++r) out_off[r] = (int64_t)line_off[(size_t)read_first[(size_t)r]];
   const size_t total = (size_t)line_off[(size_t)n_lines];
   *total_out = total;
-  t_last[0] = ms_len; t_last[1] = 0.; t_last[2] = t1 - t0;
+  times[0] = ms_len; times[1] = 0.; times[2] = t1 - t0;
   const double t2 = wall_ms();
-  if (!out_text || total > text_cap) { t_last[3] = t2 - t1; return BPSW_OK; }  // (the caller reports the capacity)
+  if (!out_text || total > text_cap) { times[3] = t2 - t1; return BPSW_OK; }  // (the caller reports the capacity)
   // ---- text ------------------------------------------------------------------------------------------------------------------
   // (the pinned input block is free again: its copy has been waited for; the line table stays where it is on the device)
   StageIn io;
@@ -166,14 +180,12 @@ int text_on_device(bpsw_ctx* c, const BnsView& bns, const bpsw_tail_opt_t& t, co
   HIP_TRY(hipStreamSynchronize(c->stream));
   float ms_write = 0.f;
   (void)hipEventElapsedTime(&ms_write, c->ev[6], c->ev[7]);
-  t_last[1] = ms_write;
-  if (*txt.host<int>(r_status)) return fail(BPSW_ERR_DEVICE, "sam_se: a line's bytes differ in number from its length (sam_line_write's status)");
+  times[1] = ms_write;
+  if (*txt.host<int>(r_status)) return fail(BPSW_ERR_DEVICE, w + ": a line's bytes differ in number from its length (sam_line_write's status)");
   memcpy(out_text, txt.host<char>(r_text), total);
-  t_last[3] = wall_ms() - t1;
+  times[3] = wall_ms() - t1;
   return BPSW_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -261,7 +273,10 @@ int bpsw_sam_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
   }
   size_t total = 0;
   if (flags & BPSW_SAM_TEXT_DEVICE) {
-    rc = text_on_device(c, bns, t, g, aa, line_read, read_first, R, out_text, text_cap, out_off, &total);
+    TextReads tr;
+    tr.n = n; tr.read_len = g->read_len; tr.read_off = g->read_off; tr.read_pool = g->read_pool; tr.qual_pool = g->qual_pool;
+    tr.read_pool_bytes = g->read_pool_bytes; tr.name_off = g->name_off; tr.name_pool = g->name_pool;
+    rc = text_on_device(c, "sam_se", bns, t, tr, aa, line_read, read_first, nullptr, R, out_text, text_cap, out_off, &total, t_last);
     if (rc != BPSW_OK) return rc;
   } else {
     Text text(out_text, text_cap);

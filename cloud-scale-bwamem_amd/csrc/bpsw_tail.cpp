@@ -618,42 +618,41 @@ int bpsw_reg2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt
   return BPSW_OK;
 }
 
-int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, char* out_text,
-                      size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
-  if (!c || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "sam_pe: null argument");
-  SwScoring sc;
-  int rc = make_scoring("tail", opt, 0, 1, &sc);
-  if (rc != BPSW_OK) return rc;
+// ---- the paired tail in pieces (bpsw_tail_internal.h): checks, plan + jobs + line lists, the text on the calling thread, the end ----
+int bpsw::pe_check(const char* who, const bpsw_pairs_t* g, size_t* n_regs) {
   const int G = g->group_size;
-  if (G < 0) return fail(BPSW_ERR_ARG, "sam_pe: negative group size");
-  if (G == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
-  if (!g->read_len || !g->read_off || !g->read_pool || !g->name_off || !g->name_pool || !g->reg_cnt) return fail(BPSW_ERR_ARG, "sam_pe: null group arrays");
-  size_t n_regs = 0;
+  const std::string w(who);
+  if (!g->read_len || !g->read_off || !g->read_pool || !g->name_off || !g->name_pool || !g->reg_cnt) return fail(BPSW_ERR_ARG, w + ": null group arrays");
+  *n_regs = 0;
   for (int r = 0; r < 2 * G; ++r) {
-    if (g->reg_cnt[r] < 0) return fail(BPSW_ERR_ARG, "sam_pe: negative region count");
+    if (g->reg_cnt[r] < 0) return fail(BPSW_ERR_ARG, w + ": negative region count");
     if (g->read_len[r] < 1 || g->read_off[r] < 0 || (unsigned long long)(g->read_off[r] + g->read_len[r]) > g->read_pool_bytes)
-      return fail(BPSW_ERR_ARG, "sam_pe: read outside its pool (or empty)");
-    n_regs += (size_t)g->reg_cnt[r];
+      return fail(BPSW_ERR_ARG, w + ": read outside its pool (or empty)");
+    *n_regs += (size_t)g->reg_cnt[r];
   }
-  if (n_regs && !g->regs) return fail(BPSW_ERR_ARG, "sam_pe: null region array");
-  ContextEntry entry(c);
-  if (entry.rc != BPSW_OK) return entry.rc;
-  BnsView bns;
-  rc = snapshot_bns(c, &bns);
-  if (rc != BPSW_OK) return rc;
+  if (*n_regs && !g->regs) return fail(BPSW_ERR_ARG, w + ": null region array");
+  return BPSW_OK;
+}
+
+namespace {
+struct PlanScratch {
+  std::vector<std::vector<bpsw_alnreg_t> > regs;
+  std::vector<PairPlan> plan;
+  std::vector<int32_t> job_len;
+  std::vector<int64_t> job_off;
+  std::vector<bpsw_alnreg_t> job_reg;
+};
+}  // namespace
+
+int bpsw::pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g,
+                   const BnsView& bns, PeLines* out) {
+  const int G = g->group_size;
   const bpsw_opt_t& o = *opt;
   const bpsw_tail_opt_t& t = *topt;
 
   // ---- plan -----------------------------------------------------------------------------------------------------------
   c->last_tail_ms = 0.f; c->last_tail_jobs = 0; c->last_tail_resubmitted = 0;
-  const double t_plan = wall_ms();
-  struct PlanScratch {
-    std::vector<std::vector<bpsw_alnreg_t> > regs;
-    std::vector<PairPlan> plan;
-    std::vector<int32_t> job_len;
-    std::vector<int64_t> job_off;
-    std::vector<bpsw_alnreg_t> job_reg;
-  };
+  out->t_plan = wall_ms();
   static thread_local PlanScratch scratch;  // 2 G + G vectors, re-filled in place: their heap blocks are reused from call to call
   std::vector<std::vector<bpsw_alnreg_t> >& regs = scratch.regs;
   std::vector<PairPlan>& plan = scratch.plan;
@@ -728,24 +727,25 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
   static thread_local JobResults results;  // (the scratch of a call is kept per calling thread: no allocation in the steady state)
   JobResults& R = results;
   std::vector<JobResult>& res = R.r;
-  const double t_dev = wall_ms();
-  rc = run_jobs(c, sc, opt, t.flavour, bns, job_len, job_off, g->read_pool, g->read_pool_bytes, job_reg, &R);
+  out->t_dev = wall_ms();
+  int rc = run_jobs(c, sc, opt, t.flavour, bns, job_len, job_off, g->read_pool, g->read_pool_bytes, job_reg, &R);
   if (rc != BPSW_OK) return rc;
   for (size_t j = 0; j < res.size(); ++j)
     if (res[j].k.status == BPSW_ALN_XREF || res[j].k.status == BPSW_ALN_OVERFLOW)
       return fail(BPSW_ERR_LIMIT, res[j].k.status == BPSW_ALN_XREF ? "sam_pe: bwaFixXref2 could not repair a region (the reference aborts here)"
                                                                    : "sam_pe: an alignment has more CIGAR operations than the kernel stages");
 
-  // ---- emit ---------------------------------------------------------------------------------------------------------------
-  const double t_emit = wall_ms();
-  Text text(out_text, text_cap);
+  // ---- the lines of every read, and the record each read's lines are printed against (the mate, `m` of memAlnToSAM) ----------------
+  out->t_emit = wall_ms();
+  out->R = &R;
+  out->regs = regs.data();
+  std::vector<Aln>& aa = out->aa;
+  aa.clear(); out->line_read.clear();
+  out->read_first.assign((size_t)(2 * G) + 1, 0);
+  out->mate.resize((size_t)(2 * G));
   for (int k = 0; k < G; ++k) {
     const PairPlan& P = plan[(size_t)k];
     const std::vector<bpsw_alnreg_t>* a = &regs[(size_t)(2 * k)];
-    const char* name = g->name_pool + g->name_off[k];
-    const size_t name_len = (size_t)(g->name_off[k + 1] - g->name_off[k]);
-    const uint8_t* seq[2] = {g->read_pool + g->read_off[2 * k], g->read_pool + g->read_off[2 * k + 1]};
-    const uint8_t* qual[2] = {g->qual_pool ? g->qual_pool + g->read_off[2 * k] : nullptr, g->qual_pool ? g->qual_pool + g->read_off[2 * k + 1] : nullptr};
     Aln h[2];
     if (P.paired) {
       for (int i = 0; i < 2; ++i) {
@@ -755,8 +755,10 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
         h[i].a.flag |= (i ? 0x80 : 0x40) | P.extra_flag;
       }
       for (int i = 0; i < 2; ++i) {
-        out_off[2 * k + i] = (int64_t)text.size();
-        aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[2 * k + i], seq[i], qual[i], &h[i], 1, 0, &h[1 - i], t.rg_id);
+        aa.push_back(h[i]);
+        out->mate[(size_t)(2 * k + i)] = h[1 - i];
+        out->line_read.push_back(2 * k + i);
+        out->read_first[(size_t)(2 * k + i) + 1] = (int32_t)aa.size();
       }
       continue;
     }
@@ -771,9 +773,8 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
       if (!g->pes[d].failed && dist >= g->pes[d].low && dist <= g->pes[d].high) extra_flag |= 2;
     }
     for (int i = 0; i < 2; ++i) {
-      out_off[2 * k + i] = (int64_t)text.size();
       const int xf = (i ? 0x81 : 0x41) | extra_flag;
-      std::vector<Aln> aa;
+      const size_t first = aa.size();
       for (size_t x = 0; x < P.end[i].se_jobs.size(); ++x) {
         const int j = P.end[i].se_jobs[x].first, jb = P.end[i].se_jobs[x].second;
         const bpsw_alnreg_t& p = a[i][(size_t)j];
@@ -781,29 +782,81 @@ int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_
         q.a.flag |= xf;
         if (p.secondary >= 0) q.a.sub = -1;  // don't output the sub-optimal score
         if (j && p.secondary < 0) q.a.flag |= (o.flag & BPSW_MEM_F_NO_MULTI) ? 0x10000 : 0x800;  // supplementary
-        if (j && !aa.empty() && q.a.mapq > aa[0].a.mapq) q.a.mapq = aa[0].a.mapq;
+        if (j && aa.size() > first && q.a.mapq > aa[first].a.mapq) q.a.mapq = aa[first].a.mapq;
         aa.push_back(q);
       }
-      if (aa.empty()) {
+      if (aa.size() == first) {
         Aln u = make_aln(o, t, nullptr, nullptr, R);
         u.a.flag |= xf;
         aa.push_back(u);
-        aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[2 * k + i], seq[i], qual[i], aa.data(), aa.size(), 0, &h[1 - i], t.rg_id);
-      } else {
-        for (size_t x = 0; x < aa.size(); ++x)
-          aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[2 * k + i], seq[i], qual[i], aa.data(), aa.size(), (int)x, &h[1 - i], t.rg_id);
       }
+      out->mate[(size_t)(2 * k + i)] = h[1 - i];
+      out->line_read.resize(aa.size(), 2 * k + i);
+      out->read_first[(size_t)(2 * k + i) + 1] = (int32_t)aa.size();
     }
   }
+  return BPSW_OK;
+}
+
+// the text on the calling thread: every line through aln_to_sam against its read's mate record
+size_t bpsw::pe_print(const PeLines& L, const BnsView& bns, const bpsw_tail_opt_t& t, const bpsw_pairs_t* g, char* out_text, size_t text_cap,
+                      int64_t* out_off) {
+  const int G = g->group_size;
+  Text text(out_text, text_cap);
+  for (int r = 0; r < 2 * G; ++r) {
+    const int k = r >> 1;
+    const char* name = g->name_pool + g->name_off[k];
+    const size_t name_len = (size_t)(g->name_off[k + 1] - g->name_off[k]);
+    const uint8_t* seq = g->read_pool + g->read_off[r];
+    const uint8_t* qual = g->qual_pool ? g->qual_pool + g->read_off[r] : nullptr;
+    const Aln* list = L.aa.data() + L.read_first[(size_t)r];
+    const size_t n_list = (size_t)(L.read_first[(size_t)r + 1] - L.read_first[(size_t)r]);
+    out_off[r] = (int64_t)text.size();
+    for (size_t x = 0; x < n_list; ++x)
+      aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[r], seq, qual, list, n_list, (int)x, &L.mate[(size_t)r], t.rg_id);
+  }
   out_off[2 * G] = (int64_t)text.size();
+  return text.size();
+}
+
+int bpsw::pe_finish(bpsw_ctx* c, const PeLines& L, const bpsw_pairs_t* g, const char* out_text, size_t text_cap, size_t total,
+                    size_t* out_needed, bpsw_alnreg_t* out_regs) {
   if (out_regs) {
     size_t w = 0;
-    for (int r = 0; r < 2 * G; ++r) { if (!regs[(size_t)r].empty()) memcpy(out_regs + w, regs[(size_t)r].data(), sizeof(bpsw_alnreg_t) * regs[(size_t)r].size()); w += regs[(size_t)r].size(); }
+    for (int r = 0; r < 2 * g->group_size; ++r) {
+      const std::vector<bpsw_alnreg_t>& v = L.regs[(size_t)r];
+      if (!v.empty()) memcpy(out_regs + w, v.data(), sizeof(bpsw_alnreg_t) * v.size());
+      w += v.size();
+    }
   }
-  c->tail_host_ms[0] = t_dev - t_plan; c->tail_host_ms[1] = t_emit - t_dev; c->tail_host_ms[2] = wall_ms() - t_emit;
-  if (out_needed) *out_needed = text.size();
-  if (!out_text || text.size() > text_cap) return fail(BPSW_ERR_CAPACITY, "sam_pe: text buffer too small (see *out_needed)");
+  c->tail_host_ms[0] = L.t_dev - L.t_plan; c->tail_host_ms[1] = L.t_emit - L.t_dev; c->tail_host_ms[2] = wall_ms() - L.t_emit;
+  if (out_needed) *out_needed = total;
+  if (!out_text || total > text_cap) return fail(BPSW_ERR_CAPACITY, "sam_pe: text buffer too small (see *out_needed)");
   return BPSW_OK;
+}
+
+int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, char* out_text,
+                      size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
+  if (!c || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "sam_pe: null argument");
+  SwScoring sc;
+  int rc = make_scoring("tail", opt, 0, 1, &sc);
+  if (rc != BPSW_OK) return rc;
+  const int G = g->group_size;
+  if (G < 0) return fail(BPSW_ERR_ARG, "sam_pe: negative group size");
+  if (G == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
+  size_t n_regs = 0;
+  rc = pe_check("sam_pe", g, &n_regs);
+  if (rc != BPSW_OK) return rc;
+  ContextEntry entry(c);
+  if (entry.rc != BPSW_OK) return entry.rc;
+  BnsView bns;
+  rc = snapshot_bns(c, &bns);
+  if (rc != BPSW_OK) return rc;
+  static thread_local PeLines lines;  // (its vectors are refilled in place from call to call)
+  rc = pe_lines(c, sc, opt, topt, g, bns, &lines);
+  if (rc != BPSW_OK) return rc;
+  const size_t total = pe_print(lines, bns, *topt, g, out_text, text_cap, out_off);
+  return pe_finish(c, lines, g, out_text, text_cap, total, out_needed, out_regs);
 }
 
 // ---- host-only exports (no device) -------------------------------------------------------------------------------------------
@@ -900,22 +953,19 @@ int bpsw_pe_stat(const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, int64_t l_p
 // memSamPeGroupJNIPrepare (PE:1895-2000) with getAlnRegRefJNI (PE:1810-1878) in coordinate form: per end the regions within
 // penUnpaired of the best one (at most maxMatesw) are anchors, each with the four orientation windows of the mate; then
 // bpsw_matesw_group (windows read from the resident reference), then bpsw_sam_pe_batch on the rescued lists.
-int bpsw_worker2_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, int rescue_mode,
-                       char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, int32_t* out_reg_cnt,
-                       bpsw_alnreg_t* out_regs, int64_t out_regs_cap, int64_t* out_regs_total) {
-  if (!c || !opt || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "worker2: null argument");
+int bpsw::pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const bpsw_pairs_t* g, int rescue_mode, std::vector<int32_t>* out_cnt,
+                    std::vector<bpsw_alnreg_t>* out_regs, int64_t* out_total) {
   const int G = g->group_size;
-  if (G < 0) return fail(BPSW_ERR_ARG, "worker2: negative group size");
-  if (G > 0 && (!g->read_len || !g->read_off || !g->read_pool || !g->reg_cnt)) return fail(BPSW_ERR_ARG, "worker2: null group arrays");
+  const std::string w(who);
   const long long l_pac = (long long)bpsw_ref_length(c);
-  if (l_pac <= 0) return fail(BPSW_ERR_ARG, "worker2: no reference loaded on this device (bpsw_ref_load)");
+  if (l_pac <= 0) return fail(BPSW_ERR_ARG, w + ": no reference loaded on this device (bpsw_ref_load)");
   // ---- prepare: anchors and their windows ----------------------------------------------------------------------------------
   std::vector<int32_t> ref_cnt((size_t)(2 * G), 0);
   std::vector<int64_t> ref_rb, ref_re;
   size_t at = 0, n_in = 0;
   for (int e = 0; e < 2 * G; ++e) {
     const int n = g->reg_cnt[e];
-    if (n < 0) return fail(BPSW_ERR_ARG, "worker2: negative region count");
+    if (n < 0) return fail(BPSW_ERR_ARG, w + ": negative region count");
     const bpsw_alnreg_t* a = g->regs + at;
     const int mate_len = g->read_len[e ^ 1];
     int cnt = 0;
@@ -953,14 +1003,31 @@ int bpsw_worker2_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt
   static const int64_t kNone = 0;
   rg.ref_rb = ref_rb.empty() ? &kNone : ref_rb.data(); rg.ref_re = ref_re.empty() ? &kNone : ref_re.data();
   rg.ref_len = nullptr; rg.ref_off = nullptr; rg.ref_pool = nullptr; rg.ref_pool_bytes = 0;  // coordinate windows
-  std::vector<int32_t> cnt2((size_t)(2 * G) + 1, 0);
-  std::vector<bpsw_alnreg_t> regs2(n_in + 4 * ref_rb.size() / 4 * 4 + 16);
+  std::vector<int32_t>& cnt2 = *out_cnt;
+  std::vector<bpsw_alnreg_t>& regs2 = *out_regs;
+  cnt2.assign((size_t)(2 * G) + 1, 0);
+  regs2.resize(n_in + 4 * ref_rb.size() / 4 * 4 + 16);
   int64_t total = 0;
   int rc = bpsw_matesw_group(c, opt, &rg, rescue_mode, cnt2.data(), regs2.data(), (int64_t)regs2.size(), &total);
   if (rc == BPSW_ERR_CAPACITY) {
     regs2.resize((size_t)total + 16);
     rc = bpsw_matesw_group(c, opt, &rg, rescue_mode, cnt2.data(), regs2.data(), (int64_t)regs2.size(), &total);
   }
+  *out_total = total;
+  return rc;
+}
+
+int bpsw_worker2_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, int rescue_mode,
+                       char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, int32_t* out_reg_cnt,
+                       bpsw_alnreg_t* out_regs, int64_t out_regs_cap, int64_t* out_regs_total) {
+  if (!c || !opt || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "worker2: null argument");
+  const int G = g->group_size;
+  if (G < 0) return fail(BPSW_ERR_ARG, "worker2: negative group size");
+  if (G > 0 && (!g->read_len || !g->read_off || !g->read_pool || !g->reg_cnt)) return fail(BPSW_ERR_ARG, "worker2: null group arrays");
+  std::vector<int32_t> cnt2;
+  std::vector<bpsw_alnreg_t> regs2;
+  int64_t total = 0;
+  int rc = pe_rescue(c, "worker2", opt, g, rescue_mode, &cnt2, &regs2, &total);
   if (rc != BPSW_OK) return rc;
   // ---- tail ------------------------------------------------------------------------------------------------------------------
   bpsw_pairs_t t = *g;

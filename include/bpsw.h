@@ -567,7 +567,8 @@ int bpsw_last_tail_resubmitted(bpsw_ctx_t *ctx, int32_t *n_resubmitted);
  * bpsw_last_tail_times as the paired tail does.
  *
  * flags: with BPSW_SAM_TEXT_DEVICE the text is written by two kernels (the length of every line, then its bytes, one line per
- * lane) and comes back in one copy; the bytes are the same.  Default: on the calling thread, as in the paired tail.
+ * lane) and comes back in one copy; the bytes are the same.  Default: on the calling thread, as in the paired tail (which has
+ * the same flag in bpsw_sam_pe_batch_ex, below).
  *
  * bpsw_align_se_batch is FastMap.scala:624-625 in one call: bpsw_worker1_batch with w1_flags | BPSW_C2A_SORT_DEDUP and zdrop_mode
  * (its capacity retry handled inside), then bpsw_sam_se_batch on the lists it got (g->reg_cnt / g->regs are ignored).  Needs the
@@ -596,6 +597,33 @@ int bpsw_align_se_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_
  * BPSW_SAM_TEXT_DEVICE), building and staging the line table, the round trip of the two kernels with the copies; and of
  * bpsw_align_se_batch: its bpsw_worker1_batch stage, its bpsw_sam_se_batch stage. */
 void bpsw_last_sam_se_times(double ms[6]);
+
+/* ---- paired-end reads to SAM (bpsw_sam_pe.hip) ------------------------------------------------------------------------------
+ *
+ * bpsw_sam_pe_batch_ex is bpsw_sam_pe_batch with a flags argument.  flags == 0 IS bpsw_sam_pe_batch.  With BPSW_SAM_TEXT_DEVICE
+ * the text is written by the two kernels of the single-end text (the length of every line, then its bytes, one line per lane):
+ * every line carries the index of the first line of its pair's other read, from which the kernels take what memAlnToSAM reads of
+ * the mate -- contig, position, strand and the CIGAR's length on the reference, for the flag bits 0x8 / 0x20, the position an
+ * unmapped end is placed at, RNEXT, PNEXT and TLEN.  The bytes are the same.  The contract is bpsw_sam_pe_batch's: out_off
+ * (2 * group_size + 1), *out_needed with BPSW_ERR_CAPACITY (nothing written past text_cap, out_off complete), BPSW_ERR_LIMIT,
+ * group_size == 0, out_regs, bpsw_last_tail_times.  A flag other than BPSW_SAM_TEXT_DEVICE is BPSW_ERR_ARG.
+ *
+ * bpsw_align_pe_batch is mem_process_seqs under MEM_F_PE (native/bwamem.c:1064-1083 == FastMap.scala:262-307 and :352-395) for a
+ * batch of pairs, in one call: bpsw_worker1_batch on the 2 * group_size reads with w1_flags | BPSW_C2A_SORT_DEDUP and zdrop_mode
+ * (its capacity retry handled inside); the insert-size statistics -- pes0[4] when given (the reference's pes0), else bpsw_pe_stat
+ * over this batch's lists -- returned through out_pes[4] when that is not NULL; the rescue of bpsw_worker2_batch with
+ * rescue_mode; bpsw_sam_pe_batch_ex with flags.  g->reg_cnt, g->regs and g->pes are ignored; pair k is hashed as g->id0 + k.
+ * Needs the reference, the contig table and the index on the context's device.  The refusals are the stages': a read of more than
+ * BPSW_SEED_MAX_QLEN bases is BPSW_ERR_LIMIT, no index (or no reference) BPSW_ERR_ARG; group_size == 0 is fine. */
+int bpsw_sam_pe_batch_ex(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_tail_opt_t *topt, const bpsw_pairs_t *g, int flags,
+                         char *out_text, size_t text_cap, int64_t *out_off, size_t *out_needed, bpsw_alnreg_t *out_regs);
+int bpsw_align_pe_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                        const bpsw_pairs_t *g, const bpsw_pestat_t *pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags,
+                        char *out_text, size_t text_cap, int64_t *out_off, size_t *out_needed, bpsw_pestat_t *out_pes);
+/* Diagnostics, of the calling thread's most recent call of the two above (ms): sam_len_kernel, sam_write_kernel (0 without
+ * BPSW_SAM_TEXT_DEVICE), building and staging the line table, the round trip of the two kernels with the copies; and of
+ * bpsw_align_pe_batch: its worker1 stage, the statistics, the rescue, the tail. */
+void bpsw_last_sam_pe_times(double ms[8]);
 
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {
