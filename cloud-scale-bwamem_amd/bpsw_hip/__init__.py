@@ -858,17 +858,20 @@ def _ctx_reg2aln_batch(self, opt: Opt, topt: TailOpt, read_len, read_off, read_p
     return alns[: j.n], cig[: j.n], md[: j.n]
 
 
-def _pairs_struct(g, with_regs: bool = True):
-    st = Pairs()
-    st.group_size, st.id0 = g.group_size, g.id0
+def _pes_struct(pes):
+    """4 x (low, high, failed, avg, std) -> PeStat[4]"""
+    a = (PeStat * 4)()
     for r in range(4):
-        lo, hi, failed, avg, std = g.pes[r]
-        st.pes[r].low, st.pes[r].high, st.pes[r].failed, st.pes[r].avg, st.pes[r].std = int(lo), int(hi), int(failed), float(avg), float(std)
+        lo, hi, failed, avg, std = pes[r]
+        a[r].low, a[r].high, a[r].failed, a[r].avg, a[r].std = int(lo), int(hi), int(failed), float(avg), float(std)
+    return a
+
+
+def _reads_into(st, g, with_regs: bool):
+    """the read, name and (with_regs) region arrays of `g` into the fields that bpsw_pairs_t and bpsw_se_reads_t name alike
+    -> (the arrays, to be kept alive by the caller; reg_cnt and regs, or None and None)"""
     keep = []
-    for f, dt in (("read_len", np.int32), ("read_off", np.int64), ("read_pool", np.uint8), ("name_off", np.int64),
-                  ("name_pool", np.uint8), ("reg_cnt", np.int32)):
-        if f == "reg_cnt" and not with_regs:
-            continue
+    for f, dt in (("read_len", np.int32), ("read_off", np.int64), ("read_pool", np.uint8), ("name_off", np.int64), ("name_pool", np.uint8)):
         a = np.ascontiguousarray(getattr(g, f), dt)
         keep.append(a)
         setattr(st, f, a.ctypes.data)
@@ -878,58 +881,77 @@ def _pairs_struct(g, with_regs: bool = True):
         st.qual_pool = q.ctypes.data
     st.read_pool_bytes = int(np.asarray(g.read_pool).size)
     if not with_regs:
-        return st, keep, None
+        return keep, None, None
+    cnt = np.ascontiguousarray(g.reg_cnt, np.int32)
     regs = np.ascontiguousarray(g.regs)
     assert regs.dtype == ALNREG_DTYPE
-    st.regs = regs.ctypes.data
-    keep.append(regs)
+    keep += [cnt, regs]
+    st.reg_cnt, st.regs = cnt.ctypes.data, regs.ctypes.data
+    return keep, cnt, regs
+
+
+def _pairs_struct(g, with_regs: bool = True):
+    st = Pairs()
+    st.group_size, st.id0 = g.group_size, g.id0
+    st.pes = _pes_struct(g.pes)
+    keep, _, regs = _reads_into(st, g, with_regs)
     return st, keep, regs
+
+
+def _text_call(lib, what, n, call, text_cap, per_read=512, slack=0, grow=None):
+    """the capacity protocol of the text entries: call(buf, cap, off, need) until it fits -> per-read byte strings.  A text_cap is
+    tried once; without one the buffer starts at per_read bytes a read and grows to what the library asks for plus `slack`.
+    grow(): a caller with a second capacity enlarges it there and says whether it was too small"""
+    off = np.zeros(n + 1, np.int64)
+    need = C.c_size_t(0)
+    cap = per_read * max(1, n) if text_cap is None else int(text_cap)
+    while True:
+        buf = np.empty(max(cap, 1), np.uint8)   # the library writes off[-1] bytes
+        rc = call(_ptr(buf), cap, _ptr(off), C.byref(need))
+        if rc == -3 and text_cap is None:   # BPSW_ERR_CAPACITY
+            short = [need.value > cap, grow is not None and grow()]
+            if any(short):
+                cap = max(cap, int(need.value) + slack)
+                continue
+        _chk(lib, rc, what)
+        break
+    text = buf[: int(off[-1])].tobytes()
+    return [text[int(off[i]):int(off[i + 1])] for i in range(n)]
 
 
 def _ctx_sam_pe_batch(self, opt: Opt, topt: TailOpt, g: "TailGroupSoA", flags: int = 0):
     """memSamPeGroupRest -> (list of 2G SAM texts (bytes), regions as the tail leaves them); flags: SAM_TEXT_DEVICE
     (bpsw_sam_pe_batch_ex; without flags the call is bpsw_sam_pe_batch itself)"""
     st, keep, regs = _pairs_struct(g)
-    off = np.zeros(2 * g.group_size + 1, np.int64)
     out_regs = np.zeros(max(regs.shape[0], 1), ALNREG_DTYPE)
-    need = C.c_size_t(0)
-    cap = 1024 * max(1, 2 * g.group_size)
-    while True:
-        buf = np.empty(cap, np.uint8)   # the library writes off[-1] bytes
-        if flags:
-            rc = self.lib.bpsw_sam_pe_batch_ex(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, _ptr(buf), cap, _ptr(off), C.byref(need),
-                                               _ptr(out_regs))
-        else:
-            rc = self.lib.bpsw_sam_pe_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), _ptr(buf), cap, _ptr(off), C.byref(need),
-                                            _ptr(out_regs))
-        if rc == -3 and need.value > cap:   # BPSW_ERR_CAPACITY
-            cap = int(need.value) + 64
-            continue
-        _chk(self.lib, rc, "bpsw_sam_pe_batch")
-        break
-    text = buf[: int(off[-1])].tobytes()
-    return [text[int(off[i]):int(off[i + 1])] for i in range(2 * g.group_size)], out_regs[: regs.shape[0]]
+    head = (self.h, C.byref(opt), C.byref(topt), C.byref(st))
+    if flags:
+        call = lambda buf, cap, off, need: self.lib.bpsw_sam_pe_batch_ex(*head, flags, buf, cap, off, need, _ptr(out_regs))
+    else:
+        call = lambda buf, cap, off, need: self.lib.bpsw_sam_pe_batch(*head, buf, cap, off, need, _ptr(out_regs))
+    texts = _text_call(self.lib, "bpsw_sam_pe_batch", 2 * g.group_size, call, None, per_read=1024, slack=64)
+    return texts, out_regs[: regs.shape[0]]
 
 
 def _ctx_worker2_batch(self, opt: Opt, topt: TailOpt, g: "TailGroupSoA", rescue_mode: int = RESCUE_C):
     """rescue + tail for a group whose g.regs are the lists BEFORE the rescue -> (SAM texts, reg_cnt[2G], regs after)"""
     st, keep, regs = _pairs_struct(g)
-    off = np.zeros(2 * g.group_size + 1, np.int64)
     cnt = np.zeros(2 * g.group_size, np.int32)
-    need, total = C.c_size_t(0), C.c_int64(0)
-    cap, rcap = 1024 * max(1, 2 * g.group_size), int(regs.shape[0]) + 8 * g.group_size + 64
-    while True:
-        buf = np.empty(cap, np.uint8)
-        out_regs = np.empty(rcap, ALNREG_DTYPE)
-        rc = self.lib.bpsw_worker2_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), rescue_mode, _ptr(buf), cap, _ptr(off),
-                                         C.byref(need), _ptr(cnt), _ptr(out_regs), rcap, C.byref(total))
-        if rc == -3 and (need.value > cap or total.value > rcap):
-            cap, rcap = max(cap, int(need.value) + 64), max(rcap, int(total.value) + 16)
-            continue
-        _chk(self.lib, rc, "bpsw_worker2_batch")
-        break
-    text = buf[: int(off[-1])].tobytes()
-    return [text[int(off[i]):int(off[i + 1])] for i in range(2 * g.group_size)], cnt, out_regs[: total.value]
+    total = C.c_int64(0)
+    out = {"cap": int(regs.shape[0]) + 8 * g.group_size + 64, "regs": None}   # the second capacity: the regions after the rescue
+
+    def call(buf, cap, off, need):
+        out["regs"] = np.empty(out["cap"], ALNREG_DTYPE)
+        return self.lib.bpsw_worker2_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), rescue_mode, buf, cap, off, need, _ptr(cnt),
+                                           _ptr(out["regs"]), out["cap"], C.byref(total))
+
+    def grow():
+        short = total.value > out["cap"]
+        out["cap"] = max(out["cap"], int(total.value) + 16)
+        return short
+
+    texts = _text_call(self.lib, "bpsw_worker2_batch", 2 * g.group_size, call, None, per_read=1024, slack=64, grow=grow)
+    return texts, cnt, out["regs"][: total.value]
 
 
 def _ctx_last_tail_kernel(self):
@@ -999,50 +1021,18 @@ class SeReadsSoA:
 def _se_struct(g: "SeReadsSoA", with_regs: bool):
     st = SeReads()
     st.n_reads, st.id0, st.id_step = g.n_reads, int(g.id0), int(g.id_step)
-    keep = []
-    for f, dt in (("read_len", np.int32), ("read_off", np.int64), ("read_pool", np.uint8), ("name_off", np.int64), ("name_pool", np.uint8)):
-        a = np.ascontiguousarray(getattr(g, f), dt)
-        keep.append(a)
-        setattr(st, f, a.ctypes.data)
-    if g.qual_pool is not None:
-        q = np.ascontiguousarray(g.qual_pool, np.uint8)
-        keep.append(q)
-        st.qual_pool = q.ctypes.data
-    st.read_pool_bytes = int(np.asarray(g.read_pool).size)
-    n_regs = 0
-    if with_regs:
-        cnt = np.ascontiguousarray(g.reg_cnt, np.int32)
-        regs = np.ascontiguousarray(g.regs)
-        assert regs.dtype == ALNREG_DTYPE and int(cnt.sum()) == regs.shape[0]
-        keep += [cnt, regs]
-        st.reg_cnt, st.regs, n_regs = cnt.ctypes.data, regs.ctypes.data, int(regs.shape[0])
-    return st, keep, n_regs
-
-
-def _se_text_call(lib, what, n, call, text_cap):
-    """the capacity protocol of the text entries: call(buf, cap, off, need) until it fits -> per-read byte strings"""
-    off = np.zeros(n + 1, np.int64)
-    need = C.c_size_t(0)
-    cap = 512 * max(1, n) if text_cap is None else int(text_cap)
-    while True:
-        buf = np.empty(max(cap, 1), np.uint8)
-        rc = call(_ptr(buf), cap, _ptr(off), C.byref(need))
-        if rc == -3 and need.value > cap and text_cap is None:   # BPSW_ERR_CAPACITY
-            cap = int(need.value)
-            continue
-        _chk(lib, rc, what)
-        break
-    text = buf[: int(off[-1])].tobytes()
-    return [text[int(off[i]):int(off[i + 1])] for i in range(n)]
+    keep, cnt, regs = _reads_into(st, g, with_regs)
+    assert regs is None or int(cnt.sum()) == regs.shape[0]
+    return st, keep, 0 if regs is None else int(regs.shape[0])
 
 
 def _ctx_sam_se_batch(self, opt: Opt, topt: "TailOpt", g: "SeReadsSoA", flags: int = 0, text_cap: int | None = None):
     """singleEndBwaMemWorker2 for a batch -> (list of n SAM texts (bytes), the region lists after mark-primary)"""
     st, keep, n_regs = _se_struct(g, True)
     out_regs = np.zeros(max(n_regs, 1), ALNREG_DTYPE)
-    texts = _se_text_call(self.lib, "bpsw_sam_se_batch", g.n_reads,
-                          lambda buf, cap, off, need: self.lib.bpsw_sam_se_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, buf, cap,
-                                                                                 off, need, _ptr(out_regs)), text_cap)
+    texts = _text_call(self.lib, "bpsw_sam_se_batch", g.n_reads,
+                       lambda buf, cap, off, need: self.lib.bpsw_sam_se_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, buf, cap,
+                                                                              off, need, _ptr(out_regs)), text_cap)
     return texts, out_regs[:n_regs]
 
 
@@ -1050,9 +1040,9 @@ def _ctx_align_se_batch(self, opt: Opt, sopt, topt: "TailOpt", g: "SeReadsSoA", 
                         flags: int = 0, text_cap: int | None = None):
     """reads -> SAM texts (bytes) per read: worker1_batch with C2A_SORT_DEDUP, then sam_se_batch, in one call"""
     st, keep, _ = _se_struct(g, False)
-    return _se_text_call(self.lib, "bpsw_align_se_batch", g.n_reads,
-                         lambda buf, cap, off, need: self.lib.bpsw_align_se_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
-                                                                                  zdrop_mode, w1_flags, flags, buf, cap, off, need), text_cap)
+    return _text_call(self.lib, "bpsw_align_se_batch", g.n_reads,
+                      lambda buf, cap, off, need: self.lib.bpsw_align_se_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
+                                                                               zdrop_mode, w1_flags, flags, buf, cap, off, need), text_cap)
 
 
 def last_sam_se_times():
@@ -1069,17 +1059,12 @@ def _ctx_align_pe_batch(self, opt: Opt, sopt, topt: "TailOpt", g: "TailGroupSoA"
     worker1_batch with C2A_SORT_DEDUP on the 2G reads, pes0 or pe_stat over their lists, the rescue, the paired tail, in one call.
     g.reg_cnt, g.regs and g.pes are ignored."""
     st, keep, _ = _pairs_struct(g, False)
-    pes_in = None
-    if pes0 is not None:
-        pes_in = (PeStat * 4)()
-        for r in range(4):
-            lo, hi, failed, avg, std = pes0[r]
-            pes_in[r].low, pes_in[r].high, pes_in[r].failed, pes_in[r].avg, pes_in[r].std = int(lo), int(hi), int(failed), float(avg), float(std)
+    pes_in = None if pes0 is None else _pes_struct(pes0)
     pes = (PeStat * 4)()
-    texts = _se_text_call(self.lib, "bpsw_align_pe_batch", 2 * g.group_size,
-                          lambda buf, cap, off, need: self.lib.bpsw_align_pe_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
-                                                                                   pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, cap, off,
-                                                                                   need, pes), text_cap)
+    texts = _text_call(self.lib, "bpsw_align_pe_batch", 2 * g.group_size,
+                       lambda buf, cap, off, need: self.lib.bpsw_align_pe_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
+                                                                                pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, cap, off,
+                                                                                need, pes), text_cap)
     return texts, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)]
 
 
@@ -1178,14 +1163,6 @@ Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute 
 
 
 # ---- host-only pieces (no device): usable and testable on a CPU-only box -------------------------------------------------
-def _pes_struct(pes):
-    a = (PeStat * 4)()
-    for r in range(4):
-        lo, hi, failed, avg, std = pes[r]
-        a[r].low, a[r].high, a[r].failed, a[r].avg, a[r].std = int(lo), int(hi), int(failed), float(avg), float(std)
-    return a
-
-
 def mark_primary_se(opt: Opt, topt: TailOpt, regs: np.ndarray, rid: int) -> np.ndarray:
     a = np.ascontiguousarray(regs.copy())
     lib = load_library()

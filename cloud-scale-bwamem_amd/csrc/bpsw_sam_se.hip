@@ -1,12 +1,12 @@
-// bpsw_sam_se.hip -- the single-end worker2 behind the C ABI: bpsw_sam_se_batch, bpsw_align_se_batch, and the SAM text written on
-// the device (BPSW_SAM_TEXT_DEVICE).
+// bpsw_sam_se.hip -- the single-end worker2 behind the C ABI: bpsw_sam_se_batch, bpsw_align_se_batch; the SAM text written on the
+// device (BPSW_SAM_TEXT_DEVICE), for both modes; worker1 in front of a tail (worker1_lists), for both modes.
 //
-// singleEndBwaMemWorker2 (worker2/BWAMemWorker2.scala:49-58 == native/bwamem.c:1052-1056) for a batch: per read mem_mark_primary_se,
-// then mem_reg2sam_se with extra_flag = 0 and no mate (native/bwamem.c:879-892, R2S:67-118).  The pieces are bpsw_tail.cpp's
-// (bpsw_tail_internal.h): mark_primary, run_jobs over reg2aln_kernel, make_aln, and aln_to_sam for the text on the calling thread.
+// bpsw_sam_se_batch is sam_batch (bpsw_tail.cpp, bpsw_tail_internal.h) on a bpsw_se_reads_t: singleEndBwaMemWorker2
+// (worker2/BWAMemWorker2.scala:49-58 == native/bwamem.c:1052-1056) for a batch, with the selection and the line rules of
+// mem_reg2sam_se that the paired tail's single-end fallback uses.  What this file adds is the choice of who writes the text.
 //
-// With BPSW_SAM_TEXT_DEVICE the text is written by two kernels over bpsw_sam_core.h, the byte definition of a line (the paired
-// entries of bpsw_sam_pe.hip go through the same two, text_on_device, with every line naming its mate):
+// With BPSW_SAM_TEXT_DEVICE the entries here and in bpsw_sam_pe.hip hand sam_batch text_on_device: two kernels over
+// bpsw_sam_core.h, the byte definition of a line (in a pair every line names its mate):
 //   sam_len_kernel    one line per lane: the line's number of bytes; the host sums them to line offsets, per-read out_off and
 //                     the total (a total past text_cap ends the call there);
 //   sam_write_kernel  one line per lane: the line's bytes at its offset in one device block, which comes back with one copy.
@@ -46,32 +46,15 @@ __global__ __launch_bounds__(64) void sam_write_kernel(sc::SamBatch B, int n_lin
 
 thread_local double t_last[6] = {0., 0., 0., 0., 0., 0.};
 
-struct SePlan {  // per read: memRegToSAMSe's selection, (region index, job)
-  std::vector<std::pair<int, int> > jobs;
-};
-
-int check_reads(const char* who, const bpsw_se_reads_t* g, bool need_regs, size_t* n_regs) {
-  const int n = g->n_reads;
-  if (!g->read_len || !g->read_off || !g->read_pool || !g->name_off || !g->name_pool) return fail(BPSW_ERR_ARG, std::string(who) + ": null read arrays");
-  if (g->id_step < 0) return fail(BPSW_ERR_ARG, std::string(who) + ": negative id_step");
-  if (need_regs && !g->reg_cnt) return fail(BPSW_ERR_ARG, std::string(who) + ": null region counts");
-  *n_regs = 0;
-  for (int r = 0; r < n; ++r) {
-    if (need_regs && g->reg_cnt[r] < 0) return fail(BPSW_ERR_ARG, std::string(who) + ": negative region count");
-    if (g->read_len[r] < 1 || g->read_off[r] < 0 || (unsigned long long)(g->read_off[r] + g->read_len[r]) > g->read_pool_bytes)
-      return fail(BPSW_ERR_ARG, std::string(who) + ": read outside its pool (or empty)");
-    if (g->name_off[r] < 0 || g->name_off[r + 1] < g->name_off[r]) return fail(BPSW_ERR_ARG, std::string(who) + ": name offsets must ascend");
-    if (need_regs) *n_regs += (size_t)g->reg_cnt[r];
-  }
-  if (need_regs && *n_regs && !g->regs) return fail(BPSW_ERR_ARG, std::string(who) + ": null region array");
-  return BPSW_OK;
-}
-
 }  // namespace
 
-int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const std::vector<Aln>& aa,
-                         const std::vector<int32_t>& line_read, const std::vector<int32_t>& read_first, const Aln* mate, const JobResults& R,
+int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& sl,
                          char* out_text, size_t text_cap, int64_t* out_off, size_t* total_out, double times[4]) {
+  const std::vector<Aln>& aa = sl.aa;
+  const std::vector<int32_t>& line_read = sl.line_read;
+  const std::vector<int32_t>& read_first = sl.read_first;
+  const Aln* mate = sl.mate.empty() ? nullptr : sl.mate.data();
+  const JobResults& R = *sl.R;
   const int n = g.n, n_lines = (int)aa.size(), n_names = g.n >> g.name_shift;
   const std::string w(who);
   const double t0 = wall_ms();
@@ -187,118 +170,33 @@ int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const
   return BPSW_OK;
 }
 
+int bpsw::worker1_lists(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const TextReads& g, int zdrop_mode, int w1_flags,
+                        std::vector<int32_t>* cnt, std::vector<bpsw_alnreg_t>* regs) {
+  bpsw_reads_t rd;
+  rd.n_reads = g.n; rd.read_len = g.read_len; rd.read_off = g.read_off; rd.read_pool = g.read_pool; rd.read_pool_bytes = g.read_pool_bytes;
+  cnt->assign((size_t)g.n, 0);
+  regs->resize((size_t)(4 * (int64_t)g.n + 64));
+  int64_t total = 0;
+  auto run = [&]() {
+    return bpsw_worker1_batch(c, opt, sopt, &rd, zdrop_mode, w1_flags | BPSW_C2A_SORT_DEDUP, cnt->data(), regs->data(), (int64_t)regs->size(), &total);
+  };
+  int rc = run();
+  if (rc == BPSW_ERR_CAPACITY && total > (int64_t)regs->size()) {
+    regs->resize((size_t)total);
+    rc = run();
+  }
+  return rc;
+}
+
 extern "C" {
 
 int bpsw_sam_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g, int flags,
                       char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
-  if (!c || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "sam_se: null argument");
-  if (flags & ~BPSW_SAM_TEXT_DEVICE) return fail(BPSW_ERR_ARG, "sam_se: unknown flag");
-  SwScoring sw;
-  int rc = make_scoring("tail", opt, 0, 1, &sw);
-  if (rc != BPSW_OK) return rc;
-  const int n = g->n_reads;
-  if (n < 0) return fail(BPSW_ERR_ARG, "sam_se: negative number of reads");
-  if (n == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
-  size_t n_regs = 0;
-  rc = check_reads("sam_se", g, true, &n_regs);
-  if (rc != BPSW_OK) return rc;
-  ContextEntry entry(c);
-  if (entry.rc != BPSW_OK) return entry.rc;
-  BnsView bns;
-  rc = snapshot_bns(c, &bns);
-  if (rc != BPSW_OK) return rc;
-  const bpsw_opt_t& o = *opt;
-  const bpsw_tail_opt_t& t = *topt;
-
-  // ---- plan: mem_mark_primary_se and mem_reg2sam_se's selection ---------------------------------------------------------------
-  c->last_tail_ms = 0.f; c->last_tail_jobs = 0; c->last_tail_resubmitted = 0;
-  memset(t_last, 0, sizeof t_last);
-  const double t_plan = wall_ms();
-  std::vector<bpsw_alnreg_t> regs(g->regs, g->regs + n_regs);  // sorted in place, read by read
-  std::vector<size_t> reg_at((size_t)n + 1, 0);
-  std::vector<SePlan> plan((size_t)n);
-  std::vector<int32_t> job_len;
-  std::vector<int64_t> job_off;
-  std::vector<bpsw_alnreg_t> job_reg;
-  std::vector<bpsw_alnreg_t> a;
-  for (int r = 0; r < n; ++r) {
-    reg_at[(size_t)r + 1] = reg_at[(size_t)r] + (size_t)g->reg_cnt[r];
-    a.assign(regs.begin() + (long)reg_at[(size_t)r], regs.begin() + (long)reg_at[(size_t)r + 1]);
-    mark_primary(o, t, a, g->id0 + (int64_t)r * g->id_step);
-    std::copy(a.begin(), a.end(), regs.begin() + (long)reg_at[(size_t)r]);
-    for (size_t j = 0; j < a.size(); ++j) {  // native/bwamem.c:879-892, R2S:67-118
-      const bpsw_alnreg_t& p = a[j];
-      if (p.score < o.T) continue;
-      if (p.secondary >= 0 && !(o.flag & BPSW_MEM_F_ALL)) continue;
-      if (p.secondary >= 0 && p.score < a[(size_t)p.secondary].score * .5) continue;
-      int job = -1;
-      if (p.rb >= 0 && p.re >= 0) {  // (else the unmapped record, R2S:175-180)
-        job_len.push_back(g->read_len[r]); job_off.push_back(g->read_off[r]); job_reg.push_back(p);
-        job = (int)job_reg.size() - 1;
-      }
-      plan[(size_t)r].jobs.push_back(std::make_pair((int)j, job));
-    }
-  }
-
-  // ---- device: memRegToAln ------------------------------------------------------------------------------------------------------
-  static thread_local JobResults results;  // (kept per calling thread: no allocation in the steady state)
-  JobResults& R = results;
-  const double t_dev = wall_ms();
-  rc = run_jobs(c, sw, opt, t.flavour, bns, job_len, job_off, g->read_pool, g->read_pool_bytes, job_reg, &R);
-  if (rc != BPSW_OK) return rc;
-  for (size_t j = 0; j < R.r.size(); ++j)
-    if (R.r[j].k.status == BPSW_ALN_XREF || R.r[j].k.status == BPSW_ALN_OVERFLOW)
-      return fail(BPSW_ERR_LIMIT, R.r[j].k.status == BPSW_ALN_XREF ? "sam_se: bwaFixXref2 could not repair a region (the reference aborts here)"
-                                                                   : "sam_se: an alignment has more CIGAR operations than the kernel stages");
-
-  // ---- emit ---------------------------------------------------------------------------------------------------------------------
-  const double t_emit = wall_ms();
-  std::vector<Aln> aa;
-  std::vector<int32_t> line_read, read_first((size_t)n + 1, 0);
-  for (int r = 0; r < n; ++r) {
-    const bpsw_alnreg_t* ar = regs.data() + reg_at[(size_t)r];
-    const size_t first = aa.size();
-    for (size_t x = 0; x < plan[(size_t)r].jobs.size(); ++x) {
-      const int j = plan[(size_t)r].jobs[x].first, jb = plan[(size_t)r].jobs[x].second;
-      const bpsw_alnreg_t& p = ar[j];
-      Aln q = make_aln(o, t, &p, jb >= 0 ? &R.r[(size_t)jb] : nullptr, R);
-      if (p.secondary >= 0) q.a.sub = -1;  // don't output the sub-optimal score
-      if (j && p.secondary < 0) q.a.flag |= (o.flag & BPSW_MEM_F_NO_MULTI) ? 0x10000 : 0x800;  // supplementary
-      if (j && aa.size() > first && q.a.mapq > aa[first].a.mapq) q.a.mapq = aa[first].a.mapq;
-      aa.push_back(q);
-    }
-    if (aa.size() == first) aa.push_back(make_aln(o, t, nullptr, nullptr, R));  // the unaligned record
-    line_read.resize(aa.size(), r);
-    read_first[(size_t)r + 1] = (int32_t)aa.size();
-  }
-  size_t total = 0;
-  if (flags & BPSW_SAM_TEXT_DEVICE) {
-    TextReads tr;
-    tr.n = n; tr.read_len = g->read_len; tr.read_off = g->read_off; tr.read_pool = g->read_pool; tr.qual_pool = g->qual_pool;
-    tr.read_pool_bytes = g->read_pool_bytes; tr.name_off = g->name_off; tr.name_pool = g->name_pool;
-    rc = text_on_device(c, "sam_se", bns, t, tr, aa, line_read, read_first, nullptr, R, out_text, text_cap, out_off, &total, t_last);
-    if (rc != BPSW_OK) return rc;
-  } else {
-    Text text(out_text, text_cap);
-    for (int r = 0; r < n; ++r) {
-      out_off[r] = (int64_t)text.size();
-      const char* name = g->name_pool + g->name_off[r];
-      const size_t name_len = (size_t)(g->name_off[r + 1] - g->name_off[r]);
-      const uint8_t* seq = g->read_pool + g->read_off[r];
-      const uint8_t* qual = g->qual_pool ? g->qual_pool + g->read_off[r] : nullptr;
-      const Aln* list = aa.data() + read_first[(size_t)r];
-      const size_t n_list = (size_t)(read_first[(size_t)r + 1] - read_first[(size_t)r]);
-      for (size_t x = 0; x < n_list; ++x)
-        aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[r], seq, qual, list, n_list, (int)x, nullptr, t.rg_id);
-    }
-    out_off[n] = (int64_t)text.size();
-    total = text.size();
-  }
-  if (out_regs && n_regs) memcpy(out_regs, regs.data(), sizeof(bpsw_alnreg_t) * n_regs);
-  c->tail_host_ms[0] = t_dev - t_plan; c->tail_host_ms[1] = t_emit - t_dev; c->tail_host_ms[2] = wall_ms() - t_emit;
-  if (out_needed) *out_needed = total;
-  if (!out_text || total > text_cap) return fail(BPSW_ERR_CAPACITY, "sam_se: text buffer too small (see *out_needed)");
-  return BPSW_OK;
+  if (c && topt && g && out_off && (flags & ~BPSW_SAM_TEXT_DEVICE)) return fail(BPSW_ERR_ARG, "sam_se: unknown flag");  // (after the null checks)
+  SamCall m;
+  m.on_device = (flags & BPSW_SAM_TEXT_DEVICE) ? text_on_device : nullptr;
+  m.times = t_last; m.n_times = 6;
+  return sam_batch(c, opt, topt, g, nullptr, m, out_text, text_cap, out_off, out_needed, out_regs);
 }
 
 int bpsw_align_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt,
@@ -309,20 +207,13 @@ int bpsw_align_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_op
   if (n < 0) return fail(BPSW_ERR_ARG, "align_se: negative number of reads");
   if (n == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
   size_t none = 0;
-  int rc = check_reads("align_se", g, false, &none);
+  int rc = se_check("align_se", g, false, &none);
   if (rc != BPSW_OK) return rc;
   // ---- worker1: reads -> region lists (FastMap.scala:624) ---------------------------------------------------------------------
   const double t0 = wall_ms();
-  bpsw_reads_t rd;
-  rd.n_reads = n; rd.read_len = g->read_len; rd.read_off = g->read_off; rd.read_pool = g->read_pool; rd.read_pool_bytes = g->read_pool_bytes;
-  std::vector<int32_t> cnt((size_t)n, 0);
-  std::vector<bpsw_alnreg_t> regs((size_t)(4 * (int64_t)n + 64));
-  int64_t total = 0;
-  rc = bpsw_worker1_batch(c, opt, sopt, &rd, zdrop_mode, w1_flags | BPSW_C2A_SORT_DEDUP, cnt.data(), regs.data(), (int64_t)regs.size(), &total);
-  if (rc == BPSW_ERR_CAPACITY && total > (int64_t)regs.size()) {
-    regs.resize((size_t)total);
-    rc = bpsw_worker1_batch(c, opt, sopt, &rd, zdrop_mode, w1_flags | BPSW_C2A_SORT_DEDUP, cnt.data(), regs.data(), (int64_t)regs.size(), &total);
-  }
+  std::vector<int32_t> cnt;
+  std::vector<bpsw_alnreg_t> regs;
+  rc = worker1_lists(c, opt, sopt, text_reads(g), zdrop_mode, w1_flags, &cnt, &regs);
   if (rc != BPSW_OK) return rc;
   // ---- worker2: the lists -> text (FastMap.scala:625) ---------------------------------------------------------------------------
   const double t1 = wall_ms();

@@ -1,4 +1,8 @@
-// bpsw_tail.cpp -- worker2's tail behind the C ABI: bpsw_reg2aln_batch, bpsw_sam_pe_batch.
+// bpsw_tail.cpp -- worker2's tail behind the C ABI: bpsw_reg2aln_batch, bpsw_sam_pe_batch, bpsw_worker2_batch, and
+// sam_batch, the one body behind bpsw_sam_pe_batch, bpsw_sam_pe_batch_ex and bpsw_sam_se_batch (the latter two are bpsw_sam_pe.hip's
+// and bpsw_sam_se.hip's; they hand in who writes the text).  The rules of mem_reg2sam_se -- which regions of a read get a line
+// (se_select) and what its lines are (se_append) -- exist once and serve single-end reads (se_lines) and the paired tail's
+// single-end fallback (pe_lines).  This file names no symbol that only a .hip file defines: the host-only builds link it alone.
 //
 // memSamPeGroupRest (worker2/MemSamPe.scala:1390-1612 == mem_sam_pe after the rescue, native/bwamem_pair.c:385-452) is
 // split in three passes so that every global alignment of a group goes to the GPU in ONE launch:
@@ -19,7 +23,7 @@
 #include <utility>
 #include <vector>
 
-#include "bpsw_tail_internal.h"  // (with bpsw_internal.h) what bpsw_sam_se.hip shares with this file
+#include "bpsw_tail_internal.h"  // (with bpsw_internal.h) what bpsw_sam_se.hip and bpsw_sam_pe.hip share with this file
 
 using namespace bpsw;
 
@@ -618,55 +622,173 @@ int bpsw_reg2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt
   return BPSW_OK;
 }
 
-// ---- the paired tail in pieces (bpsw_tail_internal.h): checks, plan + jobs + line lists, the text on the calling thread, the end ----
+// ---- the tail in pieces (bpsw_tail_internal.h): checks, plan + jobs + line lists, the text on the calling thread, the end ------------
+int bpsw::check_reads(const char* who, const TextReads& g, const int32_t* reg_cnt, bool names_ascend, size_t* n_regs) {
+  const std::string w(who);
+  *n_regs = 0;
+  for (int r = 0; r < g.n; ++r) {
+    if (reg_cnt && reg_cnt[r] < 0) return fail(BPSW_ERR_ARG, w + ": negative region count");
+    if (g.read_len[r] < 1 || g.read_off[r] < 0 || (unsigned long long)(g.read_off[r] + g.read_len[r]) > g.read_pool_bytes)
+      return fail(BPSW_ERR_ARG, w + ": read outside its pool (or empty)");
+    if (names_ascend && (g.name_off[r] < 0 || g.name_off[r + 1] < g.name_off[r])) return fail(BPSW_ERR_ARG, w + ": name offsets must ascend");
+    if (reg_cnt) *n_regs += (size_t)reg_cnt[r];
+  }
+  return BPSW_OK;
+}
+
+int bpsw::se_check(const char* who, const bpsw_se_reads_t* g, bool need_regs, size_t* n_regs) {
+  const std::string w(who);
+  if (!g->read_len || !g->read_off || !g->read_pool || !g->name_off || !g->name_pool) return fail(BPSW_ERR_ARG, w + ": null read arrays");
+  if (g->id_step < 0) return fail(BPSW_ERR_ARG, w + ": negative id_step");
+  if (need_regs && !g->reg_cnt) return fail(BPSW_ERR_ARG, w + ": null region counts");
+  const int rc = check_reads(who, text_reads(g), need_regs ? g->reg_cnt : nullptr, true, n_regs);
+  if (rc != BPSW_OK) return rc;
+  if (*n_regs && !g->regs) return fail(BPSW_ERR_ARG, w + ": null region array");
+  return BPSW_OK;
+}
+
 int bpsw::pe_check(const char* who, const bpsw_pairs_t* g, size_t* n_regs) {
-  const int G = g->group_size;
   const std::string w(who);
   if (!g->read_len || !g->read_off || !g->read_pool || !g->name_off || !g->name_pool || !g->reg_cnt) return fail(BPSW_ERR_ARG, w + ": null group arrays");
-  *n_regs = 0;
-  for (int r = 0; r < 2 * G; ++r) {
-    if (g->reg_cnt[r] < 0) return fail(BPSW_ERR_ARG, w + ": negative region count");
-    if (g->read_len[r] < 1 || g->read_off[r] < 0 || (unsigned long long)(g->read_off[r] + g->read_len[r]) > g->read_pool_bytes)
-      return fail(BPSW_ERR_ARG, w + ": read outside its pool (or empty)");
-    *n_regs += (size_t)g->reg_cnt[r];
-  }
+  const int rc = check_reads(who, text_reads(g), g->reg_cnt, false, n_regs);
+  if (rc != BPSW_OK) return rc;
   if (*n_regs && !g->regs) return fail(BPSW_ERR_ARG, w + ": null region array");
   return BPSW_OK;
 }
 
 namespace {
-struct PlanScratch {
-  std::vector<std::vector<bpsw_alnreg_t> > regs;
-  std::vector<PairPlan> plan;
+
+typedef std::vector<std::pair<int, int> > Selection;  // of one read's list: (region index, job; -1: the unmapped record)
+
+// What a call plans with, kept per calling thread and re-filled in place: no allocation in the steady state.
+struct TailScratch {
+  std::vector<std::vector<bpsw_alnreg_t> > regs;  // per read: its list, marked and sorted
+  std::vector<PairPlan> plan;                     // per pair
+  std::vector<Selection> sel;                     // single-end: per read
   std::vector<int32_t> job_len;
   std::vector<int64_t> job_off;
   std::vector<bpsw_alnreg_t> job_reg;
+  JobResults results;
+  // (forced inline: as a call per job it cost the paired plan 6 % on 10^5 pairs)
+  __attribute__((always_inline)) int add_job(int32_t read_len, int64_t read_off, const bpsw_alnreg_t& ar) {
+    if (ar.rb < 0 || ar.re < 0) return -1;  // the unmapped record, R2S:175-180
+    job_len.push_back(read_len); job_off.push_back(read_off); job_reg.push_back(ar);
+    return (int)job_reg.size() - 1;
+  }
 };
-}  // namespace
 
-int bpsw::pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g,
-                   const BnsView& bns, PeLines* out) {
+// the start of a call's plan: the context's tail counters and the calling thread's scratch, emptied, with room for n_reads lists
+TailScratch& begin_plan(bpsw_ctx* c, SamLines* out, size_t n_reads) {
+  c->last_tail_ms = 0.f; c->last_tail_jobs = 0; c->last_tail_resubmitted = 0;
+  out->t_plan = wall_ms();
+  static thread_local TailScratch S;
+  if (S.regs.size() < n_reads) S.regs.resize(n_reads);
+  S.job_len.clear(); S.job_off.clear(); S.job_reg.clear();
+  return S;
+}
+
+// memRegToSAMSe's selection (native/bwamem.c:879-892, R2S:67-118) over one read's marked list; job0: the job region 0 already has
+// (-1: none yet)
+void se_select(const bpsw_opt_t& o, const std::vector<bpsw_alnreg_t>& a, int32_t read_len, int64_t read_off, int job0, TailScratch& S,
+               Selection* sel) {
+  sel->clear();
+  for (size_t j = 0; j < a.size(); ++j) {
+    const bpsw_alnreg_t& p = a[j];
+    if (p.score < o.T) continue;
+    if (p.secondary >= 0 && !(o.flag & BPSW_MEM_F_ALL)) continue;
+    if (p.secondary >= 0 && p.score < a[(size_t)p.secondary].score * .5) continue;
+    sel->push_back(std::make_pair((int)j, j == 0 && job0 >= 0 ? job0 : S.add_job(read_len, read_off, p)));
+  }
+}
+
+// The selected regions' lines appended to `aa`, each flag OR-ed with extra_flag (memRegToSAMSe after the selection); the unaligned
+// record alone when nothing was selected.  (Forced inline, like add_job: as a call per read it cost the paired tail's line
+// building a tenth)
+__attribute__((always_inline)) inline void se_append(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, const std::vector<bpsw_alnreg_t>& a, const Selection& sel, const JobResults& R,
+               int extra_flag, std::vector<Aln>* aa) {
+  const size_t first = aa->size();
+  for (size_t x = 0; x < sel.size(); ++x) {
+    const int j = sel[x].first, jb = sel[x].second;
+    const bpsw_alnreg_t& p = a[(size_t)j];
+    Aln q = make_aln(o, t, &p, jb >= 0 ? &R.r[(size_t)jb] : nullptr, R);
+    q.a.flag |= extra_flag;
+    if (p.secondary >= 0) q.a.sub = -1;  // don't output the sub-optimal score
+    if (j && p.secondary < 0) q.a.flag |= (o.flag & BPSW_MEM_F_NO_MULTI) ? 0x10000 : 0x800;  // supplementary
+    if (j && aa->size() > first && q.a.mapq > (*aa)[first].a.mapq) q.a.mapq = (*aa)[first].a.mapq;
+    aa->push_back(q);
+  }
+  if (aa->size() == first) {
+    Aln u = make_aln(o, t, nullptr, nullptr, R);
+    u.a.flag |= extra_flag;
+    aa->push_back(u);
+  }
+}
+
+// the planned jobs through run_jobs; a job the reference would abort on, or one the kernel cannot stage, ends the call
+int run_planned(bpsw_ctx* c, const char* who, const SwScoring& sc, const bpsw_opt_t* opt, int flavour, const BnsView& bns, const TextReads& g,
+                TailScratch& S) {
+  const int rc = run_jobs(c, sc, opt, flavour, bns, S.job_len, S.job_off, g.read_pool, g.read_pool_bytes, S.job_reg, &S.results);
+  if (rc != BPSW_OK) return rc;
+  for (const JobResult& j : S.results.r)
+    if (j.k.status == BPSW_ALN_XREF || j.k.status == BPSW_ALN_OVERFLOW)
+      return fail(BPSW_ERR_LIMIT, std::string(who) + (j.k.status == BPSW_ALN_XREF ? ": bwaFixXref2 could not repair a region (the reference aborts here)"
+                                                                                   : ": an alignment has more CIGAR operations than the kernel stages"));
+  return BPSW_OK;
+}
+
+void begin_lines(SamLines* out, const TailScratch& S, int n_reads, bool mates) {
+  out->t_emit = wall_ms();
+  out->R = &S.results;
+  out->regs = S.regs.data();
+  out->aa.clear(); out->line_read.clear();
+  out->read_first.assign((size_t)n_reads + 1, 0);
+  out->mate.resize(mates ? (size_t)n_reads : 0);
+}
+void end_read(SamLines* out, int r) {  // the lines appended since the last call are read r's
+  out->line_read.resize(out->aa.size(), r);
+  out->read_first[(size_t)r + 1] = (int32_t)out->aa.size();
+}
+
+// singleEndBwaMemWorker2 (worker2/BWAMemWorker2.scala:49-58 == native/bwamem.c:1052-1056): per read mem_mark_primary_se with
+// id0 + r * id_step, then mem_reg2sam_se without a mate.  Caller holds c->mu.
+int se_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g, const BnsView& bns,
+             SamLines* out) {
+  const int n = g->n_reads;
+  TailScratch& S = begin_plan(c, out, (size_t)n);
+  if (S.sel.size() < (size_t)n) S.sel.resize((size_t)n);
+  size_t at = 0;
+  for (int r = 0; r < n; ++r) {
+    std::vector<bpsw_alnreg_t>& a = S.regs[(size_t)r];
+    a.assign(g->regs + at, g->regs + at + (size_t)g->reg_cnt[r]);
+    at += (size_t)g->reg_cnt[r];
+    mark_primary(*opt, *topt, a, g->id0 + (int64_t)r * g->id_step);
+    se_select(*opt, a, g->read_len[r], g->read_off[r], -1, S, &S.sel[(size_t)r]);
+  }
+  out->t_dev = wall_ms();
+  const int rc = run_planned(c, "sam_se", sc, opt, topt->flavour, bns, text_reads(g), S);
+  if (rc != BPSW_OK) return rc;
+  begin_lines(out, S, n, false);
+  for (int r = 0; r < n; ++r) {
+    se_append(*opt, *topt, S.regs[(size_t)r], S.sel[(size_t)r], S.results, 0, &out->aa);
+    end_read(out, r);
+  }
+  return BPSW_OK;
+}
+
+// mark-primary, memPair and the single-end fallback, the jobs through run_jobs, then every read's lines (read 2k + i) and the record
+// they are printed against.  Caller holds c->mu.
+int pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, const BnsView& bns,
+             SamLines* out) {
   const int G = g->group_size;
   const bpsw_opt_t& o = *opt;
   const bpsw_tail_opt_t& t = *topt;
 
   // ---- plan -----------------------------------------------------------------------------------------------------------
-  c->last_tail_ms = 0.f; c->last_tail_jobs = 0; c->last_tail_resubmitted = 0;
-  out->t_plan = wall_ms();
-  static thread_local PlanScratch scratch;  // 2 G + G vectors, re-filled in place: their heap blocks are reused from call to call
-  std::vector<std::vector<bpsw_alnreg_t> >& regs = scratch.regs;
-  std::vector<PairPlan>& plan = scratch.plan;
-  std::vector<int32_t>& job_len = scratch.job_len;
-  std::vector<int64_t>& job_off = scratch.job_off;
-  std::vector<bpsw_alnreg_t>& job_reg = scratch.job_reg;
-  if (regs.size() < (size_t)(2 * G)) regs.resize((size_t)(2 * G));
+  TailScratch& S = begin_plan(c, out, (size_t)(2 * G));
+  std::vector<std::vector<bpsw_alnreg_t> >& regs = S.regs;
+  std::vector<PairPlan>& plan = S.plan;
   if (plan.size() < (size_t)G) plan.resize((size_t)G);
-  job_len.clear(); job_off.clear(); job_reg.clear();
-  auto add_job = [&](int read, const bpsw_alnreg_t& ar) -> int {
-    if (ar.rb < 0 || ar.re < 0) return -1;  // the unmapped record, R2S:175-180
-    job_len.push_back(g->read_len[read]); job_off.push_back(g->read_off[read]); job_reg.push_back(ar);
-    return (int)job_reg.size() - 1;
-  };
+  auto add_job = [&](int read, const bpsw_alnreg_t& ar) -> int { return S.add_job(g->read_len[read], g->read_off[read], ar); };
   size_t at = 0;
   for (int k = 0; k < G; ++k) {
     PairPlan& P = plan[(size_t)k];
@@ -708,41 +830,25 @@ int bpsw::pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, cons
         for (int i = 0; i < 2; ++i) P.q_se[i] = approx_mapq(o, t, a[i][0]);
       }
       for (int i = 0; i < 2; ++i) P.end[i].h_job = add_job(2 * k + i, a[i][(size_t)P.z[i]]);
-    } else {  // no_pairing, PE:1553-1605 + memRegToSAMSe, R2S:67-118
+    } else {  // no_pairing, PE:1553-1605 + memRegToSAMSe
       for (int i = 0; i < 2; ++i) {
         EndPlan& E = P.end[i];
         if (!a[i].empty() && a[i][0].score >= o.T) E.h_job = add_job(2 * k + i, a[i][0]);
-        for (size_t j = 0; j < a[i].size(); ++j) {
-          const bpsw_alnreg_t& p = a[i][j];
-          if (p.score < o.T) continue;
-          if (p.secondary >= 0 && !(o.flag & BPSW_MEM_F_ALL)) continue;
-          if (p.secondary >= 0 && p.score < a[i][(size_t)p.secondary].score * .5) continue;
-          E.se_jobs.push_back(std::make_pair((int)j, j == 0 && E.h_job >= 0 ? E.h_job : add_job(2 * k + i, p)));
-        }
+        se_select(o, a[i], g->read_len[2 * k + i], g->read_off[2 * k + i], E.h_job, S, &E.se_jobs);
       }
     }
   }
 
   // ---- device -----------------------------------------------------------------------------------------------------------
-  static thread_local JobResults results;  // (the scratch of a call is kept per calling thread: no allocation in the steady state)
-  JobResults& R = results;
-  std::vector<JobResult>& res = R.r;
   out->t_dev = wall_ms();
-  int rc = run_jobs(c, sc, opt, t.flavour, bns, job_len, job_off, g->read_pool, g->read_pool_bytes, job_reg, &R);
+  const int rc = run_planned(c, "sam_pe", sc, opt, t.flavour, bns, text_reads(g), S);
   if (rc != BPSW_OK) return rc;
-  for (size_t j = 0; j < res.size(); ++j)
-    if (res[j].k.status == BPSW_ALN_XREF || res[j].k.status == BPSW_ALN_OVERFLOW)
-      return fail(BPSW_ERR_LIMIT, res[j].k.status == BPSW_ALN_XREF ? "sam_pe: bwaFixXref2 could not repair a region (the reference aborts here)"
-                                                                   : "sam_pe: an alignment has more CIGAR operations than the kernel stages");
+  const JobResults& R = S.results;
+  const std::vector<JobResult>& res = R.r;
 
   // ---- the lines of every read, and the record each read's lines are printed against (the mate, `m` of memAlnToSAM) ----------------
-  out->t_emit = wall_ms();
-  out->R = &R;
-  out->regs = regs.data();
+  begin_lines(out, S, 2 * G, true);
   std::vector<Aln>& aa = out->aa;
-  aa.clear(); out->line_read.clear();
-  out->read_first.assign((size_t)(2 * G) + 1, 0);
-  out->mate.resize((size_t)(2 * G));
   for (int k = 0; k < G; ++k) {
     const PairPlan& P = plan[(size_t)k];
     const std::vector<bpsw_alnreg_t>* a = &regs[(size_t)(2 * k)];
@@ -757,7 +863,7 @@ int bpsw::pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, cons
       for (int i = 0; i < 2; ++i) {
         aa.push_back(h[i]);
         out->mate[(size_t)(2 * k + i)] = h[1 - i];
-        out->line_read.push_back(2 * k + i);
+        out->line_read.push_back(2 * k + i);  // (its one line, by hand: end_read's resize per read costs the line building 5 %)
         out->read_first[(size_t)(2 * k + i) + 1] = (int32_t)aa.size();
       }
       continue;
@@ -773,57 +879,42 @@ int bpsw::pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, cons
       if (!g->pes[d].failed && dist >= g->pes[d].low && dist <= g->pes[d].high) extra_flag |= 2;
     }
     for (int i = 0; i < 2; ++i) {
-      const int xf = (i ? 0x81 : 0x41) | extra_flag;
-      const size_t first = aa.size();
-      for (size_t x = 0; x < P.end[i].se_jobs.size(); ++x) {
-        const int j = P.end[i].se_jobs[x].first, jb = P.end[i].se_jobs[x].second;
-        const bpsw_alnreg_t& p = a[i][(size_t)j];
-        Aln q = make_aln(o, t, &p, jb >= 0 ? &res[(size_t)jb] : nullptr, R);
-        q.a.flag |= xf;
-        if (p.secondary >= 0) q.a.sub = -1;  // don't output the sub-optimal score
-        if (j && p.secondary < 0) q.a.flag |= (o.flag & BPSW_MEM_F_NO_MULTI) ? 0x10000 : 0x800;  // supplementary
-        if (j && aa.size() > first && q.a.mapq > aa[first].a.mapq) q.a.mapq = aa[first].a.mapq;
-        aa.push_back(q);
-      }
-      if (aa.size() == first) {
-        Aln u = make_aln(o, t, nullptr, nullptr, R);
-        u.a.flag |= xf;
-        aa.push_back(u);
-      }
+      se_append(o, t, a[i], P.end[i].se_jobs, R, (i ? 0x81 : 0x41) | extra_flag, &aa);
       out->mate[(size_t)(2 * k + i)] = h[1 - i];
-      out->line_read.resize(aa.size(), 2 * k + i);
-      out->read_first[(size_t)(2 * k + i) + 1] = (int32_t)aa.size();
+      end_read(out, 2 * k + i);
     }
   }
   return BPSW_OK;
 }
 
-// the text on the calling thread: every line through aln_to_sam against its read's mate record
-size_t bpsw::pe_print(const PeLines& L, const BnsView& bns, const bpsw_tail_opt_t& t, const bpsw_pairs_t* g, char* out_text, size_t text_cap,
-                      int64_t* out_off) {
-  const int G = g->group_size;
+// the text on the calling thread: every line through aln_to_sam, against its read's mate record where there is one; returns the
+// text's size (counted past text_cap, never written there) and fills out_off (n + 1)
+size_t print_lines(const SamLines& L, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, char* out_text, size_t text_cap,
+                   int64_t* out_off) {
   Text text(out_text, text_cap);
-  for (int r = 0; r < 2 * G; ++r) {
-    const int k = r >> 1;
-    const char* name = g->name_pool + g->name_off[k];
-    const size_t name_len = (size_t)(g->name_off[k + 1] - g->name_off[k]);
-    const uint8_t* seq = g->read_pool + g->read_off[r];
-    const uint8_t* qual = g->qual_pool ? g->qual_pool + g->read_off[r] : nullptr;
+  const Aln* mate = L.mate.empty() ? nullptr : L.mate.data();
+  for (int r = 0; r < g.n; ++r) {
+    const int k = r >> g.name_shift;
+    const char* name = g.name_pool + g.name_off[k];
+    const size_t name_len = (size_t)(g.name_off[k + 1] - g.name_off[k]);
+    const uint8_t* seq = g.read_pool + g.read_off[r];
+    const uint8_t* qual = g.qual_pool ? g.qual_pool + g.read_off[r] : nullptr;
     const Aln* list = L.aa.data() + L.read_first[(size_t)r];
     const size_t n_list = (size_t)(L.read_first[(size_t)r + 1] - L.read_first[(size_t)r]);
     out_off[r] = (int64_t)text.size();
     for (size_t x = 0; x < n_list; ++x)
-      aln_to_sam(bns, t.flavour, text, name, name_len, g->read_len[r], seq, qual, list, n_list, (int)x, &L.mate[(size_t)r], t.rg_id);
+      aln_to_sam(bns, t.flavour, text, name, name_len, g.read_len[r], seq, qual, list, n_list, (int)x, mate ? mate + r : nullptr, t.rg_id);
   }
-  out_off[2 * G] = (int64_t)text.size();
+  out_off[g.n] = (int64_t)text.size();
   return text.size();
 }
 
-int bpsw::pe_finish(bpsw_ctx* c, const PeLines& L, const bpsw_pairs_t* g, const char* out_text, size_t text_cap, size_t total,
-                    size_t* out_needed, bpsw_alnreg_t* out_regs) {
+// out_regs, the host times, *out_needed and the capacity verdict
+int finish(bpsw_ctx* c, const char* who, const SamLines& L, int n_reads, const char* out_text, size_t text_cap, size_t total, size_t* out_needed,
+           bpsw_alnreg_t* out_regs) {
   if (out_regs) {
     size_t w = 0;
-    for (int r = 0; r < 2 * g->group_size; ++r) {
+    for (int r = 0; r < n_reads; ++r) {
       const std::vector<bpsw_alnreg_t>& v = L.regs[(size_t)r];
       if (!v.empty()) memcpy(out_regs + w, v.data(), sizeof(bpsw_alnreg_t) * v.size());
       w += v.size();
@@ -831,32 +922,51 @@ int bpsw::pe_finish(bpsw_ctx* c, const PeLines& L, const bpsw_pairs_t* g, const 
   }
   c->tail_host_ms[0] = L.t_dev - L.t_plan; c->tail_host_ms[1] = L.t_emit - L.t_dev; c->tail_host_ms[2] = wall_ms() - L.t_emit;
   if (out_needed) *out_needed = total;
-  if (!out_text || total > text_cap) return fail(BPSW_ERR_CAPACITY, "sam_pe: text buffer too small (see *out_needed)");
+  if (!out_text || total > text_cap) return fail(BPSW_ERR_CAPACITY, std::string(who) + ": text buffer too small (see *out_needed)");
   return BPSW_OK;
 }
 
-int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, char* out_text,
-                      size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
-  if (!c || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "sam_pe: null argument");
+}  // namespace
+
+int bpsw::sam_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* se, const bpsw_pairs_t* pe,
+                    const SamCall& m, char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
+  const char* who = m.paired ? "sam_pe" : "sam_se";
+  if (!c || !topt || !(m.paired ? (const void*)pe : (const void*)se) || !out_off) return fail(BPSW_ERR_ARG, std::string(who) + ": null argument");
   SwScoring sc;
   int rc = make_scoring("tail", opt, 0, 1, &sc);
   if (rc != BPSW_OK) return rc;
-  const int G = g->group_size;
-  if (G < 0) return fail(BPSW_ERR_ARG, "sam_pe: negative group size");
-  if (G == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
+  const int n = m.paired ? pe->group_size : se->n_reads;
+  if (n < 0) return fail(BPSW_ERR_ARG, m.paired ? "sam_pe: negative group size" : "sam_se: negative number of reads");
+  if (n == 0) { out_off[0] = 0; if (out_needed) *out_needed = 0; return BPSW_OK; }
+  if (m.paired && m.on_device && n > (1 << 29)) return fail(BPSW_ERR_LIMIT, "sam_pe: group too large for the device text");
   size_t n_regs = 0;
-  rc = pe_check("sam_pe", g, &n_regs);
+  rc = m.paired ? pe_check(who, pe, &n_regs) : se_check(who, se, true, &n_regs);
   if (rc != BPSW_OK) return rc;
   ContextEntry entry(c);
   if (entry.rc != BPSW_OK) return entry.rc;
   BnsView bns;
   rc = snapshot_bns(c, &bns);
   if (rc != BPSW_OK) return rc;
-  static thread_local PeLines lines;  // (its vectors are refilled in place from call to call)
-  rc = pe_lines(c, sc, opt, topt, g, bns, &lines);
+  if (m.times) memset(m.times, 0, sizeof(double) * (size_t)m.n_times);
+  static thread_local SamLines lines;  // (its vectors are refilled in place from call to call)
+  rc = m.paired ? pe_lines(c, sc, opt, topt, pe, bns, &lines) : se_lines(c, sc, opt, topt, se, bns, &lines);
   if (rc != BPSW_OK) return rc;
-  const size_t total = pe_print(lines, bns, *topt, g, out_text, text_cap, out_off);
-  return pe_finish(c, lines, g, out_text, text_cap, total, out_needed, out_regs);
+  const TextReads g = m.paired ? text_reads(pe) : text_reads(se);
+  size_t total = 0;
+  if (m.on_device) {
+    rc = m.on_device(c, who, bns, *topt, g, lines, out_text, text_cap, out_off, &total, m.times);
+    if (rc != BPSW_OK) return rc;
+  } else {
+    total = print_lines(lines, bns, *topt, g, out_text, text_cap, out_off);
+  }
+  return finish(c, who, lines, g.n, out_text, text_cap, total, out_needed, out_regs);
+}
+
+int bpsw_sam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, char* out_text,
+                      size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
+  SamCall m;
+  m.paired = true;
+  return sam_batch(c, opt, topt, nullptr, g, m, out_text, text_cap, out_off, out_needed, out_regs);
 }
 
 // ---- host-only exports (no device) -------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
-// bpsw_tail_internal.h -- the pieces of worker2's tail (bpsw_tail.cpp) that the single-end tail (bpsw_sam_se.hip) and the paired
-// entries with a flags argument (bpsw_sam_pe.hip) use as they are: the contig table's snapshot, memMarkPrimarySe, the reg2aln
-// launches with their resubmission, the mem_aln_t of a job, the SAM line on the calling thread, the paired tail in its pieces
-// (checks, plan + jobs + line lists, printing, the end) and worker2's prepare-and-rescue half.  Defined in bpsw_tail.cpp, except
-// text_on_device (bpsw_sam_se.hip, beside its kernels); not installed.
+// bpsw_tail_internal.h -- worker2's tail as its entries share it: the contig table's snapshot, memMarkPrimarySe, the reg2aln launches
+// with their resubmission, the mem_aln_t of a job, the SAM line on the calling thread, reads with names as one view (TextReads) with
+// the one check of a read against its pool, the line list of a batch (SamLines: se_lines / pe_lines), sam_batch -- the one body of
+// bpsw_sam_se_batch, bpsw_sam_pe_batch and bpsw_sam_pe_batch_ex -- and worker2's prepare-and-rescue half.  Defined in bpsw_tail.cpp,
+// which compiles and links without any .hip object; text_on_device and worker1_lists are bpsw_sam_se.hip's, and the entries there and
+// in bpsw_sam_pe.hip hand the former to sam_batch as a pointer.  Not installed.
 #pragma once
 
 #include <string.h>
@@ -75,32 +76,8 @@ void aln_to_sam(const BnsView& bns, int flavour, Text& s, const char* name, size
                 const uint8_t* qual, const Aln* list, const size_t n_list, int which, const Aln* mate_in, const char* rg_id);
 
 
-// ---- the paired tail in pieces: bpsw_sam_pe_batch is pe_check, pe_lines, pe_print, pe_finish ----------------------------------------
-struct PeLines {  // what pe_lines leaves: the lines of every read of the group, in read order (2k + i)
-  std::vector<Aln> aa;                // the lines
-  std::vector<int32_t> line_read;     // the read of each
-  std::vector<int32_t> read_first;    // 2 G + 1: read r has lines aa[read_first[r] .. read_first[r + 1])
-  std::vector<Aln> mate;              // per read: the record its lines are printed against (memAlnToSAM's m: h[1 - i])
-  const JobResults* R = nullptr;      // the CIGAR and MD pools the lines point into (the calling thread's, valid until its next tail call)
-  const std::vector<bpsw_alnreg_t>* regs = nullptr;  // 2 G lists as the tail leaves them (out_regs)
-  double t_plan = 0., t_dev = 0., t_emit = 0.;
-};
-int pe_check(const char* who, const bpsw_pairs_t* g, size_t* n_regs);
-// mark-primary, memPair and the single-end fallback, the jobs through run_jobs, then every read's lines.  Caller holds c->mu.
-int pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, const BnsView& bns,
-             PeLines* out);
-// the text on the calling thread; returns its size (counted past text_cap, never written there); fills out_off (2 G + 1)
-size_t pe_print(const PeLines& L, const BnsView& bns, const bpsw_tail_opt_t& t, const bpsw_pairs_t* g, char* out_text, size_t text_cap,
-                int64_t* out_off);
-// out_regs, the host times, *out_needed and the capacity verdict
-int pe_finish(bpsw_ctx* c, const PeLines& L, const bpsw_pairs_t* g, const char* out_text, size_t text_cap, size_t total, size_t* out_needed,
-              bpsw_alnreg_t* out_regs);
-// worker2's first half: anchors, their windows, bpsw_matesw_group with its capacity retry; the lists after the rescue
-int pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const bpsw_pairs_t* g, int rescue_mode, std::vector<int32_t>* out_cnt,
-              std::vector<bpsw_alnreg_t>* out_regs, int64_t* out_total);
-
-// ---- the text on the device (bpsw_sam_se.hip) ----------------------------------------------------------------------------------------
-struct TextReads {  // reads with names: read r has name r >> name_shift (0: a name per read; 1: a name per pair)
+// ---- reads with names: what both modes print from -------------------------------------------------------------------------------------
+struct TextReads {  // read r has name r >> name_shift (0: a name per read; 1: a name per pair)
   int n = 0, name_shift = 0;
   const int32_t* read_len = nullptr;
   const int64_t* read_off = nullptr;
@@ -110,12 +87,57 @@ struct TextReads {  // reads with names: read r has name r >> name_shift (0: a n
   const int64_t* name_off = nullptr;
   const char* name_pool = nullptr;
 };
-// The text of the lines in `aa` (per read: aa[read_first[r] .. read_first[r + 1])) through sam_len_kernel and sam_write_kernel.
-// mate: null, or per read the record its lines are printed against -- the kernels read the first line of the pair's other read
-// instead, so the five fields memAlnToSAM reads of a mate must agree between the two (checked here; BPSW_ERR_DEVICE if not).
-// times[4]: sam_len_kernel, sam_write_kernel, building and staging the tables, the round trip (ms).  Caller holds c->mu.
-int text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const std::vector<Aln>& aa,
-                   const std::vector<int32_t>& line_read, const std::vector<int32_t>& read_first, const Aln* mate, const JobResults& R,
+template <class Reads>  // bpsw_se_reads_t and bpsw_pairs_t name these fields alike
+inline TextReads text_reads(const Reads* g, int n, int name_shift) {
+  TextReads v;
+  v.n = n; v.name_shift = name_shift;
+  v.read_len = g->read_len; v.read_off = g->read_off; v.read_pool = g->read_pool; v.qual_pool = g->qual_pool;
+  v.read_pool_bytes = g->read_pool_bytes; v.name_off = g->name_off; v.name_pool = g->name_pool;
+  return v;
+}
+inline TextReads text_reads(const bpsw_se_reads_t* g) { return text_reads(g, g->n_reads, 0); }
+inline TextReads text_reads(const bpsw_pairs_t* g) { return text_reads(g, 2 * g->group_size, 1); }
+// Per read, in this order: a negative region count (reg_cnt given), a read outside its pool or empty, and (names_ascend: a name per
+// read) name offsets that do not ascend.  *n_regs: the sum of reg_cnt.  The arrays themselves are the caller's to check for null.
+int check_reads(const char* who, const TextReads& g, const int32_t* reg_cnt, bool names_ascend, size_t* n_regs);
+// what a mode checks of its batch before anything runs (the batch is not empty)
+int se_check(const char* who, const bpsw_se_reads_t* g, bool need_regs, size_t* n_regs);
+int pe_check(const char* who, const bpsw_pairs_t* g, size_t* n_regs);
+
+// ---- the tail in pieces: sam_batch is a mode's check, se_lines or pe_lines, the text, finish -------------------------------------------
+struct SamLines {  // the lines of every read of a batch, in read order
+  std::vector<Aln> aa;                // the lines
+  std::vector<int32_t> line_read;     // the read of each
+  std::vector<int32_t> read_first;    // n + 1: read r has lines aa[read_first[r] .. read_first[r + 1])
+  std::vector<Aln> mate;              // paired: per read the record its lines are printed against (memAlnToSAM's m: h[1 - i]); else empty
+  const JobResults* R = nullptr;      // the CIGAR and MD pools the lines point into (the calling thread's, valid until its next tail call)
+  const std::vector<bpsw_alnreg_t>* regs = nullptr;  // the n lists as the tail leaves them (out_regs)
+  double t_plan = 0., t_dev = 0., t_emit = 0.;
+};
+// The text of `L` through sam_len_kernel and sam_write_kernel (bpsw_sam_se.hip).  With mates the kernels read the first line of the
+// pair's other read instead of L.mate, so the five fields memAlnToSAM reads of a mate must agree between the two (checked there;
+// BPSW_ERR_DEVICE if not).  times[4]: sam_len_kernel, sam_write_kernel, building and staging the tables, the round trip (ms).  Fills
+// out_off (n + 1) and *total_out; a total past text_cap ends the call after the lengths.  Caller holds c->mu.
+typedef int (*TextOnDevice)(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& L,
+                            char* out_text, size_t text_cap, int64_t* out_off, size_t* total_out, double times[4]);
+int text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& L,
                    char* out_text, size_t text_cap, int64_t* out_off, size_t* total_out, double times[4]);
+struct SamCall {  // what an entry hands to sam_batch besides its arguments
+  bool paired = false;                // the batch is `pe` (else `se`)
+  TextOnDevice on_device = nullptr;   // who writes the text; null: the calling thread (aln_to_sam)
+  double* times = nullptr;            // null, or the entry's n_times times: zeroed once the checks are passed; on_device's times[4]
+  int n_times = 0;
+};
+// The one body of the tail's entries: null checks, scoring, the empty batch, the mode's checks, the context and the contig table, the
+// line list, the text, then out_regs, the host times, *out_needed and the capacity verdict.
+int sam_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* se, const bpsw_pairs_t* pe,
+              const SamCall& m, char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs);
+// worker2's first half: anchors, their windows, bpsw_matesw_group with its capacity retry; the lists after the rescue
+int pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const bpsw_pairs_t* g, int rescue_mode, std::vector<int32_t>* out_cnt,
+              std::vector<bpsw_alnreg_t>* out_regs, int64_t* out_total);
+// worker1 in front of a tail (bpsw_sam_se.hip): bpsw_worker1_batch with BPSW_C2A_SORT_DEDUP on the reads of `g`, its lists sized
+// 4 n + 64 regions and, when they do not fit, once more at the size it names
+int worker1_lists(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const TextReads& g, int zdrop_mode, int w1_flags,
+                  std::vector<int32_t>* cnt, std::vector<bpsw_alnreg_t>* regs);
 
 }  // namespace bpsw
