@@ -312,7 +312,8 @@ __device__ void sw4_pass(const int lane, const Quartet& J, const int (&on)[4], c
     Lq[g] = on[g] ? (qCols[g] - 1) / C : 0;          // lane (within the row) that holds the last real column
     nsteps[g] = on[g] ? J.tLen[g] + Lq[g] : 0;
     maxsteps = max(maxsteps, nsteps[g]);
-    stop[g] = on[g] ? 0 : 1;
+    // (an empty window has no row to book: with a mate of up to C columns, Lq == 0, the loop below would take row 0 of it at step 0)
+    stop[g] = (on[g] && J.tLen[g] > 0) ? 0 : 1;
     mx[g] = MINUS_INF; max_i[g] = -1; max_j[g] = -1; nb[g] = 0; lastScore[g] = 0; lastT[g] = -2;
   }
   int hlast_cur = 0, hlast_old = 0, fout = 0, keyout = 0;

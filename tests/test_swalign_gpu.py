@@ -5,6 +5,7 @@ import pytest
 import bpsw_hip
 from bpsw_hip import synth
 import pyoracle as po
+from sw_cases import jobs_from as _jobs_from
 
 pytestmark = pytest.mark.gpu
 
@@ -35,17 +36,6 @@ def test_forward_only_and_stop_flags(ctx, orc):
     _check(ctx, orc, jobs, xtra=po.KSW_XSTART | po.KSW_XSUBO | 60)      # higher threshold
     _check(ctx, orc, jobs, xtra=po.KSW_XSTOP | 40)                      # early stop, no list
     _check(ctx, orc, jobs, xtra=0)
-
-
-def _jobs_from(pairs):
-    q_len, t_len, q_off, t_off, q_rev, qp, tp = [], [], [], [], [], [], []
-    for q, t, rev in pairs:
-        q_off.append(len(qp)); t_off.append(len(tp)); q_len.append(len(q)); t_len.append(len(t)); q_rev.append(rev)
-        qp.extend(q); tp.extend(t)
-        qp.extend([0] * ((-len(qp)) % 16)); tp.extend([0] * ((-len(tp)) % 16))
-    return dict(q_len=np.array(q_len, np.int32), t_len=np.array(t_len, np.int32), q_off=np.array(q_off, np.int64),
-                t_off=np.array(t_off, np.int64), q_rev=np.array(q_rev, np.uint8), q_pool=np.array(qp + [0] * 16, np.uint8),
-                t_pool=np.array(tp + [0] * 16, np.uint8))
 
 
 def test_edge_cases(ctx, orc):
