@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "bpsw_mark_primary_se", "bpsw_approx_mapq_se", "bpsw_mem_pair", "bpsw_sort_dedup", "bpsw_pe_stat",
     "bpsw_fmi_load", "bpsw_fmi_unload", "bpsw_fmi_length", "bpsw_seed_opt_default", "bpsw_seed_batch", "bpsw_chain_seeds",
     "bpsw_worker1_batch", "bpsw_last_worker1_times", "bpsw_seed_set_resident_lanes",
+    "bpsw_seed_batch_ex", "bpsw_last_seed_bytes", "bpsw_scan_set_tile",
     "bpsw_chain_batch", "bpsw_chain_set_arena_budget", "bpsw_chain_last_split",
     "bpsw_sam_se_batch", "bpsw_align_se_batch", "bpsw_last_sam_se_times",
     "bpsw_sam_pe_batch_ex", "bpsw_align_pe_batch", "bpsw_last_sam_pe_times",
@@ -119,6 +120,8 @@ class Chains(C.Structure):  # bpsw_chains_t
 
 C2A_SORT_DEDUP, C2A_DEDUP_SCALA = 1, 2
 W1_CHAIN_DEVICE = 4   # worker1_batch only: chain and filter the seeds on the device (BPSW_W1_CHAIN_DEVICE)
+W1_SEED_PLAN_DEVICE = 8   # worker1_batch only: plan the suffix-array pass on the device (BPSW_W1_SEED_PLAN_DEVICE)
+SEED_PLAN_DEVICE = 1      # seed_batch(flags=): the same for bpsw_seed_batch_ex (BPSW_SEED_PLAN_DEVICE)
 
 
 class RescueGroup(C.Structure):  # bpsw_rescue_group_t
@@ -235,6 +238,10 @@ def _bind_seeding(lib):
         "bpsw_seed_opt_default": ([C.c_void_p], None),
         "bpsw_seed_batch": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                              C.c_int64, C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_seed_batch_ex": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                C.c_int64, C.POINTER(C.c_int64), C.c_int], C.c_int),
+        "bpsw_last_seed_bytes": ([C.c_void_p], None),
+        "bpsw_scan_set_tile": ([C.c_int], None),
         "bpsw_chain_seeds": ([C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
         "bpsw_worker1_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                 C.POINTER(C.c_int64)], C.c_int),
@@ -570,23 +577,38 @@ class Context:
     def fmi_length(self) -> int:
         return int(self.lib.bpsw_fmi_length(self.h))
 
-    def seed_batch(self, sopt, reads):
-        """reads (fmi.ReadBatch) -> (intv_cnt[n], intervals (fmi.SMEM_DTYPE), seed_cnt[n], seeds (fmi.SEED_DTYPE))"""
+    def seed_batch(self, sopt, reads, flags: int | None = None, intervals: bool = True):
+        """reads (fmi.ReadBatch) -> (intv_cnt[n], intervals (fmi.SMEM_DTYPE), seed_cnt[n], seeds (fmi.SEED_DTYPE)).  With flags (0 or
+        SEED_PLAN_DEVICE) through bpsw_seed_batch_ex; intervals=False then passes no interval buffer and gives None in their place."""
         from . import fmi
         st = reads.as_struct()
         n = reads.n_reads
         icnt, scnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         icap, scap = 8 * n + 64, 16 * n + 64
+        if flags is None:
+            assert intervals
+        elif not intervals:
+            icap = 0
         while True:
-            iv, sv = np.zeros(icap, fmi.SMEM_DTYPE), np.zeros(scap, fmi.SEED_DTYPE)
+            iv, sv = (np.zeros(icap, fmi.SMEM_DTYPE) if intervals else None), np.zeros(scap, fmi.SEED_DTYPE)
             it, stt = C.c_int64(0), C.c_int64(0)
-            rc = self.lib.bpsw_seed_batch(self.h, C.byref(sopt), C.byref(st), _ptr(icnt), _ptr(iv), icap, C.byref(it), _ptr(scnt), _ptr(sv),
-                                          scap, C.byref(stt))
-            if rc == -3 and (it.value > icap or stt.value > scap):   # BPSW_ERR_CAPACITY: the totals say what is needed
-                icap, scap = max(icap, it.value), max(scap, stt.value)
+            if flags is None:
+                rc = self.lib.bpsw_seed_batch(self.h, C.byref(sopt), C.byref(st), _ptr(icnt), _ptr(iv), icap, C.byref(it), _ptr(scnt), _ptr(sv),
+                                              scap, C.byref(stt))
+            else:
+                rc = self.lib.bpsw_seed_batch_ex(self.h, C.byref(sopt), C.byref(st), _ptr(icnt), _ptr(iv), icap, C.byref(it), _ptr(scnt),
+                                                 _ptr(sv), scap, C.byref(stt), flags)
+            if rc == -3 and ((intervals and it.value > icap) or stt.value > scap):   # BPSW_ERR_CAPACITY: the totals say what is needed
+                icap, scap = (max(icap, it.value) if intervals else 0), max(scap, stt.value)
                 continue
-            _chk(self.lib, rc, "bpsw_seed_batch")
-            return icnt[:n], iv[: it.value], scnt[:n], sv[: stt.value]
+            _chk(self.lib, rc, "bpsw_seed_batch" if flags is None else "bpsw_seed_batch_ex")
+            return icnt[:n], (iv[: it.value] if intervals else None), scnt[:n], sv[: stt.value]
+
+    def last_seed_bytes(self):
+        """(H2D, D2H) bytes of this thread's last seeding stage (bpsw_last_seed_bytes)"""
+        b = (C.c_int64 * 2)()
+        self.lib.bpsw_last_seed_bytes(b)
+        return int(b[0]), int(b[1])
 
     def chain_batch(self, sopt, w: int, l_pac: int, seed_cnt, seeds, filter: bool = True):
         """bpsw_chain_batch: per read its seeds (seed_cnt[n], fmi.SEED_DTYPE in emission order) -> (chain_cnt[n], seeds per chain,

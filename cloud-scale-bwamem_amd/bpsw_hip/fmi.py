@@ -1,5 +1,5 @@
 """The FM-index as the aligner's .bwt / .sa files hold it, and the records of the seeding entries (include/bpsw.h:
-bpsw_fmi_load, bpsw_seed_batch, bpsw_chain_seeds, bpsw_worker1_batch).  Data carriers only: nothing is computed here."""
+bpsw_fmi_load, bpsw_seed_batch, bpsw_seed_batch_ex, bpsw_chain_seeds, bpsw_worker1_batch).  Data carriers only: nothing is computed here."""
 from __future__ import annotations
 
 import ctypes as C

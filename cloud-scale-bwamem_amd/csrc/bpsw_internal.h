@@ -480,6 +480,14 @@ struct ChainDevResult {
 // Caller holds c->mu and has set the device (ContextEntry).  Uses d_seed[0], [1], [3] and d_chain; leaves d_seed[4] alone.
 int chain_dev_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, int w, int64_t l_pac, const ChainDevJob& J, ChainDevResult* R);
 
+// ---- exclusive prefix sums on the device (bpsw_scan.hip) -----------------------------------------------------------------------
+// `cols` columns of n 64-bit values each, scanned in place by three launches on s: column k is data[k (n + 1) ..], and its total is left
+// in entry n of the column.  tile: items per workgroup, a multiple of 64 (scan_tile_items(): the default, or what bpsw_scan_set_tile
+// set); tile_sums: workspace of cols * scan_tiles(n, tile) values.  Nothing is waited for.
+int scan_tile_items();
+long long scan_tiles(long long n, int tile);
+hipError_t scan_exclusive_i64(hipStream_t s, long long* data, int cols, long long n, int tile, long long* tile_sums);
+
 }  // namespace bpsw
 
 struct bpsw_ctx {

@@ -19,6 +19,7 @@
 #include <optional>
 
 #include "bpsw_internal.h"
+#include "bpsw_seed_plan_core.h"
 
 using namespace bpsw;
 
@@ -279,6 +280,27 @@ __global__ __launch_bounds__(256) void seed_sa_kernel(FmiDev F, long long n_occ,
   out[t] = s;
 }
 
+// ---- the plan of the suffix-array pass on the device (BPSW_SEED_PLAN_DEVICE), one read per lane ---------------------------------------
+// What seed_run's loop over the intervals computes on the calling thread, from the rows where seed_smem_kernel left them
+// (bpsw_seed_plan_core.h): seed_plan_count_kernel writes per read the number of kept intervals and the sum of their x2, the scan of
+// bpsw_scan.hip turns both columns into kept_base[] and read_occ[] with the totals in entry n, and seed_plan_fill_kernel writes the
+// three tables seed_sa_kernel reads.  flags[1] is set when the second pass counted another number of intervals than the first.
+__global__ __launch_bounds__(256) void seed_plan_count_kernel(SeedPlanRows R, int n, const int32_t* __restrict__ cnt2, int* flags,
+                                                              long long* __restrict__ n_kept, long long* __restrict__ n_occ) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  if (R.cnt[r] > R.stride && cnt2[seed_plan_todo_index(R, r)] != R.cnt[r]) flags[1] = 1;
+  seed_plan_count(R, r, n_kept + r, n_occ + r);
+}
+__global__ __launch_bounds__(256) void seed_plan_fill_kernel(SeedPlanRows R, int n, const long long* __restrict__ kept_base,
+                                                             const long long* __restrict__ read_occ, long long* __restrict__ occ_base,
+                                                             long long* __restrict__ kept_x0, int32_t* __restrict__ kept_q) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r == 0) occ_base[kept_base[n]] = read_occ[n];  // the end of the last interval: seed_sa_kernel's search stops below it
+  if (r >= n) return;
+  seed_plan_fill(R, r, kept_base[r], read_occ[r], occ_base, kept_x0, kept_q);
+}
+
 // ---- the index, per device --------------------------------------------------------------------------------------------
 struct DeviceFmi {
   RefGate gate;
@@ -304,14 +326,19 @@ int seed_resident_waves(int num_cu, long long n_reads) {
 }
 
 thread_local double t_w1_ms[3] = {0., 0., 0.};
+thread_local int64_t t_seed_bytes[2] = {0, 0};  // H2D, D2H of the calling thread's last seed_run (bpsw_last_seed_bytes)
 
 // seeding of a validated batch: per read the intervals and the seeds (bridging ones dropped), concatenated in read order.
 // With dev_read_occ (the caller then holds c->mu through a ContextEntry of its own): the seeds stay where seed_sa_kernel wrote them,
 // at the start of c->d_seed[4], bridging ones included -- read r's are [dev_read_occ[r], dev_read_occ[r + 1]) --, and scnt / seeds
 // come back empty.
+// With plan_dev the tables of the suffix-array pass are made on the device from the interval rows (seed_plan_*_kernel and the scan):
+// the rows come back only with want_intv, for the caller; otherwise intv comes back empty.
 int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std::vector<int32_t>* icnt, std::vector<bpsw_smem_t>* intv,
-             std::vector<int32_t>* scnt, std::vector<bpsw_seed_t>* seeds, std::vector<long long>* dev_read_occ = nullptr) {
+             std::vector<int32_t>* scnt, std::vector<bpsw_seed_t>* seeds, std::vector<long long>* dev_read_occ = nullptr,
+             bool plan_dev = false, bool want_intv = true) {
   const int n = R.n_reads;
+  t_seed_bytes[0] = t_seed_bytes[1] = 0;
   int max_len = 1;
   for (int r = 0; r < n; ++r) {
     const int ql = R.read_len[r];
@@ -345,9 +372,16 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   const int i_pool = in.add(R.read_pool, R.read_pool_bytes);
   in.add(nullptr, 16);  // room behind the pool
   HIP_TRY(in.stage(c->h_stage_in, d_in, c->stream));
+  t_seed_bytes[0] += (int64_t)in.total();
   const int waves = seed_resident_waves(c->num_cu, n);
   const int list_cap = max_len + 1;
   HIP_TRY(d_arena.reserve((size_t)waves * 4 * (size_t)list_cap * 64 * sizeof(Intv)));
+  // what seed_sa_kernel reads: staged from the calling thread's loop over the intervals, or written by the plan kernels
+  const long long *d_occ_base = nullptr, *d_kept_x0 = nullptr;
+  const int2* d_kept_q = nullptr;
+  size_t nk = 0;
+  long long n_occ = 0;
+  std::vector<long long> read_occ((size_t)n + 1, 0);
   // first pass: rows of 16 records (a read of 150 bases has about five intervals); the reads that produced more are run once more
   // by themselves, each with exactly the room its count asks for -- so the records of a batch never take more than
   // 16 n + (the intervals of the overflowing reads), whatever one repeat-rich read produces
@@ -361,56 +395,152 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
                        in.dev<int32_t>(i_len), in.dev<long long>(i_off), in.dev<uint8_t>(i_pool), (Intv*)d_arena.ptr, list_cap,
                        out.dev<bpsw_smem_t>(r_rec), stride, (const long long*)nullptr, out.dev<int32_t>(r_cnt), out.dev<int>(r_ovf));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(out.fetch(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (*out.host<int>(r_ovf)) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
-    const int32_t* cnt = out.host<int32_t>(r_cnt);
-    icnt->assign(cnt, cnt + n);
-    std::vector<int32_t> todo;
-    std::vector<long long> base(1, 0);
-    for (int r = 0; r < n; ++r)
-      if (cnt[r] > stride) { todo.push_back(r); base.push_back(base.back() + cnt[r]); }
-    std::vector<bpsw_smem_t> first;  // the first pass's rows, taken out of the pinned block before the second pass reuses it
-    const bpsw_smem_t* rec = out.host<bpsw_smem_t>(r_rec);
-    const bpsw_smem_t* more = nullptr;
-    if (!todo.empty()) {
-      first.assign(rec, rec + (size_t)n * (size_t)stride);
-      rec = first.data();
-      const size_t m = todo.size();
-      StageIn in2;
-      const int i_todo = in2.add(todo.data(), 4 * m), i_base = in2.add(base.data(), 8 * (m + 1));
-      StageOut out2;
-      const int r2_cnt = out2.add(4 * m), r2_ovf = out2.add(16), r2_rec = out2.add(sizeof(bpsw_smem_t) * (size_t)base.back());
-      HIP_TRY(out2.reserve(c->h_stage_out, d_out));
-      HIP_TRY(in2.stage(c->h_stage_in, d_sa_in, c->stream));
-      HIP_TRY(hipMemsetAsync(out2.dev<int>(r2_ovf), 0, 16, c->stream));
-      const int waves2 = seed_resident_waves(c->num_cu, (long long)m);
-      hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves2), dim3(64), 0, c->stream, F, P, (int)m, in2.dev<int32_t>(i_todo),
-                         in.dev<int32_t>(i_len), in.dev<long long>(i_off), in.dev<uint8_t>(i_pool), (Intv*)d_arena.ptr, list_cap,
-                         out2.dev<bpsw_smem_t>(r2_rec), 0, in2.dev<long long>(i_base), out2.dev<int32_t>(r2_cnt), out2.dev<int>(r2_ovf));
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(out2.fetch(c->stream));
+    if (plan_dev) {
+      // Only the counts and the overflow word come back; the rows stay in d_out for the plan kernels.
+      //   d_seed[1] (d_out)    cnt | overflow word | first-pass rows                    until seed_plan_fill_kernel has run
+      //   d_seed[4] (d_sa_out) the second pass's rows                                     until seed_plan_fill_kernel has run; then
+      //                        seed_sa_kernel's seeds (both plan kernels have been waited for before it is reserved again)
+      //   d_seed[3] (d_sa_in)  todo | base (staged) | cnt2 | n_kept[n + 1] n_occ[n + 1] | flags | tile sums | occ_base kept_x0 kept_q
+      //                        until seed_sa_kernel has run; nothing is staged over it for the suffix-array pass
+      const size_t head = out.at[r_rec];
+      HIP_TRY(hipMemcpyAsync(out.h, out.d, head, hipMemcpyDeviceToHost, c->stream));
+      t_seed_bytes[1] += (int64_t)head;
       HIP_TRY(hipStreamSynchronize(c->stream));
-      const int32_t* cnt2 = out2.host<int32_t>(r2_cnt);
-      for (size_t i = 0; i < m; ++i)
-        if (cnt2[i] != (*icnt)[(size_t)todo[i]]) return fail(BPSW_ERR_DEVICE, "seed: interval counts changed between two runs");
-      more = out2.host<bpsw_smem_t>(r2_rec);
-    }
-    intv->clear();
-    size_t ti = 0;
-    for (int r = 0; r < n; ++r) {
-      const int m = (*icnt)[(size_t)r];
-      if (m <= stride) intv->insert(intv->end(), rec + (size_t)r * (size_t)stride, rec + (size_t)r * (size_t)stride + m);
-      else { intv->insert(intv->end(), more + base[ti], more + base[ti] + m); ++ti; }
+      if (*out.host<int>(r_ovf)) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
+      const int32_t* cnt = out.host<int32_t>(r_cnt);
+      icnt->assign(cnt, cnt + n);  // (the pinned block is reserved again below: cnt is not read after this)
+      std::vector<int32_t> todo;
+      std::vector<long long> base(1, 0);
+      long long n_intv = 0;
+      for (int r = 0; r < n; ++r) {
+        n_intv += (*icnt)[(size_t)r];
+        if ((*icnt)[(size_t)r] > stride) { todo.push_back(r); base.push_back(base.back() + (*icnt)[(size_t)r]); }
+      }
+      const size_t m = todo.size();
+      const int tile = scan_tile_items();
+      const long long tiles = scan_tiles(n, tile);
+      StageLayout L;
+      const size_t o_todo = L.add(4 * m), o_base = L.add(8 * (m + 1)), table_bytes = L.total();
+      const size_t o_cnt2 = L.add(4 * m), o_cols = L.add(8 * 2 * ((size_t)n + 1)), o_flags = L.add(16);  // (the flags lie right behind the columns)
+      const size_t o_tiles = L.add(8 * 2 * (size_t)tiles), o_occ = L.add(8 * ((size_t)n_intv + 1)), o_x0 = L.add(8 * (size_t)n_intv);
+      const size_t o_q = L.add(8 * (size_t)n_intv);
+      HIP_TRY(d_sa_in.reserve(L.total()));
+      uint8_t* D = (uint8_t*)d_sa_in.ptr;
+      int* d_flags = (int*)(D + o_flags);  // [0] a list of the second pass outgrew its room, [1] interval counts changed between two runs
+      HIP_TRY(hipMemsetAsync(d_flags, 0, 16, c->stream));
+      if (m) {
+        HIP_TRY(c->h_stage_in.reserve(table_bytes));  // (the reads have arrived: the stream was waited for)
+        uint8_t* hp = (uint8_t*)c->h_stage_in.ptr;
+        memcpy(hp + o_todo, todo.data(), 4 * m);
+        memcpy(hp + o_base, base.data(), 8 * (m + 1));
+        HIP_TRY(hipMemcpyAsync(D, hp, table_bytes, hipMemcpyHostToDevice, c->stream));
+        t_seed_bytes[0] += (int64_t)table_bytes;
+        HIP_TRY(d_sa_out.reserve(sizeof(bpsw_smem_t) * (size_t)base.back()));
+        const int waves2 = seed_resident_waves(c->num_cu, (long long)m);
+        hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves2), dim3(64), 0, c->stream, F, P, (int)m, (const int32_t*)(D + o_todo),
+                           in.dev<int32_t>(i_len), in.dev<long long>(i_off), in.dev<uint8_t>(i_pool), (Intv*)d_arena.ptr, list_cap,
+                           (bpsw_smem_t*)d_sa_out.ptr, 0, (const long long*)(D + o_base), (int32_t*)(D + o_cnt2), d_flags);
+        HIP_TRY(hipGetLastError());
+      }
+      SeedPlanRows PR;
+      PR.cnt = out.dev<int32_t>(r_cnt); PR.first = out.dev<bpsw_smem_t>(r_rec); PR.stride = stride;
+      PR.todo = (const int32_t*)(D + o_todo); PR.n_todo = (int)m; PR.base = (const long long*)(D + o_base);
+      PR.more = (const bpsw_smem_t*)d_sa_out.ptr;
+      long long* cols = (long long*)(D + o_cols);  // n_kept[0 .. n] then n_occ[0 .. n]; after the scan kept_base[] and read_occ[]
+      const unsigned plan_blocks = (unsigned)((n + 255) / 256);
+      hipLaunchKernelGGL(seed_plan_count_kernel, dim3(plan_blocks), dim3(256), 0, c->stream, PR, n, (const int32_t*)(D + o_cnt2), d_flags, cols,
+                         cols + n + 1);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(scan_exclusive_i64(c->stream, cols, 2, n, tile, (long long*)(D + o_tiles)));
+      hipLaunchKernelGGL(seed_plan_fill_kernel, dim3(plan_blocks), dim3(256), 0, c->stream, PR, n, (const long long*)cols,
+                         (const long long*)(cols + n + 1), (long long*)(D + o_occ), (long long*)(D + o_x0), (int32_t*)(D + o_q));
+      HIP_TRY(hipGetLastError());
+      // back: n_kept | read_occ[0 .. n] | flags, one copy; the rows only for a caller that asked for them
+      const size_t tail_bytes = 8 + 8 * ((size_t)n + 1) + 16, rec1_bytes = sizeof(bpsw_smem_t) * (size_t)n * (size_t)stride;
+      const size_t rec2_bytes = sizeof(bpsw_smem_t) * (size_t)base.back();
+      StageLayout H;
+      const size_t h_tail = H.add(tail_bytes), h_rec1 = H.add(want_intv ? rec1_bytes : 0), h_rec2 = H.add(want_intv ? rec2_bytes : 0);
+      HIP_TRY(c->h_stage_out.reserve(H.total()));
+      const uint8_t* hp = (const uint8_t*)c->h_stage_out.ptr;
+      HIP_TRY(hipMemcpyAsync((void*)(hp + h_tail), cols + n, tail_bytes, hipMemcpyDeviceToHost, c->stream));
+      t_seed_bytes[1] += (int64_t)tail_bytes;
+      if (want_intv) {
+        HIP_TRY(hipMemcpyAsync((void*)(hp + h_rec1), PR.first, rec1_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (m) HIP_TRY(hipMemcpyAsync((void*)(hp + h_rec2), PR.more, rec2_bytes, hipMemcpyDeviceToHost, c->stream));
+        t_seed_bytes[1] += (int64_t)(rec1_bytes + rec2_bytes);
+      }
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const long long* tail = (const long long*)(hp + h_tail);
+      const int* fl = (const int*)(tail + n + 2);
+      if (fl[0]) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
+      if (fl[1]) return fail(BPSW_ERR_DEVICE, "seed: interval counts changed between two runs");
+      nk = (size_t)tail[0];
+      memcpy(read_occ.data(), tail + 1, 8 * ((size_t)n + 1));
+      n_occ = read_occ[(size_t)n];
+      d_occ_base = (const long long*)(D + o_occ); d_kept_x0 = (const long long*)(D + o_x0); d_kept_q = (const int2*)(D + o_q);
+      intv->clear();
+      if (want_intv) {
+        const bpsw_smem_t *rec = (const bpsw_smem_t*)(hp + h_rec1), *more = (const bpsw_smem_t*)(hp + h_rec2);
+        size_t ti = 0;
+        for (int r = 0; r < n; ++r) {
+          const int k = (*icnt)[(size_t)r];
+          if (k <= stride) intv->insert(intv->end(), rec + (size_t)r * (size_t)stride, rec + (size_t)r * (size_t)stride + k);
+          else { intv->insert(intv->end(), more + base[ti], more + base[ti] + k); ++ti; }
+        }
+      }
+    } else {
+      HIP_TRY(out.fetch(c->stream));
+      t_seed_bytes[1] += (int64_t)out.total();
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      if (*out.host<int>(r_ovf)) return fail(BPSW_ERR_DEVICE, "seed: an interval list outgrew read_len + 1 entries");
+      const int32_t* cnt = out.host<int32_t>(r_cnt);
+      icnt->assign(cnt, cnt + n);
+      std::vector<int32_t> todo;
+      std::vector<long long> base(1, 0);
+      for (int r = 0; r < n; ++r)
+        if (cnt[r] > stride) { todo.push_back(r); base.push_back(base.back() + cnt[r]); }
+      std::vector<bpsw_smem_t> first;  // the first pass's rows, taken out of the pinned block before the second pass reuses it
+      const bpsw_smem_t* rec = out.host<bpsw_smem_t>(r_rec);
+      const bpsw_smem_t* more = nullptr;
+      if (!todo.empty()) {
+        first.assign(rec, rec + (size_t)n * (size_t)stride);
+        rec = first.data();
+        const size_t m = todo.size();
+        StageIn in2;
+        const int i_todo = in2.add(todo.data(), 4 * m), i_base = in2.add(base.data(), 8 * (m + 1));
+        StageOut out2;
+        const int r2_cnt = out2.add(4 * m), r2_ovf = out2.add(16), r2_rec = out2.add(sizeof(bpsw_smem_t) * (size_t)base.back());
+        HIP_TRY(out2.reserve(c->h_stage_out, d_out));
+        HIP_TRY(in2.stage(c->h_stage_in, d_sa_in, c->stream));
+        t_seed_bytes[0] += (int64_t)in2.total();
+        HIP_TRY(hipMemsetAsync(out2.dev<int>(r2_ovf), 0, 16, c->stream));
+        const int waves2 = seed_resident_waves(c->num_cu, (long long)m);
+        hipLaunchKernelGGL(seed_smem_kernel, dim3((unsigned)waves2), dim3(64), 0, c->stream, F, P, (int)m, in2.dev<int32_t>(i_todo),
+                           in.dev<int32_t>(i_len), in.dev<long long>(i_off), in.dev<uint8_t>(i_pool), (Intv*)d_arena.ptr, list_cap,
+                           out2.dev<bpsw_smem_t>(r2_rec), 0, in2.dev<long long>(i_base), out2.dev<int32_t>(r2_cnt), out2.dev<int>(r2_ovf));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(out2.fetch(c->stream));
+        t_seed_bytes[1] += (int64_t)out2.total();
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const int32_t* cnt2 = out2.host<int32_t>(r2_cnt);
+        for (size_t i = 0; i < m; ++i)
+          if (cnt2[i] != (*icnt)[(size_t)todo[i]]) return fail(BPSW_ERR_DEVICE, "seed: interval counts changed between two runs");
+        more = out2.host<bpsw_smem_t>(r2_rec);
+      }
+      intv->clear();
+      size_t ti = 0;
+      for (int r = 0; r < n; ++r) {
+        const int m = (*icnt)[(size_t)r];
+        if (m <= stride) intv->insert(intv->end(), rec + (size_t)r * (size_t)stride, rec + (size_t)r * (size_t)stride + m);
+        else { intv->insert(intv->end(), more + base[ti], more + base[ti] + m); ++ti; }
+      }
     }
   }
 
   // ---- seeds: one occurrence per lane, offsets from the prefix sum of the kept intervals' x2 ----
   std::vector<long long> occ_base, kept_x0;
   std::vector<int32_t> kept_q;
-  std::vector<long long> read_occ((size_t)n + 1, 0);
-  long long n_occ = 0;
-  {
+  if (!plan_dev) {
     size_t at = 0;
     for (int r = 0; r < n; ++r) {
       read_occ[(size_t)r] = n_occ;
@@ -429,19 +559,26 @@ int seed_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, const bpsw_reads_t& R, std:
   if (dev_read_occ) *dev_read_occ = read_occ;
   if (n_occ == 0) return BPSW_OK;
   if (n_occ > 0x3fffffffll) return fail(BPSW_ERR_LIMIT, "seed: more than 2^30 seed occurrences in one batch");
-  const size_t nk = occ_base.size();
-  occ_base.push_back(n_occ);
-  StageIn sin;
-  const int i_base = sin.add(occ_base.data(), 8 * (nk + 1)), i_x0 = sin.add(kept_x0.data(), 8 * nk), i_q = sin.add(kept_q.data(), 8 * nk);
   StageOut sout;
   const int r_seeds = sout.add(sizeof(bpsw_seed_t) * (size_t)n_occ);
   if (dev_read_occ) HIP_TRY(d_sa_out.reserve(sout.total()));
   else HIP_TRY(sout.reserve(c->h_stage_out, d_sa_out));
-  HIP_TRY(sin.stage(c->h_stage_in, d_sa_in, c->stream));
-  hipLaunchKernelGGL(seed_sa_kernel, dim3((unsigned)((n_occ + 255) / 256)), dim3(256), 0, c->stream, F, n_occ, (int)nk,
-                     sin.dev<long long>(i_base), sin.dev<long long>(i_x0), sin.dev<int2>(i_q), (bpsw_seed_t*)d_sa_out.ptr);
+  StageIn sin;
+  if (!plan_dev) {
+    nk = occ_base.size();
+    occ_base.push_back(n_occ);
+    const int i_base = sin.add(occ_base.data(), 8 * (nk + 1)), i_x0 = sin.add(kept_x0.data(), 8 * nk), i_q = sin.add(kept_q.data(), 8 * nk);
+    HIP_TRY(sin.stage(c->h_stage_in, d_sa_in, c->stream));
+    t_seed_bytes[0] += (int64_t)sin.total();
+    d_occ_base = sin.dev<long long>(i_base); d_kept_x0 = sin.dev<long long>(i_x0); d_kept_q = sin.dev<int2>(i_q);
+  }
+  hipLaunchKernelGGL(seed_sa_kernel, dim3((unsigned)((n_occ + 255) / 256)), dim3(256), 0, c->stream, F, n_occ, (int)nk, d_occ_base, d_kept_x0,
+                     d_kept_q, (bpsw_seed_t*)d_sa_out.ptr);
   HIP_TRY(hipGetLastError());
-  if (!dev_read_occ) HIP_TRY(sout.fetch(c->stream));
+  if (!dev_read_occ) {
+    HIP_TRY(sout.fetch(c->stream));
+    t_seed_bytes[1] += (int64_t)sout.total();
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (dev_read_occ) return BPSW_OK;
   const bpsw_seed_t* all = sout.host<bpsw_seed_t>(r_seeds);
@@ -552,6 +689,32 @@ int bpsw_seed_batch(bpsw_ctx_t* c, const bpsw_seed_opt_t* sopt, const bpsw_reads
   return BPSW_OK;
 }
 
+int bpsw_seed_batch_ex(bpsw_ctx_t* c, const bpsw_seed_opt_t* sopt, const bpsw_reads_t* reads, int32_t* intv_cnt, bpsw_smem_t* intv,
+                       int64_t intv_cap, int64_t* intv_total, int32_t* seed_cnt, bpsw_seed_t* seeds, int64_t seed_cap, int64_t* seed_total,
+                       int flags) {
+  if (flags == 0) return bpsw_seed_batch(c, sopt, reads, intv_cnt, intv, intv_cap, intv_total, seed_cnt, seeds, seed_cap, seed_total);
+  if (flags & ~BPSW_SEED_PLAN_DEVICE) return fail(BPSW_ERR_ARG, "seed_batch_ex: unknown flag");
+  if (!c || !sopt || !intv_cnt || !intv_total || !seed_cnt || !seed_total) return fail(BPSW_ERR_ARG, "seed_batch_ex: null argument");
+  int rc = check_reads("seed_batch_ex", reads);
+  if (rc != BPSW_OK) return rc;
+  *intv_total = *seed_total = 0;
+  if (reads->n_reads == 0) return BPSW_OK;
+  std::vector<int32_t> ic, sc;
+  std::vector<bpsw_smem_t> iv;
+  std::vector<bpsw_seed_t> sv;
+  rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv, nullptr, true, intv != nullptr);  // intv null: no interval leaves the device
+  if (rc != BPSW_OK) return rc;
+  for (const int32_t k : ic) *intv_total += k;
+  *seed_total = (int64_t)sv.size();
+  if ((intv && *intv_total > intv_cap) || (int64_t)sv.size() > seed_cap || (!sv.empty() && !seeds))
+    return fail(BPSW_ERR_CAPACITY, "seed_batch_ex: intv / seeds too small (the totals say what is needed)");
+  memcpy(intv_cnt, ic.data(), 4 * ic.size());
+  memcpy(seed_cnt, sc.data(), 4 * sc.size());
+  if (!iv.empty()) memcpy(intv, iv.data(), sizeof(bpsw_smem_t) * iv.size());
+  if (!sv.empty()) memcpy(seeds, sv.data(), sizeof(bpsw_seed_t) * sv.size());
+  return BPSW_OK;
+}
+
 int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_reads_t* reads, int zdrop_mode,
                        int flags, int32_t* out_cnt, bpsw_alnreg_t* out_regs, int64_t out_cap, int64_t* out_total) {
   if (!c || !opt || !sopt || !out_cnt || !out_total) return fail(BPSW_ERR_ARG, "worker1: null argument");
@@ -565,8 +728,8 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
   if (bpsw_fmi_length(c) != 2 * l_pac) return fail(BPSW_ERR_ARG, "worker1: no index is loaded, or its seq_len is not 2 * l_pac (bpsw_fmi_load)");
   for (int r = 0; r < n; ++r)
     if (reads->read_len[r] < 1) return fail(BPSW_ERR_ARG, "worker1: empty read");
-  const bool chain_on_device = (flags & BPSW_W1_CHAIN_DEVICE) != 0;
-  flags &= ~BPSW_W1_CHAIN_DEVICE;
+  const bool chain_on_device = (flags & BPSW_W1_CHAIN_DEVICE) != 0, plan_on_device = (flags & BPSW_W1_SEED_PLAN_DEVICE) != 0;
+  flags &= ~(BPSW_W1_CHAIN_DEVICE | BPSW_W1_SEED_PLAN_DEVICE);
   const double t0 = wall_ms();
   std::vector<int32_t> ic, sc;
   std::vector<bpsw_smem_t> iv;
@@ -580,7 +743,7 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
     ContextEntry entry(c);
     if (entry.rc != BPSW_OK) return entry.rc;
     std::vector<long long> read_occ;
-    rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv, &read_occ);
+    rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv, &read_occ, plan_on_device, false);
     if (rc != BPSW_OK) return rc;
     t1 = wall_ms();
     ChainDevJob J;
@@ -594,7 +757,7 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
     rbeg.reserve(R.seeds.size()); qbeg.reserve(R.seeds.size()); len.reserve(R.seeds.size());
     for (const bpsw_seed_t& s : R.seeds) { rbeg.push_back(s.rbeg); qbeg.push_back(s.qbeg); len.push_back(s.len); }
   } else {
-    rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv);
+    rc = seed_run(c, *sopt, *reads, &ic, &iv, &sc, &sv, nullptr, plan_on_device, false);
     if (rc != BPSW_OK) return rc;
     t1 = wall_ms();
     // chaining + filter per read (bpsw_chain.cpp), into the shape bpsw_chain2aln_batch takes
@@ -626,6 +789,10 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
 }
 
 void bpsw_seed_set_resident_lanes(int lanes) { g_seed_lanes.store(lanes > 0 ? lanes : 0, std::memory_order_relaxed); }
+
+void bpsw_last_seed_bytes(int64_t b[2]) {
+  if (b) memcpy(b, t_seed_bytes, sizeof t_seed_bytes);
+}
 
 void bpsw_last_worker1_times(double ms[3]) {
   if (ms) memcpy(ms, t_w1_ms, sizeof t_w1_ms);

@@ -38,6 +38,27 @@ __device__ __forceinline__ int wave_scan_add(int v) {
   v += dpp_mov<DPP_ROW_BCAST31, 0xc>(0, v);
   return v;
 }
+// the same over 64-bit values: both halves moved by the same control, one 64-bit add per step
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ long long dpp_mov64(long long src) {
+  const int lo = dpp_mov<CTRL, ROW_MASK>(0, (int)(unsigned long long)src);
+  const int hi = dpp_mov<CTRL, ROW_MASK>(0, (int)((unsigned long long)src >> 32));
+  return (long long)((unsigned long long)(unsigned)hi << 32 | (unsigned)lo);
+}
+__device__ __forceinline__ long long wave_scan_add64(long long v) {
+  v += dpp_mov64<DPP_ROW_SHR1, 0xf>(v);
+  v += dpp_mov64<DPP_ROW_SHR2, 0xf>(v);
+  v += dpp_mov64<DPP_ROW_SHR4, 0xf>(v);
+  v += dpp_mov64<DPP_ROW_SHR8, 0xf>(v);
+  v += dpp_mov64<DPP_ROW_BCAST15, 0xa>(v);
+  v += dpp_mov64<DPP_ROW_BCAST31, 0xc>(v);
+  return v;
+}
+__device__ __forceinline__ long long readlane64(long long v, int lane) {
+  const int lo = __builtin_amdgcn_readlane((int)(unsigned long long)v, lane);
+  const int hi = __builtin_amdgcn_readlane((int)((unsigned long long)v >> 32), lane);
+  return (long long)((unsigned long long)(unsigned)hi << 32 | (unsigned)lo);
+}
 constexpr int POS = 1 << 29;
 __device__ __forceinline__ int wave_scan_min(int v) {
   v = min(v, dpp_mov<DPP_ROW_SHR1, 0xf>(POS, v));

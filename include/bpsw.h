@@ -310,6 +310,7 @@ int bpsw_ref_fetch(bpsw_ctx_t *ctx, int32_t n, const int64_t *beg, const int64_t
 #define BPSW_C2A_SORT_DEDUP 1
 #define BPSW_C2A_DEDUP_SCALA 2
 #define BPSW_W1_CHAIN_DEVICE 4 /* bpsw_worker1_batch only: chain and filter the seeds on the device (bpsw_chain_batch's kernels) */
+#define BPSW_W1_SEED_PLAN_DEVICE 8 /* bpsw_worker1_batch only: plan the suffix-array pass on the device (as BPSW_SEED_PLAN_DEVICE) */
 typedef struct {
   int32_t n_reads;
   const int32_t *read_len;
@@ -378,6 +379,24 @@ int bpsw_seed_batch(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, const bpsw_rea
                     int64_t intv_cap, int64_t *intv_total, int32_t *seed_cnt, bpsw_seed_t *seeds, int64_t seed_cap,
                     int64_t *seed_total);
 
+/* bpsw_seed_batch with flags.  0: bpsw_seed_batch itself.  BPSW_SEED_PLAN_DEVICE: the tables of the suffix-array pass (which
+ * intervals are kept, the prefix sums of their x2) are made on the device by two kernels and a device-wide scan, from the interval
+ * rows where the search left them, instead of by the calling thread from rows copied to the host; seed_cnt and seeds are what
+ * bpsw_seed_batch gives, and intv_cnt and *intv_total are still returned.  intv == NULL (with intv_cap == 0) is allowed: then no
+ * interval leaves the device -- per read the counts (4 bytes), the occurrence offsets (8 bytes) and the seeds come back.  A non-null
+ * intv gets the intervals as well, fetched for the caller only.  Any other flag is BPSW_ERR_ARG. */
+#define BPSW_SEED_PLAN_DEVICE 1
+int bpsw_seed_batch_ex(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, const bpsw_reads_t *reads, int32_t *intv_cnt, bpsw_smem_t *intv,
+                       int64_t intv_cap, int64_t *intv_total, int32_t *seed_cnt, bpsw_seed_t *seeds, int64_t seed_cap,
+                       int64_t *seed_total, int flags);
+/* Diagnostics.  b[0], b[1]: the bytes staged to the device and fetched from it by the calling thread's most recent seeding stage
+ * (bpsw_seed_batch, bpsw_seed_batch_ex, or the seeding stage of bpsw_worker1_batch): what was copied, as bpsw_last_worker1_times
+ * says what was waited.  bpsw_scan_set_tile: the items one workgroup of the device scan takes (bpsw_scan.hip), process-wide; 0 = the
+ * default (2 048), other values are rounded up to a multiple of 64.  The tests lower it to reach several tiles, and a second level
+ * that loops, with a few thousand reads. */
+void bpsw_last_seed_bytes(int64_t b[2]);
+void bpsw_scan_set_tile(int items);
+
 /* Host only (no context, no GPU), one read: its seeds in emission order -> chains.  Chaining is mem_insert_seed's tree side
  * (test_and_merge against the chain with the largest pos <= rbeg, else a new chain; the chains come out in the B-tree's in-order
  * traversal, chains of equal pos included, in the order kbtree.h leaves them); with `filter` != 0 mem_chain_flt follows.
@@ -407,7 +426,9 @@ void bpsw_chain_last_split(int64_t st[4]);
  * (zdrop_mode, flags, out_* exactly as there; *out_total is set to the needed out_cap on BPSW_ERR_CAPACITY).  Needs the reference
  * (bpsw_ref_load) and an index with seq_len == 2 * l_pac on the context's device.  With BPSW_W1_CHAIN_DEVICE in flags the seeds
  * stay on the device and are chained and filtered there (as bpsw_chain_batch does; seeds bridging l_pac dropped by the kernel), and
- * only the chains come back; the regions are the same. */
+ * only the chains come back; the regions are the same.  With BPSW_W1_SEED_PLAN_DEVICE the seeding stage plans its suffix-array pass on
+ * the device (bpsw_seed_batch_ex) and the intervals do not come back; with both flags the seeding stage fetches per read its interval
+ * count and its occurrence offset and nothing else.  Neither flag is passed on to bpsw_chain2aln_batch. */
 int bpsw_worker1_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_reads_t *reads, int zdrop_mode,
                        int flags, int32_t *out_cnt, bpsw_alnreg_t *out_regs, int64_t out_cap, int64_t *out_total);
 /* Diagnostics: the number of lanes (reads in flight, a multiple of 64) seed_smem_kernel keeps resident, process-wide; 0 = the default,

@@ -4,7 +4,7 @@ synthetic genome, next to the reference's mem_chain on the same reads from oracl
 library is built.
 
     python tools/seed_throughput.py [--genome-mb 50] [--reads 100000] [--read-len 150] [--sa-intv 32] [--reps 5] [--threads 16]
-                                    [--out profiles/seed_throughput.json]
+                                    [--seed-plan-device] [--out profiles/seed_throughput.json]
 
 The chain stage both ways is slot 1 of bpsw_last_worker1_times without and with BPSW_W1_CHAIN_DEVICE on the same batch.  The
 long-read threshold (BPSW_CHAIN_DEV_MAX_SEEDS) is read once per process, and reads of a random genome have a handful of seeds,
@@ -14,7 +14,13 @@ reads of L seeds each (tests/chain_lists.py), for every L of --long-seeds: at 0 
 
 The index is built here (numpy): a random genome has practically no repeated 27-mer, so the suffix array is one sort by the
 27-base prefix and a byte-wise comparison inside the few groups that tie.  After one warm-up call the median of --reps calls is
-reported, one JSON line.  The three stage times of a bpsw_worker1_batch call come from bpsw_last_worker1_times."""
+reported, one JSON line.  The three stage times of a bpsw_worker1_batch call come from bpsw_last_worker1_times.
+
+--seed-plan-device adds the seeding stage both ways: bpsw_worker1_batch without and with BPSW_W1_SEED_PLAN_DEVICE, each without and
+with BPSW_W1_CHAIN_DEVICE, the four settings taken in turn within every repetition after one warm-up round.  Per setting and
+repetition it prints the three stage times, the calling thread's CPU time over the whole call (the stages after seeding are the same
+code both ways, so a difference is the seeding stage's) and the H2D / D2H bytes of the seeding stage from bpsw_last_seed_bytes.  A
+library without the flag (BPSW_LIB pointing at an older build) is measured on the two settings it has."""
 import argparse
 import ctypes as C
 import json
@@ -167,6 +173,36 @@ def threshold_runs(scnt, sv, l_pac, n_long, sizes, reps):
     return out
 
 
+def seed_plan_runs(ctx, opt, so, rb, reps):
+    """worker1_batch on the four settings of (seeding plan on the host / the device) x (chaining on the host / the device), in turn"""
+    has_plan = hasattr(ctx.lib, "bpsw_seed_batch_ex")
+    settings = {"plan_host__chain_host": 0, "plan_host__chain_device": bpsw_hip.W1_CHAIN_DEVICE}
+    if has_plan:
+        settings["plan_device__chain_host"] = bpsw_hip.W1_SEED_PLAN_DEVICE
+        settings["plan_device__chain_device"] = bpsw_hip.W1_SEED_PLAN_DEVICE | bpsw_hip.W1_CHAIN_DEVICE
+    runs = {k: {"stage_ms": [], "call_ms": [], "thread_cpu_ms": [], "seed_bytes_h2d_d2h": None} for k in settings}
+    want = None
+    for k in range(reps + 1):
+        for name, fl in settings.items():
+            c0, t0 = time.thread_time(), time.perf_counter()
+            cnt, regs = ctx.worker1_batch(opt, so, rb, flags=bpsw_hip.C2A_SORT_DEDUP | fl)
+            t1, c1 = time.perf_counter(), time.thread_time()
+            if want is None:
+                want = (cnt.copy(), regs.copy())
+            assert np.array_equal(cnt, want[0]) and regs.tobytes() == want[1].tobytes(), f"{name} changed the regions"
+            if k:
+                r = runs[name]
+                r["stage_ms"].append([round(x, 2) for x in bpsw_hip.last_worker1_times()])
+                r["call_ms"].append(round(1e3 * (t1 - t0), 2))
+                r["thread_cpu_ms"].append(round(1e3 * (c1 - c0), 2))
+                if has_plan:
+                    r["seed_bytes_h2d_d2h"] = list(ctx.last_seed_bytes())
+    for r in runs.values():
+        r["seeding_call_ms_median"] = round(float(np.median([s[0] for s in r["stage_ms"]])), 2)
+        r["thread_cpu_ms_median"] = round(float(np.median(r["thread_cpu_ms"])), 2)
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=50.0)
@@ -176,7 +212,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--long-reads", type=int, default=64)
-    ap.add_argument("--long-seeds", default="64,128,512,3000")
+    ap.add_argument("--long-seeds", default="64,128,512,3000", help="'' leaves the long-read runs out")
+    ap.add_argument("--seed-plan-device", action="store_true", help="also measure the seeding stage with its plan on the host and on the device")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seed_throughput.json"))
     ap.add_argument("--chain-child", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -232,8 +269,14 @@ def main():
         "reads_on_device": split[0], "reads_on_host": split[1], "slices": split[2], "arena_bytes": split[3],
         "max_seeds_in_a_read": int(scnt.max()),
     }
-    res["chain_batch_with_long_reads"] = dict(threshold_runs(scnt, sv, l_pac, a.long_reads, [int(x) for x in a.long_seeds.split(",")], a.reps),
-                                              long_reads=a.long_reads)
+    if a.seed_plan_device:
+        res["seed_plan"] = seed_plan_runs(ctx, opt, so, rb, a.reps)
+        for name, r in res["seed_plan"].items():
+            print(f"{name}: stages (seeding, chaining, round loop) ms {r['stage_ms']}; thread CPU ms {r['thread_cpu_ms']}; "
+                  f"seeding stage H2D / D2H bytes {r['seed_bytes_h2d_d2h']}", file=sys.stderr)
+    if a.long_seeds:
+        res["chain_batch_with_long_reads"] = dict(threshold_runs(scnt, sv, l_pac, a.long_reads, [int(x) for x in a.long_seeds.split(",")], a.reps),
+                                                  long_reads=a.long_reads)
     if os.path.exists(pyoracle.REF_SO):
         res["reference_mem_chain_reads_per_s"] = round(reference_mem_chain(idx, l_pac, rb, a.threads))
         res["reference_threads"] = a.threads
