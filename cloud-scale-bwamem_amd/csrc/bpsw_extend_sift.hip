@@ -12,20 +12,24 @@
 // 2 = a record per side for ext_kernel: "no form holds" (sweep at once) or "resolved when hInit >= hmin, with these results
 // relative to hInit" -- every form is linear in the start score, and the right side's start score is the left side's result, which
 // only ext_kernel knows when the left side needs the DP;  0 = not examined: ext_kernel does it all.
-// A side that this kernel does not judge (an N in either flank) is marked "not examined" and evaluated by ext_kernel's own
-// wave-wide code: the decisions are the same either way, never a guess.
+// A side that this kernel does not judge (more than three deficit columns, very long shifts) is marked "not examined" and evaluated
+// by ext_kernel's own wave-wide code: the decisions are the same either way, never a guess.
 // Restrictions (the launch checks them): wire format 1, a matrix whose sixteen base-vs-base entries are a on the diagonal and one
-// value a - dm off it (sc.exact_a > 0 says the first, `dm` is passed in), flanks up to 127 bases.
+// value a - dm off it (sc.exact_a > 0 says the first, `dm` is passed in), flanks up to 127 bases.  A flank that holds an N is judged
+// like any other when the nine entries that involve N are one value a - dn (`dn` > 0: an N column is a deficit column of its own
+// weight; a ticket of ext_kernel for such a flank costs it the certificate's scans on a whole wavefront); with any other matrix
+// (`dn` = 0) such a side is left "not examined".
 //
-// The single-gap certificate without scans.  With one mismatch score every term of bpsw_extend_core.h's conditions is a multiple of
-// dm: along a shifted diagonal a column GAINS dm where the main diagonal mismatches and the shifted one matches, LOSES dm where the
-// main one matches and the shifted one does not, and G(y) - min_{z<y} G(z) = dm * r(y) with r(y) = c(y) + max(0, r(y-1)).  So
-// W(y) = max(0, r(y)) is a counter that goes up at a gain and down (not below 0) at a loss, gains are among the <= 3 deficit columns
-// of the flank, and the conditions can only fail at a handful of columns: at a gain (insertion: dm (W + 1) >= T), at the end of the
-// range, and -- deletion, where the comparison is with the main diagonal d rows further down, tail(x) = A(min(x+d, n-1)) - A(x) --
-// wherever dm W(x) - tail(x) can rise: at x = 0, at a deficit column p, at p - d (p enters the tail), and in the last d columns (the
-// tail gets shorter).  Between such columns only the number of losses matters, and only up to W: a popcount over words, nearly
-// always one word.  Same decisions as the scans (tests/test_extend_gpu.py, tools/soak_cert2.py compare the verdicts side by side).
+// The single-gap certificate without scans.  Along a shifted diagonal a column scores c(y) = S(shifted step) - S(main step): a
+// main-diagonal match scores the matrix maximum, so c(y) <= 0 there (a LOSS of dm, or of dn where the shifted sequence holds an N),
+// and c(y) > 0 (a GAIN: dm, dn or dm - dn) only at the <= 3 deficit columns of the flank.  G(y) - min_{z<y} G(z) = r(y) with
+// r(y) = c(y) + max(0, r(y-1)), so W(y) = max(0, r(y)) is a score that goes up at a gain and down (not below 0) at a loss, and the
+// conditions can only fail at a handful of columns: at a gain (insertion: W + c >= T), at the end of the range, and -- deletion,
+// where the comparison is with the main diagonal d rows further down, tail(x) = A(min(x+d, n-1)) - A(x) -- wherever
+// W(x) - tail(x) can rise: at x = 0, at a deficit column p, at p - d (p enters the tail), and in the last d columns (the tail
+// gets shorter).  Where W = 0 nothing but the deficit columns matters; where it is above 0, a few columns behind a gain, they are
+// walked one by one.  Same decisions as the scans (tests/test_extend_gpu.py, tests/test_sift_n_gpu.py, tools/soak_cert2.py compare
+// the verdicts side by side).
 // Cites: the forms follow SWUtil.scala:61-230 / MemChainToAlignBatched.scala:789-883 exactly as bpsw_extend_core.h derives them;
 // the chaining of the two sides mirrors ext_kernel (bpsw_extend.hip).
 #include "bpsw_extend_core.h"
@@ -87,7 +91,7 @@ constexpr int SIFT_T_WORDS = 21;  // a coordinate task's staged target flank: 12
 // one wavefront per workgroup, 64 consecutive tasks
 template <bool COORD>
 __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict__ wire, const int n_tasks, int16_t* __restrict__ out,
-                                                      const ExtScoring sc, const int dm, const int qmax, uint8_t* __restrict__ flag,
+                                                      const ExtScoring sc, const int dm, const int dn, const int qmax, uint8_t* __restrict__ flag,
                                                       uint4* __restrict__ recs, const ExtPrepass* __restrict__ pre,
                                                       int* __restrict__ todo_count, int* __restrict__ todo_list, const int heavy_min) {
   // asynchronous entry (bpsw_extend_batch_device): the table scan ran just before on the same stream and nobody has read it back
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
   if (BPSW_SIFT_PRIO) __builtin_amdgcn_s_setprio(BPSW_SIFT_PRIO);
   __shared__ uint32_t raw[SIFT_RAW_WORDS + 4 + (COORD ? 2 * 64 * SIFT_T_WORDS : 0)];
   constexpr int T_BASE = SIFT_RAW_WORDS + 4;  // COORD: the target flank of (side, lane) at T_BASE + (side * 64 + lane) * SIFT_T_WORDS
-  __shared__ int items[128 * 8];   // the flanks whose closed form waits for its certificate: query stream, qs | ts << 8, target stream, n | tLen << 8, k, p0, p1, p2
+  __shared__ int items[128 * 8];   // the flanks whose closed form waits for its certificate: query stream, qs | ts << 8, target stream, n | tLen << 8, k | N columns << 2, p0, p1, p2
   __shared__ int item_fail[128];
   const int lane = threadIdx.x;
   const int task = (int)blockIdx.x * 64 + lane;
@@ -111,7 +115,7 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
   P.oIns = (int8_t)((hdr0 >> 16) & 0xff); P.eIns = (int8_t)((hdr0 >> 24) & 0xff);
   const int penClip5 = (int8_t)(hdr1 & 0xff), penClip3 = (int8_t)((hdr1 >> 8) & 0xff);
   P.wBand = (int8_t)((hdr1 >> 16) & 0xff);
-  P.zdrop = sc.zdrop; P.certify = sc.certify; P.dm = dm;
+  P.zdrop = sc.zdrop; P.certify = sc.certify; P.dm = dm; P.dn = dn;
   const int oe_min = min(P.oIns + P.eIns, P.oDel + P.eDel);
   P.a = (oe_min > 0 && P.wBand >= 2) ? sc.exact_a : 0;
 
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
     todo(live, false);
     return;
   }
-  uint32_t n_codes = 0u;  // codes above 3 (N) anywhere in the wave's streams?  (mostly none: then no lane looks for them again)
+  uint32_t n_codes = 0u;  // codes above 3 (N) anywhere in the wave's streams?  (only a matrix without a uniform N score asks)
   {
     const uint32_t* __restrict__ src = wire + (size_t)base;
     int i = lane;
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
   }
   if (lane < 4) raw[span + lane] = 0u;
   item_fail[lane] = 0; item_fail[64 + lane] = 0;
-  const bool any_n = __builtin_amdgcn_ballot_w64(n_codes != 0u) != 0ull;
+  const bool any_n = dn <= 0 && __builtin_amdgcn_ballot_w64(n_codes != 0u) != 0ull;
   __syncthreads();
   const bool mine = live && lq <= qmax && rq <= qmax;  // else not a task the short build of ext_kernel takes
   const int regScore0 = s_lo16(r3), qBeg = s_hi16(r3), h0 = s_lo16(r4);
@@ -198,12 +202,8 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
     int k = 0, p[3] = {0, 0, 0}, dI = 0, dD = 0;
     *st = CF_UNSEEN;
     if (mine && qLen > 0) {
-      uint32_t n_seen = 0u;
-      if (any_n) {  // a code above 3 (N) anywhere in the two flanks: the side is left to ext_kernel
-        for (int j = 0; j < qLen; j += 8) n_seen |= s.q8(j) & top_nibbles(qLen - j) & 0xCCCCCCCCu;
-        if (!COORD) for (int j = 0; j < rLen; j += 8) n_seen |= s.t8(j) & top_nibbles(rLen - j) & 0xCCCCCCCCu;
-      }
-      if (!n_seen) *st = sift_closed_form(s, qLen, rLen, P, r, &k, p, &dI, &dD);
+      // (no uniform N score: a side with a code above 3 anywhere in its two flanks is left to ext_kernel)
+      if (!(any_n && sift_flank_has_n(s, qLen, rLen, !COORD))) *st = sift_closed_form(s, qLen, rLen, P, r, &k, p, &dI, &dD);
     }
     const bool need = *st == CF_IF_CERTIFIED;
     const unsigned long long needs = __builtin_amdgcn_ballot_w64(need);
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
       if (slot < n_items * per) {
         const int it = slot / per, d = slot - it * per + 1;
         const int* e = items + 8 * it;
-        const int k = e[4], D = k * dm;
+        const int k = e[4], D = sift_deficit_sum(P, k);
         const int mine_d = kind ? max(0, (D - P.oDel) / P.eDel) : max(0, (D - P.oIns) / P.eIns);
         if (d <= mine_d) {
           const SiftSeq s = {raw + e[0], e[1] & 0xff, raw + e[2], e[1] >> 8};
@@ -288,13 +288,14 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
 
 }  // namespace
 
-hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int dm, int qmax,
+hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int dmn, int qmax,
                                   uint8_t* d_flag, uint4* d_recs, hipStream_t s, KernelEvents kev, const ExtPrepass* d_pre_check,
                                   int* d_todo_count, int* d_todo_list, int heavy_min) {
   if (n_tasks <= 0) return hipSuccess;
   const int blocks = (n_tasks + 63) / 64;
-  if (sc.pac) BPSW_LAUNCH(kev, ext_sift_kernel<true>, dim3(blocks), dim3(64), 0, s, d_wire, n_tasks, d_out, sc, dm, qmax, d_flag, d_recs, d_pre_check, d_todo_count, d_todo_list, heavy_min);
-  else BPSW_LAUNCH(kev, ext_sift_kernel<false>, dim3(blocks), dim3(64), 0, s, d_wire, n_tasks, d_out, sc, dm, qmax, d_flag, d_recs, d_pre_check, d_todo_count, d_todo_list, heavy_min);
+  const int dm = dmn & 0xffff, dn = dmn >> 16;
+  if (sc.pac) BPSW_LAUNCH(kev, ext_sift_kernel<true>, dim3(blocks), dim3(64), 0, s, d_wire, n_tasks, d_out, sc, dm, dn, qmax, d_flag, d_recs, d_pre_check, d_todo_count, d_todo_list, heavy_min);
+  else BPSW_LAUNCH(kev, ext_sift_kernel<false>, dim3(blocks), dim3(64), 0, s, d_wire, n_tasks, d_out, sc, dm, dn, qmax, d_flag, d_recs, d_pre_check, d_todo_count, d_todo_list, heavy_min);
   return hipGetLastError();
 }
 

@@ -3,6 +3,9 @@
 // compiles for the host -- tests/sift_host runs it on a CPU against the oracle's full DP (tests/test_sift_host.py), the GPU tests run
 // it where it ships.  The forms and their proofs are in bpsw_extend_core.h; the head of bpsw_extend_sift.hip says how the
 // certificate is evaluated without scans.
+// Scores: a where two bases 0..3 are equal, a - dm where they differ, a - dn where either code is above 3 (N) -- the launch checks
+// that the matrix has this shape (sift_uniform_dm, sift_uniform_dn); dn = 0: no uniform N score, the caller keeps every flank
+// that holds an N away from these functions (sift_flank_has_n).  tests/sift_n_host runs the N columns against the oracle.
 #pragma once
 #include <stdint.h>
 
@@ -41,10 +44,15 @@ struct SiftSeq {
 
 // the top `cnt` nibbles of a word (cnt >= 1; 8 and more: all of it)
 BPSW_HD uint32_t top_nibbles(int cnt) { return cnt >= 8 ? 0xFFFFFFFFu : 0xFFFFFFFFu << (32 - 4 * cnt); }
-// one flag (bit 0 of its nibble) per nibble in which two words of codes 0..3 differ
+// one flag (bit 0 of its nibble) per nibble in which either word holds a code above 3 (N)
+BPSW_HD uint32_t n_flags(uint32_t x, uint32_t y) {
+  const uint32_t v = x | y;
+  return ((v >> 2) | (v >> 3)) & 0x11111111u;
+}
+// one flag per nibble that is not a match: the two codes differ, or either is an N (N against N scores like any other N column)
 BPSW_HD uint32_t differ(uint32_t x, uint32_t y) {
   const uint32_t v = x ^ y;
-  return (v | (v >> 1)) & 0x11111111u;
+  return ((v | (v >> 1)) & 0x11111111u) | n_flags(x, y);
 }
 
 enum { SIFT_UNSEEN = 0, SIFT_FAIL = 1, SIFT_FORM = 2 };
@@ -56,9 +64,26 @@ struct SideRec {
 struct SiftParams {
   int a, dm;                 // match score, a - (mismatch score)
   int oDel, eDel, oIns, eIns, zdrop, certify, wBand;
+  int dn = 0;                // a - (the one score of every pair that involves an N); 0: the matrix has no such score
 };
 
-// how many of the columns lo..hi have q[y + dq] != t[y + dt]; stops counting at `cap` (lo <= hi)
+// a - S(t, q): what a step over target base t and query base q falls short of a match
+BPSW_HD int sift_deficit(const SiftParams& P, const int t, const int q) { return (t | q) > 3 ? P.dn : (t != q ? P.dm : 0); }
+// the deficit columns of a flank as one word: their number k (<= 3) in bits 0-1, bit 2 + i set when column p[i] is an N column
+BPSW_HD int sift_col_deficit(const SiftParams& P, const int kk, const int i) { return (kk >> (2 + i)) & 1 ? P.dn : P.dm; }
+BPSW_HD int sift_deficit_sum(const SiftParams& P, const int kk) {
+  const int k = kk & 3;
+  return (k > 0 ? sift_col_deficit(P, kk, 0) : 0) + (k > 1 ? sift_col_deficit(P, kk, 1) : 0) + (k > 2 ? sift_col_deficit(P, kk, 2) : 0);
+}
+// a code above 3 anywhere in the query flank or in the first tLen bases of the target flank (`with_t`: the target can hold one)
+BPSW_HD bool sift_flank_has_n(const SiftSeq& s, const int n, const int tLen, const bool with_t) {
+  uint32_t seen = 0u;
+  for (int j = 0; j < n; j += 8) seen |= s.q8(j) & top_nibbles(n - j) & 0xCCCCCCCCu;
+  if (with_t) for (int j = 0; j < tLen; j += 8) seen |= s.t8(j) & top_nibbles(tLen - j) & 0xCCCCCCCCu;
+  return seen != 0u;
+}
+
+// how many of the columns lo..hi have q[y + dq], t[y + dt] not a match; stops counting at `cap` (lo <= hi)
 BPSW_HD int sift_count_differ(const SiftSeq& s, const int lo, const int hi, const int dq, const int dt, const int cap) {
   int cnt = 0;
   for (int k = lo; k <= hi && cnt < cap; k += 8) cnt += __builtin_popcount(differ(s.q8(k + dq), s.t8(k + dt)) & top_nibbles(hi + 1 - k));
@@ -68,49 +93,50 @@ BPSW_HD bool sift_equal_run(const SiftSeq& s, const int lo, const int hi, const 
   return sift_count_differ(s, lo, hi, dq, dt, 1) == 0;
 }
 
-// One shift of single_gap_certificate (bpsw_extend_core.h) for a flank without N whose main diagonal mismatches in columns
-// p0 < p1 < p2 (the first k of them, k <= 3; D = k dm): see the head of this file.  `ins`: one insertion of d query bases, then the
-// diagonal shifted right by d; else one deletion of d target bases, then the diagonal shifted down by d.  W is only ever above 0 in
-// a short run of columns behind a gain, so the columns are walked one by one there and nowhere else; where W = 0 the deletion
-// condition is -tail(x) < T, which depends on the deficit columns alone.  The shifts of a flank are independent: the kernel spreads
-// (flank, shift) pairs over the lanes of the wavefront.
-BPSW_HD bool sift_certificate_shift(const SiftSeq& s, const int n, const int tLen, const SiftParams& P, const int k, const int p0,
+// One shift of single_gap_certificate (bpsw_extend_core.h) for a flank whose main diagonal falls short of a match in columns
+// p0 < p1 < p2 (the first k of them, k <= 3; `kk` holds k and which of them are N columns, D = their deficits summed): see the head
+// of bpsw_extend_sift.hip.  `ins`: one insertion of d query bases, then the diagonal shifted right by d; else one deletion of d target
+// bases, then the diagonal shifted down by d.  W is only ever above 0 in a short run of columns behind a gain, so the columns are
+// walked one by one there and nowhere else; where W = 0 the deletion condition is -tail(x) < T, which depends on the deficit
+// columns alone.  The shifts of a flank are independent: the kernel spreads (flank, shift) pairs over the lanes of the wavefront.
+BPSW_HD bool sift_certificate_shift(const SiftSeq& s, const int n, const int tLen, const SiftParams& P, const int kk, const int p0,
                                        const int p1, const int p2, const bool ins, const int d) {
-  const int a = P.a, dm = P.dm;
-  const auto deficits_in = [&](const int lo, const int hi) {  // deficit columns in lo..hi
-    return (int)(k > 0 && p0 >= lo && p0 <= hi) + (int)(k > 1 && p1 >= lo && p1 <= hi) + (int)(k > 2 && p2 >= lo && p2 <= hi);
+  const int a = P.a, k = kk & 3;
+  const int f0 = sift_col_deficit(P, kk, 0), f1 = sift_col_deficit(P, kk, 1), f2 = sift_col_deficit(P, kk, 2);
+  const auto deficits_in = [&](const int lo, const int hi) {  // the deficit of the columns lo..hi
+    return (k > 0 && p0 >= lo && p0 <= hi ? f0 : 0) + (k > 1 && p1 >= lo && p1 <= hi ? f1 : 0) + (k > 2 && p2 >= lo && p2 <= hi ? f2 : 0);
   };
   const auto col = [&](const int i) { return i == 0 ? p0 : (i == 1 ? p1 : p2); };
+  const auto fcol = [&](const int i) { return i == 0 ? f0 : (i == 1 ? f1 : f2); };
   if (ins) {
     if (d >= n) return true;
     const int xl = n - 1 - d, T = P.oIns + d * P.eIns;
-    const int tail_main = a * d - dm * deficits_in(xl + 1, n - 1);  // A(n-1) - A(xl)
+    const int tail_main = a * d - deficits_in(xl + 1, n - 1);  // A(n-1) - A(xl)
     int W = 0, x = 0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int p = col(i);
       if (i < k && p <= xl) {
-        while (W > 0 && x < p) { if (s.qn(x + d) != s.tn(x)) --W; ++x; }  // losses
-        if (s.qn(p + d) == s.tn(p)) {                                      // a gain
-          if (dm * (W + 1) >= T) return false;
-          ++W;
-        }
+        while (W > 0 && x < p) { W = sift_max(0, W - sift_deficit(P, s.tn(x), s.qn(x + d))); ++x; }  // losses
+        const int c = fcol(i) - sift_deficit(P, s.tn(p), s.qn(p + d));  // what the shifted step scores above the main one
+        if (c > 0 && W + c >= T) return false;                           // a gain
+        W = sift_max(0, W + c);
         x = p + 1;
       }
     }
-    while (W > 0 && x <= xl) { if (s.qn(x + d) != s.tn(x)) --W; ++x; }
-    return dm * W - tail_main <= T;  // (W = W(xl): the walk ended at xl, or at 0 before it)
+    while (W > 0 && x <= xl) { W = sift_max(0, W - sift_deficit(P, s.tn(x), s.qn(x + d))); ++x; }
+    return W - tail_main <= T;  // (W = W(xl): the walk ended at xl, or at 0 before it)
   }
   const int T = P.oDel + d * P.eDel;
   const int xmax = sift_min(n - 1, tLen - d - 1);  // the columns whose shifted cell exists
   if (xmax < 0) return true;
   const auto tail = [&](const int x) {  // A(min(x+d, n-1)) - A(x)
     const int z = sift_min(x + d, n - 1);
-    return a * (z - x) - dm * deficits_in(x + 1, z);
+    return a * (z - x) - deficits_in(x + 1, z);
   };
   // where W = 0: -tail(x) < T for every column; -tail rises only where a deficit column enters the tail (x = p - d), and in the
   // last d columns (the tail gets shorter) up to the last column or the one before a deficit column leaves it
-  if (dm * sift_min(k, d) >= T) {  // (else no window of d columns holds enough deficit)
+  if (sift_max(P.dm, P.dn) * sift_min(k, d) >= T) {  // (else no window of d columns holds enough deficit)
     if (-tail(0) >= T || -tail(xmax) >= T) return false;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -128,18 +154,18 @@ BPSW_HD bool sift_certificate_shift(const SiftSeq& s, const int n, const int tLe
     const int p = col(i);
     if (i < k && p <= xmax) {
       while (W > 0 && x < p) {
-        if (s.tn(x + d) != s.qn(x)) --W;
-        if (W > 0 && dm * W - tail(x) >= T) return false;
+        W = sift_max(0, W - sift_deficit(P, s.tn(x + d), s.qn(x)));
+        if (W > 0 && W - tail(x) >= T) return false;
         ++x;
       }
-      if (s.tn(p + d) == s.qn(p)) ++W;
-      if (W > 0 && dm * W - tail(p) >= T) return false;
+      W = sift_max(0, W + fcol(i) - sift_deficit(P, s.tn(p + d), s.qn(p)));
+      if (W > 0 && W - tail(p) >= T) return false;
       x = p + 1;
     }
   }
   while (W > 0 && x <= xmax) {
-    if (s.tn(x + d) != s.qn(x)) --W;
-    if (W > 0 && dm * W - tail(x) >= T) return false;
+    W = sift_max(0, W - sift_deficit(P, s.tn(x + d), s.qn(x)));
+    if (W > 0 && W - tail(x) >= T) return false;
     ++x;
   }
   return true;
@@ -149,9 +175,9 @@ enum { CF_HOLDS = 0, CF_IF_CERTIFIED = 1, CF_FAILS = 2, CF_UNSEEN = 3 };
 constexpr int SIFT_MAX_SHIFTS = 16;  // shifts per direction the certificate lanes take (default scoring: 9); more: left to ext_kernel
 
 // flank_closed_form of bpsw_extend_core.h for one side up to its certificate, with everything that depends on the start score
-// factored out (hmin, *_rel).  n = qLen (1..127), tLen = the target flank's length; the sequences hold no N.  CF_IF_CERTIFIED: `rec`
-// is the result provided every shift 1..dI (insertion) and 1..dD (deletion) passes sift_certificate_shift for the deficit columns
-// p[0..k).
+// factored out (hmin, *_rel).  n = qLen (1..127), tLen = the target flank's length.  CF_IF_CERTIFIED: `rec` is the result provided
+// every shift 1..dI (insertion) and 1..dD (deletion) passes sift_certificate_shift for the deficit columns p[0..k), *k_out being
+// the word that function takes (k and which columns are N columns).
 BPSW_HD int sift_closed_form(const SiftSeq& s, const int n, const int tLen, const SiftParams& P, SideRec* rec, int* k_out, int* p,
                                 int* dI, int* dD) {
   if (tLen < n) return CF_FAILS;
@@ -162,16 +188,23 @@ BPSW_HD int sift_closed_form(const SiftSeq& s, const int n, const int tLen, cons
   const int limit = P.certify ? (two_opens ? 2 * oe_min + 2 : 2 * oe_min) : oe_min;
   int D = 0, best_rel = 0, best_i = -1, k = 0;
   int p_last = -1, p_prev = -1, p_prev2 = -1;
+  int nmask = 0;  // which of p_prev2, p_prev, p_last (bits 0, 1, 2) are N columns
   for (int j = 0; j < n; j += 8) {
-    uint32_t m = differ(s.q8(j), s.t8(j)) & top_nibbles(n - j);
+    const uint32_t qw = s.q8(j), tw = s.t8(j);
+    uint32_t m = differ(qw, tw) & top_nibbles(n - j);
+    const uint32_t nn = n_flags(qw, tw);
     while (m) {  // the (very few) diagonal cells that are not a match
       const int i = __builtin_clz(m) >> 2;
-      m &= ~(0x10000000u >> (4 * i));
+      const uint32_t bit = 0x10000000u >> (4 * i);
+      m &= ~bit;
       const int pos = j + i;
+      const bool is_n = (nn & bit) != 0u;
+      if (is_n && P.dn <= 0) return CF_UNSEEN;  // (sift_flank_has_n keeps such flanks away)
       const int v = pos * a - D;  // m(pos-1) - h0: the last row before this deficit
       if (pos >= 1 && v > best_rel) { best_rel = v; best_i = pos - 1; }
-      D += dm;
+      D += is_n ? P.dn : dm;
       p_prev2 = p_prev; p_prev = p_last; p_last = pos;
+      nmask = (nmask >> 1) | (is_n ? 4 : 0);
       ++k;
       if (D >= limit) return CF_FAILS;
     }
@@ -183,7 +216,7 @@ BPSW_HD int sift_closed_form(const SiftSeq& s, const int n, const int tLen, cons
   if (D >= oe_min && (k > 3 || *dI > SIFT_MAX_SHIFTS || *dD > SIFT_MAX_SHIFTS)) return CF_UNSEEN;
   if (D >= 2 * oe_min) {  // two gap opens: tests 1 and 2 of flank_closed_form
     const auto is_match = [&](const int ti, const int qi) {
-      return ti >= 0 && qi >= 0 && ti < tLen && qi < n && s.tn(ti) == s.qn(qi);
+      return ti >= 0 && qi >= 0 && ti < tLen && qi < n && sift_deficit(P, s.tn(ti), s.qn(qi)) == 0;
     };
     for (int L = 2; L <= 2 + (D - 2 * oe_min); ++L) {
       if (is_match(p_last, p_last + L)) {
@@ -205,7 +238,7 @@ BPSW_HD int sift_closed_form(const SiftSeq& s, const int n, const int tLen, cons
   rec->kind = SIFT_FORM; rec->hmin = D + 1;
   rec->max_rel = best_rel; rec->g_rel = g_rel; rec->qle = best_i + 1; rec->tle = best_i + 1; rec->gtle = n; rec->max_off = 0;
   if (D < oe_min) return CF_HOLDS;
-  *k_out = k;  // ascending deficit columns
+  *k_out = k | ((k == 1 ? nmask >> 2 : (k == 2 ? nmask >> 1 : nmask)) << 2);  // ascending deficit columns
   p[0] = k == 1 ? p_last : (k == 2 ? p_prev : p_prev2); p[1] = k == 2 ? p_last : p_prev; p[2] = p_last;
   return CF_IF_CERTIFIED;
 }
@@ -225,27 +258,30 @@ BPSW_HD bool sift_start_gap_form(const SiftSeq& s, const int n, const int tLen, 
   if (!ins && !del) return false;
   if (del2) del2 = sift_equal_run(s, 0, n - 1, 0, 2);
   if (ins && (del || del2)) return false;
-  // the main diagonal must never get back above h0: S(j) = a(j+1) - dm * (mismatches up to j) <= 0 for every j < sift_min(n, tLen);
+  // the main diagonal must never get back above h0: S(j) = a(j+1) - (the deficits up to j) <= 0 for every j < sift_min(n, tLen);
   // S peaks on the last base of a run of matches
   {
     const int nt = sift_min(n, tLen);
-    int mm = 0;
+    int D = 0;
     for (int j = 0; j < nt; j += 8) {
-      uint32_t m = differ(s.q8(j), s.t8(j)) & top_nibbles(nt - j);
+      const uint32_t qw = s.q8(j), tw = s.t8(j);
+      uint32_t m = differ(qw, tw) & top_nibbles(nt - j);
+      const uint32_t nn = n_flags(qw, tw);
       while (m) {
         const int i = __builtin_clz(m) >> 2;
-        m &= ~(0x10000000u >> (4 * i));
+        const uint32_t bit = 0x10000000u >> (4 * i);
+        m &= ~bit;
         const int pos = j + i;
-        if (pos * a - dm * mm > 0) return false;  // S(pos - 1)
-        ++mm;
+        if (pos * a - D > 0) return false;  // S(pos - 1)
+        D += (nn & bit) ? P.dn : dm;
       }
     }
-    if (nt * a - dm * mm > 0) return false;
+    if (nt * a - D > 0) return false;
   }
   if (del) {
-    const int s0 = s.tn(0) == s.qn(0) ? a : a - dm;
+    const int s0 = a - sift_deficit(P, s.tn(0), s.qn(0));
     if (s0 + oe + 1 <= 0) return false;
-    if (s.tn(0) == s.qn(1) || s.tn(0) == s.qn(2)) return false;  // n >= 5 here
+    if (sift_deficit(P, s.tn(0), s.qn(1)) == 0 || sift_deficit(P, s.tn(0), s.qn(2)) == 0) return false;  // n >= 5 here
     const int g_rel = -oe + a * n;
     rec->kind = SIFT_FORM; rec->hmin = sift_max(2 * oe + 1, a - s0 + 1);  // h0 >= 2 oe + 1 and h0 + s0 > a
     rec->max_rel = g_rel; rec->g_rel = g_rel; rec->qle = n; rec->tle = n + 1; rec->gtle = n + 1; rec->max_off = 1;

@@ -89,8 +89,9 @@ hipError_t launch_ext_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out
                              const int* d_todo_list = nullptr);
 // The sift kernel (bpsw_extend_sift.hip): the exact shortcuts of every task of a format-1 batch, one task per lane, in front of
 // the short ext_kernel, which reads d_flag[task] (1: record written, skip; 2: d_recs[2 task + side] holds the verdict per side).
-// dm = a - (the one mismatch score of the matrix), sift_uniform_dm(); qmax = the longest flank the short build takes.
-hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int dm, int qmax,
+// dmn = dm | dn << 16: dm = a - (the one mismatch score of the matrix), sift_uniform_dm(); dn = a - (the one score of the pairs with an N),
+// sift_uniform_dn(), or 0 (then a side with an N is left to ext_kernel); qmax = the longest flank the short build takes.
+hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int dmn, int qmax,
                                   uint8_t* d_flag, uint4* d_recs, hipStream_t s, KernelEvents kev = KernelEvents(),
                                   const ExtPrepass* d_pre_check = nullptr, int* d_todo_count = nullptr, int* d_todo_list = nullptr,
                                   int heavy_min = 0);
@@ -100,6 +101,7 @@ hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* 
 // counts are the third and fourth word of the queue heads, d_counter[2..3]: zero between launches, ext_kernel's last wave puts
 // them back.)
 int sift_uniform_dm(const int8_t mat[25], int exact_a);  // > 0 when all twelve base-vs-other-base entries equal exact_a - dm, else 0
+int sift_uniform_dn(const int8_t mat[25], int exact_a);  // > 0 when all nine entries that involve N equal exact_a - dn, else 0
 // ---- local SW (boundary 1) ---------------------------------------------------------------------
 struct SwScoring {
   MatRows mat;

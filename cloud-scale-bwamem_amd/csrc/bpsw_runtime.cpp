@@ -128,6 +128,14 @@ int sift_uniform_dm(const int8_t mat[25], int exact_a) {
   return exact_a - mm > 0 ? exact_a - mm : 0;
 }
 
+int sift_uniform_dn(const int8_t mat[25], int exact_a) {
+  if (exact_a <= 0) return 0;
+  const int sn = mat[4];
+  for (int i = 0; i < 5; ++i)
+    if (mat[5 * i + 4] != sn || mat[20 + i] != sn) return 0;
+  return exact_a - sn > 0 ? exact_a - sn : 0;
+}
+
 void apply_shortcuts(int mask, const int8_t mat[25], int* exact_a, int* certify, int* tail_bound) {
   *exact_a = (mask & 1) ? exact_match_score(mat) : 0;
   int lvl = *exact_a > 0 ? certify_level(mat) : 0;
@@ -836,7 +844,7 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
           KernelEvents sev;
           sev.start = kev.start; kev.start = nullptr;
           todo_guard.armed = true;
-          HIP_TRY(launch_ext_sift_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, sift_dm, 127, d_sflag, d_srecs, s, sev, nullptr,
+          HIP_TRY(launch_ext_sift_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, sift_dm | (sift_uniform_dn(c->ext_mat, c->ext_sc.exact_a) << 16), 127, d_sflag, d_srecs, s, sev, nullptr,
                                          d_queue + 2, d_todo, heavy_min));
         }
         HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, std::min(mq, 255), mr_short, c->num_cu, d_queue, nullptr, s,
@@ -998,7 +1006,7 @@ int bpsw_extend_batch_device(bpsw_ctx_t* c, const void* d_wire, size_t wire_byte
       HIP_TRY(c->d_sift.reserve(sift_rec_off + 32 * (size_t)n_tasks));
       d_sflag = (uint8_t*)c->d_sift.ptr;
       d_srecs = (uint4*)((char*)c->d_sift.ptr + sift_rec_off);
-      HIP_TRY(launch_ext_sift_kernel((const uint32_t*)d_wire, n_tasks, (int16_t*)d_out, c->ext_sc, sift_dm, 127, d_sflag, d_srecs, s, KernelEvents(), d_pre));
+      HIP_TRY(launch_ext_sift_kernel((const uint32_t*)d_wire, n_tasks, (int16_t*)d_out, c->ext_sc, sift_dm | (sift_uniform_dn(c->ext_mat, c->ext_sc.exact_a) << 16), 127, d_sflag, d_srecs, s, KernelEvents(), d_pre));
     }
     HIP_TRY(launch_ext_kernel((const uint32_t*)d_wire, n_tasks, (int16_t*)d_out, c->ext_sc, qcap, rcap, c->num_cu, d_queue, nullptr, s,
                               d_pre, true, KernelEvents(), true, d_list, -255, d_sflag, d_srecs));

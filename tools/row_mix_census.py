@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which DP rows a bench-shaped extension batch sweeps, by what the row loops of csrc/bpsw_extend_rows.h care about: CPU only.
-The host build of the sift arithmetic (tests/sift_host) says which sides the exact shortcuts resolve; every other side is swept
+The host build of the sift arithmetic (tests/sift_n_host: flanks with N included) says which sides the exact shortcuts resolve; every other side is swept
 row by row here (the recurrences of SWUtil.scala:61-230 in the kernels' parallel form, checked against the oracle's result) and
 every row is binned by: columns per lane the band needs (1: <= 63 columns, 2), phase of h1 (live / dead), band end at the query
 end, zero cell in the band (the trimming's slow path), row improved the maximum, row at or past the query end (tail).
@@ -28,18 +28,18 @@ orc = po.Oracle()
 mat = po.default_mat().reshape(5, 5).astype(np.int64)
 
 # the host sift
-here = os.path.join(ROOT, "tests", "sift_host")
-so = os.path.join(here, "_build", "libsift_host.so")
+here = os.path.join(ROOT, "tests", "sift_n_host")
+so = os.path.join(here, "_build", "libsift_n_host.so")
 os.makedirs(os.path.dirname(so), exist_ok=True)
 hdr = os.path.join(ROOT, "cloud-scale-bwamem_amd", "csrc")
-subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + hdr, "-o", so, os.path.join(here, "sift_host.cpp")], check=True)
+subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + hdr, "-o", so, os.path.join(here, "sift_n_host.cpp")], check=True)
 lib = C.CDLL(so)
 n = soa.n
 out = np.zeros(10 * n, np.int16); flag = np.zeros(n, np.uint8); kinds = np.zeros(2 * n, np.uint8)
 w32 = np.ascontiguousarray(wire).view(np.uint32)
-lib.sift_host_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] * 1 + [C.c_int] * 5 + [C.c_void_p] * 3
+lib.sift_n_host_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int] * 1 + [C.c_int] * 6 + [C.c_void_p] * 3
 qmax = 127 if W["read_len"] <= 150 else 0   # the sift kernel is not launched for batches with longer flanks
-rc = lib.sift_host_batch(w32.ctypes.data, w32.size, n, 100, 3, 1, 5, qmax, out.ctypes.data, flag.ctypes.data, kinds.ctypes.data)
+rc = lib.sift_n_host_batch(w32.ctypes.data, w32.size, n, 100, 3, 1, 5, 2, qmax, out.ctypes.data, flag.ctypes.data, kinds.ctypes.data)   # default matrix: a 1, dm 5, dn 2
 assert rc == 0
 SIFT_FORM = 2  # bpsw_extend_sift_core.h: SIFT_UNSEEN 0, SIFT_FAIL 1, SIFT_FORM 2
 
@@ -127,7 +127,7 @@ for tsk in pick:
         hinit = reg if side else h
         want, _ = orc.sw_extend(q.astype(np.uint8), t.astype(np.uint8), po.default_mat(), soa.o_del, soa.e_del, soa.o_ins, soa.e_ins, soa.w, 5, 100, hinit)
         sides_all += 1
-        if kinds[2 * tsk + side] != SIFT_FORM:  # the DP (a side the sift did not examine may still be resolved by ext_kernel's own forms: slight overcount)
+        if kinds[2 * tsk + side] != SIFT_FORM:  # the DP (a side the sift did not examine -- four deficit columns or more -- may still be resolved by ext_kernel's own forms: slight overcount)
             st = collections.Counter()
             got = sweep(q, t, hinit, soa.w, st, 5)
             # (the tail-row bound ends the sweep early without changing the result)
