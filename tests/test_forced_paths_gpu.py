@@ -26,7 +26,7 @@ def _forced(files, extra_k=""):
 
 
 def test_extension_suites_with_the_sift_kernel_on_every_batch():
-    _forced(["test_golden_gpu.py", "test_extend_gpu.py", "test_extend_coords_gpu.py", "test_chain2aln_gpu.py"])
+    _forced(["test_golden_gpu.py", "test_extend_gpu.py", "test_ext_forms_gpu.py", "test_extend_coords_gpu.py", "test_chain2aln_gpu.py"])
 
 
 def test_boundary_1_suites_with_every_sw_batch_on_the_ring():

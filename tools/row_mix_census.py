@@ -17,6 +17,7 @@ for p in ("cloud-scale-bwamem_amd", "oracle", "tests", ""):
 import numpy as np  # noqa: E402
 import bench  # noqa: E402
 import bpsw_hip  # noqa: E402
+import ext_rows_model as erm  # noqa: E402
 import pyoracle as po  # noqa: E402
 
 cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 3
@@ -45,69 +46,13 @@ SIFT_FORM = 2  # bpsw_extend_sift_core.h: SIFT_UNSEEN 0, SIFT_FAIL 1, SIFT_FORM 
 
 
 def sweep(q, t, h0, w, stats, end_bonus):
-    global span_hist
-    """one SWExtend call; returns (max, qle, tle, gtle, gscore, max_off) and bins its rows"""
-    oD, eD, oI, eI = soa.o_del, soa.e_del, soa.o_ins, soa.e_ins
-    qlen, tlen = len(q), len(t)
-    amax = 1
-    max_ins = max(1, int((qlen * amax + end_bonus - oI) / eI + 1.0)); w = min(w, max_ins)
-    max_del = max(1, int((qlen * amax + end_bonus - oD) / eD + 1.0)); w = min(w, max_del)
-    H = np.zeros(qlen + 2, np.int64); E = np.zeros(qlen + 2, np.int64)
-    H[0] = h0
-    if qlen >= 1:
-        H[1] = h0 - (oI + eI) if h0 > oI + eI else 0
-    j = 2
-    while j <= qlen and H[j - 1] > eI:
-        H[j] = H[j - 1] - eI; j += 1
-    mx, max_i, max_j, max_ie, gscore, max_off = h0, -1, -1, -1, -1, 0
-    beg, end = 0, qlen
-    sc = mat[:, q] if qlen else np.zeros((5, 0), np.int64)
-    for i in range(tlen):
-        h1 = max(0, h0 - (oD + eD * (i + 1)))
-        beg = max(beg, i - w); end = min(end, i + w + 1, qlen)
-        # tail-row bound (bpsw_extend_core.h tail_row_bound): the kernels stop here
-        if i >= qlen:
-            U = max(h0 + qlen * amax - oD - (i - qlen + 1) * eD, qlen * amax)
-            if U <= mx and U < gscore:
-                break
-        span = end - beg
-        span_hist[min(span, 255) // 8] += 1
-        key = ("cols2" if span > 63 else "cols1", "live" if h1 > 0 else "dead", "atend" if end == qlen else "inner", "tail" if i >= qlen else "body")
-        if span > 0:
-            js = np.arange(beg, end)
-            a = np.maximum(H[js] + sc[t[i], js], E[js])
-            g = a + js * eI - (oI + eI)
-            pre = np.maximum.accumulate(g)
-            F = np.concatenate(([0], np.maximum(0, pre[:-1] - (js[1:] - 1) * eI)))
-            Hn = np.maximum(a, F)
-            m = int(Hn.max()); mj = int(js[len(js) - 1 - int(np.argmax(Hn[::-1]))])
-            E[js] = np.maximum(np.maximum(E[js] - eD, Hn - (oD + eD)), 0)
-            H[beg] = h1; H[beg + 1:end + 1] = Hn
-            E[end] = 0
-            hlast = int(Hn[-1])
-        else:
-            m, mj, hlast = 0, -1, h1
-            H[end] = h1; E[end] = 0
-        if (end if span > 0 else beg) == qlen and gscore <= hlast:
-            max_ie, gscore = i, hlast
-        zero = span > 0 and bool((Hn == 0).any())
-        imp = m > mx
-        stats[key + ("zero" if zero else "nozero", "imp" if imp else "noimp")] += 1
-        if m == 0:
-            break
-        if imp:
-            mx, max_i, max_j = m, i, mj; max_off = max(max_off, abs(mj - i))
-        else:
-            k = (i - max_i) - (mj - max_j)
-            if k > 0 and (mx - m) + k * eI > 100:   # Scala parse (bpsw_extend_rows.h)
-                break
-        j = mj
-        while j >= beg and H[j] > 0: j -= 1
-        beg = j + 1
-        j = mj + 2
-        while j <= end and H[j] > 0: j += 1
-        end = j
-    return np.array([mx, max_j + 1, max_i + 1, max_ie + 1, gscore, max_off])
+    """one SWExtend call (tests/ext_rows_model.py: the row-by-row model the named case tables are held to); returns
+    (max, qle, tle, gtle, gscore, max_off) and bins its rows"""
+    sc = erm.Scoring(o_del=soa.o_del, e_del=soa.e_del, o_ins=soa.o_ins, e_ins=soa.e_ins, w=w)
+    qlen, amax = len(q), 1
+    max_ins = max(1, int((qlen * amax + end_bonus - sc.o_ins) / sc.e_ins + 1.0)); w = min(w, max_ins)
+    max_del = max(1, int((qlen * amax + end_bonus - sc.o_del) / sc.e_del + 1.0)); w = min(w, max_del)
+    return erm.sweep(q, t, h0, sc, w, tail_bound=True, stats=stats, span_hist=span_hist).res
 
 
 stats = collections.Counter()
