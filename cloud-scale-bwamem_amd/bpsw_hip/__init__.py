@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "bpsw_worker1_batch", "bpsw_last_worker1_times", "bpsw_seed_set_resident_lanes",
     "bpsw_seed_batch_ex", "bpsw_last_seed_bytes", "bpsw_scan_set_tile",
     "bpsw_chain_batch", "bpsw_chain_set_arena_budget", "bpsw_chain_last_split",
+    "bpsw_chain_batch_ex", "bpsw_last_chain_bytes",
     "bpsw_sam_se_batch", "bpsw_align_se_batch", "bpsw_last_sam_se_times",
     "bpsw_sam_pe_batch_ex", "bpsw_align_pe_batch", "bpsw_last_sam_pe_times",
 ]
@@ -121,7 +122,9 @@ class Chains(C.Structure):  # bpsw_chains_t
 C2A_SORT_DEDUP, C2A_DEDUP_SCALA = 1, 2
 W1_CHAIN_DEVICE = 4   # worker1_batch only: chain and filter the seeds on the device (BPSW_W1_CHAIN_DEVICE)
 W1_SEED_PLAN_DEVICE = 8   # worker1_batch only: plan the suffix-array pass on the device (BPSW_W1_SEED_PLAN_DEVICE)
+W1_CHAINS_RESIDENT = 16   # worker1_batch only: W1_CHAIN_DEVICE, and the round loop reads the chains on the device (BPSW_W1_CHAINS_RESIDENT)
 SEED_PLAN_DEVICE = 1      # seed_batch(flags=): the same for bpsw_seed_batch_ex (BPSW_SEED_PLAN_DEVICE)
+CHAIN_TABLES_DEVICE = 1   # chain_batch(flags=): the resident tables, fetched for the caller (BPSW_CHAIN_TABLES_DEVICE)
 
 
 class RescueGroup(C.Structure):  # bpsw_rescue_group_t
@@ -249,6 +252,9 @@ def _bind_seeding(lib):
         "bpsw_seed_set_resident_lanes": ([C.c_int], None),
         "bpsw_chain_batch": ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                               C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_chain_batch_ex": ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int], C.c_int),
+        "bpsw_last_chain_bytes": ([C.c_void_p], None),
         "bpsw_chain_set_arena_budget": ([C.c_int64], None),
         "bpsw_chain_last_split": ([C.c_void_p], None),
         # single-end reads to SAM (bpsw_sam_se.hip): as little part of the host-only sanitizer builds as the seeding entries
@@ -610,9 +616,10 @@ class Context:
         self.lib.bpsw_last_seed_bytes(b)
         return int(b[0]), int(b[1])
 
-    def chain_batch(self, sopt, w: int, l_pac: int, seed_cnt, seeds, filter: bool = True):
+    def chain_batch(self, sopt, w: int, l_pac: int, seed_cnt, seeds, filter: bool = True, flags: int = 0):
         """bpsw_chain_batch: per read its seeds (seed_cnt[n], fmi.SEED_DTYPE in emission order) -> (chain_cnt[n], seeds per chain,
-        seeds in chain order), per read what chain_seeds gives, concatenated in read order"""
+        seeds in chain order), per read what chain_seeds gives, concatenated in read order.  With flags (CHAIN_TABLES_DEVICE) through
+        bpsw_chain_batch_ex."""
         from . import fmi
         seed_cnt = np.ascontiguousarray(seed_cnt, np.int32)
         seeds = np.ascontiguousarray(seeds, fmi.SEED_DTYPE)
@@ -623,12 +630,16 @@ class Context:
         while True:
             cnt, out = np.zeros(ccap, np.int32), np.zeros(scap, fmi.SEED_DTYPE)
             ct, st = C.c_int64(0), C.c_int64(0)
-            rc = self.lib.bpsw_chain_batch(self.h, C.byref(sopt), w, l_pac, n, _ptr(seed_cnt), _ptr(seeds), 1 if filter else 0, _ptr(chain_cnt),
-                                           _ptr(cnt), ccap, _ptr(out), scap, C.byref(ct), C.byref(st))
+            if flags == 0:
+                rc = self.lib.bpsw_chain_batch(self.h, C.byref(sopt), w, l_pac, n, _ptr(seed_cnt), _ptr(seeds), 1 if filter else 0, _ptr(chain_cnt),
+                                               _ptr(cnt), ccap, _ptr(out), scap, C.byref(ct), C.byref(st))
+            else:
+                rc = self.lib.bpsw_chain_batch_ex(self.h, C.byref(sopt), w, l_pac, n, _ptr(seed_cnt), _ptr(seeds), 1 if filter else 0,
+                                                  _ptr(chain_cnt), _ptr(cnt), ccap, _ptr(out), scap, C.byref(ct), C.byref(st), flags)
             if rc == -3 and (ct.value > ccap or st.value > scap):   # BPSW_ERR_CAPACITY: the totals say what is needed
                 ccap, scap = max(ccap, ct.value), max(scap, st.value)
                 continue
-            _chk(self.lib, rc, "bpsw_chain_batch")
+            _chk(self.lib, rc, "bpsw_chain_batch" if flags == 0 else "bpsw_chain_batch_ex")
             return chain_cnt[:n], cnt[: ct.value], out[: st.value]
 
     def worker1_batch(self, opt: Opt, sopt, reads, zdrop_mode: int = ZDROP_SCALA, flags: int = 0):
@@ -707,6 +718,13 @@ def chain_last_split():
     st = (C.c_int64 * 4)()
     load_library().bpsw_chain_last_split(st)
     return tuple(st)
+
+
+def last_chain_bytes():
+    """(H2D, D2H) bytes of this thread's last chain stage on the device (bpsw_last_chain_bytes)"""
+    b = (C.c_int64 * 2)()
+    load_library().bpsw_last_chain_bytes(b)
+    return int(b[0]), int(b[1])
 
 
 def last_worker1_times():

@@ -479,8 +479,35 @@ struct ChainDevResult {
   std::vector<int32_t> chain_cnt, chain_seed_cnt;
   std::vector<bpsw_seed_t> seeds;
 };
-// Caller holds c->mu and has set the device (ContextEntry).  Uses d_seed[0], [1], [3] and d_chain; leaves d_seed[4] alone.
-int chain_dev_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, int w, int64_t l_pac, const ChainDevJob& J, ChainDevResult* R);
+// The chains of a batch left on the device in read order (chain_dev_run with a ChainTablesDev): what ChainBatchDev takes of them, in
+// the context's d_chain_tab, which nothing else reserves -- the pointers hold until the context's next chain stage.
+struct ChainTablesDev {
+  const int32_t* chain_cnt;    // per read
+  const int32_t* chain_base;
+  const long long* reg_base;
+  const int32_t* seed_cnt;     // per chain
+  const long long* seed_base;
+  const long long* seed_rbeg;  // per seed
+  const int32_t* seed_qbeg;
+  const int32_t* seed_len;
+  long long nchains, nseeds;
+  int max_seeds;               // the largest seed count of any chain (0: no chain)
+};
+// Caller holds c->mu and has set the device (ContextEntry).  Uses d_seed[0], [1], [3] and d_chain; leaves d_seed[4] alone.  With T
+// the chains stay on the device (R is not filled and may be null): d_seed[1] holds the counts of a slice, d_chain_tab the pools and tables.
+int chain_dev_run(bpsw_ctx* c, const bpsw_seed_opt_t& so, int w, int64_t l_pac, const ChainDevJob& J, ChainDevResult* R,
+                  ChainTablesDev* T = nullptr);
+
+// ---- the round loop in two halves (bpsw_sw_runtime.cpp) ---------------------------------------------------------------------------
+// chain2aln_check: what bpsw_chain2aln_batch asks of its scoring and its reads.  chain2aln_back: everything after the tables are
+// known -- B filled but for the parts of `in`, which has been packed and is sent here (its parts i_rlen, i_roff, i_pool are the read
+// block); nseeds / max_seeds: the seeds of all chains and the largest count of one chain; h_reg_base: reg_base on the host, or null when
+// it exists on the device only (B.reg_base, fetched here behind the regions).  Launch, fetch, compaction, sort / dedup; the
+// capacity contract of bpsw_chain2aln_batch.  Caller holds c->mu, has set the device and keeps its hold on the reference.
+int chain2aln_check(const bpsw_opt_t* opt, int zdrop_mode, int n, const int32_t* read_len, const int64_t* read_off, size_t read_pool_bytes);
+int chain2aln_back(bpsw_ctx* c, const bpsw_opt_t* opt, int zdrop_mode, int flags, ChainBatchDev B, StageIn& in, int i_rlen, int i_roff,
+                   int i_pool, long long nseeds, int max_seeds, const long long* h_reg_base, int32_t* out_cnt, bpsw_alnreg_t* out_regs,
+                   int64_t out_cap, int64_t* out_total);
 
 // ---- exclusive prefix sums on the device (bpsw_scan.hip) -----------------------------------------------------------------------
 // `cols` columns of n 64-bit values each, scanned in place by three launches on s: column k is data[k (n + 1) ..], and its total is left
@@ -530,6 +557,7 @@ struct bpsw_ctx {
   bpsw_stats_t stats;
   float last_ext_ms = 0.f, last_sw_ms = 0.f;
   bool have_ext_ev = false, have_sw_ev = false;
+  bpsw::DeviceBuffer d_chain_tab;  // the resident chains (bpsw_chain_dev.hip, ChainTablesDev): pools, per-read columns, the tables the round loop indexes
 };
 
 namespace bpsw {

@@ -1075,8 +1075,8 @@ JNIEXPORT jint JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_loadFmiJNI(
 //                              readLen: Array[Int], reads: Array[Byte]): Array[Long]
 // optInts and mat as for chainToAlnJNI; seedInts = (minSeedLen, maxOcc, splitWidth, maxChainGap, noExact), seedFloats =
 // (splitFactor, chainDropRatio, maskLevel, maskLevelRedun); flags = BPSW_C2A_SORT_DEDUP | BPSW_C2A_DEDUP_SCALA | BPSW_W1_CHAIN_DEVICE
-// | BPSW_W1_SEED_PLAN_DEVICE (the last two: chaining and chain filter on the device, bpsw_chain_dev.hip; the plan of the suffix-array pass on the
-// device, bpsw_seed.hip); reads back to back (codes 0..4).  Result: n longs (regions per read), then 8 longs per region as chainToAlnJNI returns them.  Needs loadPacJNI and
+// | BPSW_W1_SEED_PLAN_DEVICE | BPSW_W1_CHAINS_RESIDENT (the last three: chaining and chain filter on the device, bpsw_chain_dev.hip; the plan of the
+// suffix-array pass on the device, bpsw_seed.hip; the chains left on the device for the round loop, which implies the first); reads back to back (codes 0..4).  Result: n longs (regions per read), then 8 longs per region as chainToAlnJNI returns them.  Needs loadPacJNI and
 // loadFmiJNI first; BPSW_ZDROP as for chainToAlnJNI.
 JNIEXPORT jlongArray JNICALL Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_worker1FlatJNI(
     JNIEnv* env, jobject, jintArray optInts, jbyteArray matArr, jintArray seedInts, jdoubleArray seedFloats, jint flags, jintArray readLenArr,

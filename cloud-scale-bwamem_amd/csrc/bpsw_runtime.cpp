@@ -479,6 +479,7 @@ void bpsw_destroy(bpsw_ctx_t* c) {
   c->d_sw_in.release(); c->d_sw_out.release(); c->d_sw_scratch.release(); c->d_gl_z.release(); c->d_ext_lists.release(); c->d_sift.release();
   for (bpsw::DeviceBuffer& b : c->d_seed) b.release();
   c->d_chain.release();
+  c->d_chain_tab.release();
   c->h_stage_in.release(); c->h_stage_out.release(); c->h_pre.release();
   rescue_scratch_free(c->rescue_scratch);
   for (int i = 0; i < 8; ++i)

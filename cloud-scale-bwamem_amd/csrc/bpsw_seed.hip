@@ -728,8 +728,9 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
   if (bpsw_fmi_length(c) != 2 * l_pac) return fail(BPSW_ERR_ARG, "worker1: no index is loaded, or its seq_len is not 2 * l_pac (bpsw_fmi_load)");
   for (int r = 0; r < n; ++r)
     if (reads->read_len[r] < 1) return fail(BPSW_ERR_ARG, "worker1: empty read");
-  const bool chain_on_device = (flags & BPSW_W1_CHAIN_DEVICE) != 0, plan_on_device = (flags & BPSW_W1_SEED_PLAN_DEVICE) != 0;
-  flags &= ~(BPSW_W1_CHAIN_DEVICE | BPSW_W1_SEED_PLAN_DEVICE);
+  const bool chains_resident = (flags & BPSW_W1_CHAINS_RESIDENT) != 0;
+  const bool chain_on_device = chains_resident || (flags & BPSW_W1_CHAIN_DEVICE) != 0, plan_on_device = (flags & BPSW_W1_SEED_PLAN_DEVICE) != 0;
+  flags &= ~(BPSW_W1_CHAIN_DEVICE | BPSW_W1_SEED_PLAN_DEVICE | BPSW_W1_CHAINS_RESIDENT);
   const double t0 = wall_ms();
   std::vector<int32_t> ic, sc;
   std::vector<bpsw_smem_t> iv;
@@ -749,6 +750,34 @@ int bpsw_worker1_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt
     ChainDevJob J;
     J.n_reads = n; J.seed_beg = read_occ.data(); J.d_seeds = (const bpsw_seed_t*)c->d_seed[4].ptr; J.h_seeds = nullptr;
     J.filter = 1; J.drop_bridging = 1;
+    if (chains_resident) {
+      // the chains stay where chain_tables_kernel left them (d_chain_tab); only the read block is staged for the round loop, whose
+      // back half runs under this call's hold on the context.  The seeds are the library's own: not validated again.
+      ChainTablesDev T;
+      rc = chain_dev_run(c, *sopt, opt->w, l_pac, J, nullptr, &T);
+      if (rc != BPSW_OK) return rc;
+      const double t2 = wall_ms();
+      rc = chain2aln_check(opt, zdrop_mode, n, reads->read_len, reads->read_off, reads->read_pool_bytes);
+      if (rc != BPSW_OK) return rc;
+      const uint8_t* d_pac = nullptr;
+      long long ref_len = 0;
+      const RefHold ref_hold = ref_snapshot(c, &d_pac, &ref_len);
+      if (ref_len != l_pac) return fail(BPSW_ERR_ARG, "worker1: the reference was replaced during the call");
+      StageIn in;
+      const int i_rlen = in.add(reads->read_len, 4 * (size_t)n), i_roff = in.add(reads->read_off, 8 * (size_t)n);
+      const int i_pool = in.add(reads->read_pool, reads->read_pool_bytes);
+      HIP_TRY(in.pack(c->h_stage_in, c->d_sw_in));
+      ChainBatchDev B;
+      B.n_reads = n;
+      B.chain_cnt = T.chain_cnt; B.chain_base = T.chain_base; B.reg_base = T.reg_base;
+      B.seed_cnt = T.seed_cnt; B.seed_base = T.seed_base;
+      B.seed_rbeg = T.seed_rbeg; B.seed_qbeg = T.seed_qbeg; B.seed_len = T.seed_len;
+      B.pac = d_pac; B.l_pac = ref_len;
+      rc = chain2aln_back(c, opt, zdrop_mode, flags, B, in, i_rlen, i_roff, i_pool, T.nseeds, T.max_seeds, nullptr, out_cnt, out_regs, out_cap,
+                          out_total);
+      t_w1_ms[0] = t1 - t0; t_w1_ms[1] = t2 - t1; t_w1_ms[2] = wall_ms() - t2;
+      return rc;
+    }
     ChainDevResult R;
     rc = chain_dev_run(c, *sopt, opt->w, l_pac, J, &R);
     if (rc != BPSW_OK) return rc;

@@ -417,9 +417,8 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   *out_total = 0;
   if (n == 0) return BPSW_OK;
   if (n < 0 || !b->read_len || !b->read_off || !b->read_pool || !b->chain_cnt) return fail(BPSW_ERR_ARG, "chain2aln: null read arrays");
-  if (opt->a < 1 || opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 1 || opt->e_ins < 1)
-    return fail(BPSW_ERR_ARG, "chain2aln: scoring must have a >= 1, gap opens >= 0 and gap extensions >= 1");
-  if (opt->w < 1 || opt->w > 254) return fail(BPSW_ERR_LIMIT, "chain2aln: band width must be 1..254");
+  const int orc = chain2aln_check(opt, zdrop_mode, 0, nullptr, nullptr, 0);
+  if (orc != BPSW_OK) return orc;
   ContextEntry entry(c);
   if (entry.rc != BPSW_OK) return entry.rc;
   const uint8_t* d_pac = nullptr;
@@ -477,20 +476,50 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   const int i_scnt = in.add(b->seed_cnt, 4 * (size_t)nchains), i_sbase = in.add(seed_base.data(), 8 * (size_t)nchains);
   const int i_srb = in.add(b->seed_rbeg, 8 * (size_t)nseeds), i_sqb = in.add(b->seed_qbeg, 4 * (size_t)nseeds);
   const int i_sln = in.add(b->seed_len, 4 * (size_t)nseeds), i_pool = in.add(b->read_pool, b->read_pool_bytes);
-  StageOut out;
-  const int r_cnt = out.add(4 * (size_t)n), r_regs = out.add(sizeof(bpsw_alnreg_t) * (size_t)(nseeds > 0 ? nseeds : 1));
-  const int srt_per_wave = (max_seeds + 15) & ~15;
-  HIP_TRY(out.reserve(c->h_stage_out, c->d_sw_out));
-  HIP_TRY(c->d_sw_scratch.reserve(4 * (size_t)srt_per_wave * (size_t)chain2aln_resident_waves(c->num_cu)));
   HIP_TRY(in.pack(c->h_stage_in, c->d_sw_in));
   ChainBatchDev B;
   B.n_reads = n;
-  B.read_len = in.dev<int32_t>(i_rlen); B.read_off = in.dev<long long>(i_roff); B.read_pool = in.dev<uint8_t>(i_pool);
   B.chain_cnt = in.dev<int32_t>(i_ccnt); B.chain_base = in.dev<int32_t>(i_cbase);
   B.seed_cnt = in.dev<int32_t>(i_scnt); B.seed_base = in.dev<long long>(i_sbase);
   B.seed_rbeg = in.dev<long long>(i_srb); B.seed_qbeg = in.dev<int32_t>(i_sqb); B.seed_len = in.dev<int32_t>(i_sln);
   B.reg_base = in.dev<long long>(i_rbase);
   B.pac = d_pac; B.l_pac = l_pac;
+  return chain2aln_back(c, opt, zdrop_mode, flags, B, in, i_rlen, i_roff, i_pool, nseeds, max_seeds, reg_base.data(), out_cnt, out_regs, out_cap,
+                        out_total);
+}
+
+}  // extern "C"
+
+namespace bpsw {
+
+int chain2aln_check(const bpsw_opt_t* opt, int zdrop_mode, int n, const int32_t* read_len, const int64_t* read_off, size_t read_pool_bytes) {
+  if (zdrop_mode != BPSW_ZDROP_SCALA && zdrop_mode != BPSW_ZDROP_BWA) return fail(BPSW_ERR_ARG, "chain2aln: bad zdrop_mode");
+  if (opt->a < 1 || opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 1 || opt->e_ins < 1)
+    return fail(BPSW_ERR_ARG, "chain2aln: scoring must have a >= 1, gap opens >= 0 and gap extensions >= 1");
+  if (opt->w < 1 || opt->w > 254) return fail(BPSW_ERR_LIMIT, "chain2aln: band width must be 1..254");
+  for (int r = 0; r < n; ++r) {
+    const int ql = read_len[r];
+    const long long qo = read_off[r];
+    if (ql < 1 || qo < 0 || (unsigned long long)(qo + ql) > read_pool_bytes) return fail(BPSW_ERR_ARG, "chain2aln: read outside read_pool");
+    if (ql > 256) return fail(BPSW_ERR_LIMIT, "chain2aln: read longer than 256 bases");
+  }
+  return BPSW_OK;
+}
+
+int chain2aln_back(bpsw_ctx* c, const bpsw_opt_t* opt, int zdrop_mode, int flags, ChainBatchDev B, StageIn& in, int i_rlen, int i_roff,
+                   int i_pool, long long nseeds, int max_seeds, const long long* h_reg_base, int32_t* out_cnt, bpsw_alnreg_t* out_regs,
+                   int64_t out_cap, int64_t* out_total) {
+  const int n = B.n_reads;
+  *out_total = nseeds;  // upper bound until the kernel has run: one region per seed at most
+  if (nseeds > out_cap || (nseeds > 0 && !out_regs)) return fail(BPSW_ERR_CAPACITY, "chain2aln: out_regs must hold one region per seed");
+  if (max_seeds < 1) max_seeds = 1;
+  StageOut out;
+  const int r_cnt = out.add(4 * (size_t)n), r_regs = out.add(sizeof(bpsw_alnreg_t) * (size_t)(nseeds > 0 ? nseeds : 1));
+  const int r_rbase = out.add(h_reg_base ? 0 : 8 * (size_t)n);  // reg_base behind the regions, when the host does not have it
+  const int srt_per_wave = (max_seeds + 15) & ~15;
+  HIP_TRY(out.reserve(c->h_stage_out, c->d_sw_out));
+  HIP_TRY(c->d_sw_scratch.reserve(4 * (size_t)srt_per_wave * (size_t)chain2aln_resident_waves(c->num_cu)));
+  B.read_len = in.dev<int32_t>(i_rlen); B.read_off = in.dev<long long>(i_roff); B.read_pool = in.dev<uint8_t>(i_pool);
   ChainParams P;
   P.mat = pack_mat(opt->mat);
   P.mat_max = opt->mat[0];
@@ -506,6 +535,10 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
                                   srt_per_wave, c->num_cu, (int*)((char*)c->d_pre.ptr + 384), c->stream));  // its own queue head: +128 belongs to ext_kernel, which expects it zero
   HIP_TRY(hipEventRecord(c->ev[2], c->stream));
   HIP_TRY(out.fetch(c->stream));
+  if (!h_reg_base) {
+    HIP_TRY(hipMemcpyAsync(out.h + out.at[r_rbase], B.reg_base, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    h_reg_base = out.host<long long>(r_rbase);
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   float ms = 0;
   (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
@@ -519,7 +552,7 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   int64_t at = 0;
   std::vector<bpsw_alnreg_t> v;
   for (int r = 0; r < n; ++r) {
-    const bpsw_alnreg_t* first = regs + reg_base[(size_t)r];
+    const bpsw_alnreg_t* first = regs + h_reg_base[r];
     int m = cnt[r];
     if (flags & BPSW_C2A_SORT_DEDUP) {
       v.assign(first, first + m);
@@ -532,6 +565,10 @@ int bpsw_chain2aln_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_chains
   *out_total = at;
   return BPSW_OK;
 }
+
+}  // namespace bpsw
+
+extern "C" {
 
 int bpsw_global_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_global_jobs_t* j, int32_t* out_score,
                       int32_t* out_ncigar, uint32_t* out_cigar) {

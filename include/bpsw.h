@@ -311,6 +311,7 @@ int bpsw_ref_fetch(bpsw_ctx_t *ctx, int32_t n, const int64_t *beg, const int64_t
 #define BPSW_C2A_DEDUP_SCALA 2
 #define BPSW_W1_CHAIN_DEVICE 4 /* bpsw_worker1_batch only: chain and filter the seeds on the device (bpsw_chain_batch's kernels) */
 #define BPSW_W1_SEED_PLAN_DEVICE 8 /* bpsw_worker1_batch only: plan the suffix-array pass on the device (as BPSW_SEED_PLAN_DEVICE) */
+#define BPSW_W1_CHAINS_RESIDENT 16 /* bpsw_worker1_batch only: BPSW_W1_CHAIN_DEVICE, and the chains stay on the device for the round loop */
 typedef struct {
   int32_t n_reads;
   const int32_t *read_len;
@@ -422,13 +423,33 @@ int bpsw_chain_batch(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, int32_t w, in
 void bpsw_chain_set_arena_budget(int64_t bytes);
 void bpsw_chain_last_split(int64_t st[4]);
 
+/* bpsw_chain_batch with flags.  0: bpsw_chain_batch itself.  BPSW_CHAIN_TABLES_DEVICE: the stage leaves the chains on the device in
+ * read order, as the tables the round loop's kernel indexes (what bpsw_worker1_batch does with BPSW_W1_CHAINS_RESIDENT), and the entry
+ * then fetches them for the caller only: chain_cnt, chain_seed_cnt and the seeds, zipped back into bpsw_seed_t.  Results, totals and
+ * the capacity behaviour are exactly bpsw_chain_batch's.  Any other flag is BPSW_ERR_ARG. */
+#define BPSW_CHAIN_TABLES_DEVICE 1
+int bpsw_chain_batch_ex(bpsw_ctx_t *ctx, const bpsw_seed_opt_t *sopt, int32_t w, int64_t l_pac, int32_t n_reads, const int32_t *seed_cnt,
+                        const bpsw_seed_t *seeds, int32_t filter, int32_t *chain_cnt, int32_t *chain_seed_cnt, int64_t chain_cap,
+                        bpsw_seed_t *out_seeds, int64_t seed_cap, int64_t *chain_total, int64_t *seed_total, int flags);
+/* Diagnostics.  b[0], b[1]: the bytes staged to the device and fetched from it by the calling thread's most recent chain stage
+ * (bpsw_chain_batch, bpsw_chain_batch_ex, or bpsw_worker1_batch with BPSW_W1_CHAIN_DEVICE or BPSW_W1_CHAINS_RESIDENT), in the manner of
+ * bpsw_last_seed_bytes; the copy bpsw_chain_batch_ex makes for its caller is not counted.  With the chains resident the stage
+ * fetches 32 bytes a slice of the arena (an error word and the slice's totals) and 32 bytes of totals once, whatever the number of
+ * reads, plus the seeds of the reads it chains on the calling thread (BPSW_CHAIN_DEV_MAX_SEEDS) when those are on the device only. */
+void bpsw_last_chain_bytes(int64_t b[2]);
+
 /* worker1 from reads to regions: bpsw_seed_batch, bpsw_chain_seeds with the filter per read, then bpsw_chain2aln_batch as it is
  * (zdrop_mode, flags, out_* exactly as there; *out_total is set to the needed out_cap on BPSW_ERR_CAPACITY).  Needs the reference
  * (bpsw_ref_load) and an index with seq_len == 2 * l_pac on the context's device.  With BPSW_W1_CHAIN_DEVICE in flags the seeds
  * stay on the device and are chained and filtered there (as bpsw_chain_batch does; seeds bridging l_pac dropped by the kernel), and
  * only the chains come back; the regions are the same.  With BPSW_W1_SEED_PLAN_DEVICE the seeding stage plans its suffix-array pass on
  * the device (bpsw_seed_batch_ex) and the intervals do not come back; with both flags the seeding stage fetches per read its interval
- * count and its occurrence offset and nothing else.  Neither flag is passed on to bpsw_chain2aln_batch. */
+ * count and its occurrence offset and nothing else.  With BPSW_W1_CHAINS_RESIDENT (which implies BPSW_W1_CHAIN_DEVICE and composes
+ * with the other flags) the chains do not come back either: the chain stage leaves on the device, in read order, the tables the round
+ * loop's kernel indexes, and the round loop runs on them; with all three flags nothing is fetched between the reads going out and the
+ * regions coming back except counts and totals.  The seeds are then not validated as bpsw_chain2aln_batch validates a caller's (inside
+ * their read, on one strand, inside the reference): the library's own kernels produced them.  out_cnt, the regions and the capacity
+ * contract are bit-identical.  None of the three flags is passed on to the round loop. */
 int bpsw_worker1_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_reads_t *reads, int zdrop_mode,
                        int flags, int32_t *out_cnt, bpsw_alnreg_t *out_regs, int64_t out_cap, int64_t *out_total);
 /* Diagnostics: the number of lanes (reads in flight, a multiple of 64) seed_smem_kernel keeps resident, process-wide; 0 = the default,

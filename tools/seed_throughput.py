@@ -4,7 +4,7 @@ synthetic genome, next to the reference's mem_chain on the same reads from oracl
 library is built.
 
     python tools/seed_throughput.py [--genome-mb 50] [--reads 100000] [--read-len 150] [--sa-intv 32] [--reps 5] [--threads 16]
-                                    [--seed-plan-device] [--out profiles/seed_throughput.json]
+                                    [--seed-plan-device] [--chains-resident] [--out profiles/seed_throughput.json]
 
 The chain stage both ways is slot 1 of bpsw_last_worker1_times without and with BPSW_W1_CHAIN_DEVICE on the same batch.  The
 long-read threshold (BPSW_CHAIN_DEV_MAX_SEEDS) is read once per process, and reads of a random genome have a handful of seeds,
@@ -20,7 +20,11 @@ reported, one JSON line.  The three stage times of a bpsw_worker1_batch call com
 with BPSW_W1_CHAIN_DEVICE, the four settings taken in turn within every repetition after one warm-up round.  Per setting and
 repetition it prints the three stage times, the calling thread's CPU time over the whole call (the stages after seeding are the same
 code both ways, so a difference is the seeding stage's) and the H2D / D2H bytes of the seeding stage from bpsw_last_seed_bytes.  A
-library without the flag (BPSW_LIB pointing at an older build) is measured on the two settings it has."""
+library without the flag (BPSW_LIB pointing at an older build) is measured on the two settings it has.
+
+--chains-resident adds BPSW_W1_CHAINS_RESIDENT to that rotation (with the plan on the host, and on the device under
+--seed-plan-device), and per setting the H2D / D2H bytes of the chain stage from bpsw_last_chain_bytes, the chain stage's, the round
+loop call's and the whole call's median."""
 import argparse
 import ctypes as C
 import json
@@ -173,14 +177,21 @@ def threshold_runs(scnt, sv, l_pac, n_long, sizes, reps):
     return out
 
 
-def seed_plan_runs(ctx, opt, so, rb, reps):
-    """worker1_batch on the four settings of (seeding plan on the host / the device) x (chaining on the host / the device), in turn"""
-    has_plan = hasattr(ctx.lib, "bpsw_seed_batch_ex")
+def seed_plan_runs(ctx, opt, so, rb, reps, plan=True, resident=False):
+    """worker1_batch on the settings of (seeding plan on the host / the device) x (chaining on the host / the device / the device with
+    the chains resident), in turn; those the library has"""
+    has_plan = plan and hasattr(ctx.lib, "bpsw_seed_batch_ex")
+    has_resident = resident and hasattr(ctx.lib, "bpsw_chain_batch_ex")
+    has_chain_bytes = hasattr(ctx.lib, "bpsw_last_chain_bytes")
     settings = {"plan_host__chain_host": 0, "plan_host__chain_device": bpsw_hip.W1_CHAIN_DEVICE}
+    if has_resident:
+        settings["plan_host__chains_resident"] = bpsw_hip.W1_CHAINS_RESIDENT
     if has_plan:
         settings["plan_device__chain_host"] = bpsw_hip.W1_SEED_PLAN_DEVICE
         settings["plan_device__chain_device"] = bpsw_hip.W1_SEED_PLAN_DEVICE | bpsw_hip.W1_CHAIN_DEVICE
-    runs = {k: {"stage_ms": [], "call_ms": [], "thread_cpu_ms": [], "seed_bytes_h2d_d2h": None} for k in settings}
+        if has_resident:
+            settings["plan_device__chains_resident"] = bpsw_hip.W1_SEED_PLAN_DEVICE | bpsw_hip.W1_CHAINS_RESIDENT
+    runs = {k: {"stage_ms": [], "call_ms": [], "thread_cpu_ms": [], "seed_bytes_h2d_d2h": None, "chain_bytes_h2d_d2h": None} for k in settings}
     want = None
     for k in range(reps + 1):
         for name, fl in settings.items():
@@ -195,10 +206,15 @@ def seed_plan_runs(ctx, opt, so, rb, reps):
                 r["stage_ms"].append([round(x, 2) for x in bpsw_hip.last_worker1_times()])
                 r["call_ms"].append(round(1e3 * (t1 - t0), 2))
                 r["thread_cpu_ms"].append(round(1e3 * (c1 - c0), 2))
-                if has_plan:
+                if hasattr(ctx.lib, "bpsw_last_seed_bytes"):
                     r["seed_bytes_h2d_d2h"] = list(ctx.last_seed_bytes())
+                if has_chain_bytes and fl & ~bpsw_hip.W1_SEED_PLAN_DEVICE:
+                    r["chain_bytes_h2d_d2h"] = list(bpsw_hip.last_chain_bytes())
     for r in runs.values():
         r["seeding_call_ms_median"] = round(float(np.median([s[0] for s in r["stage_ms"]])), 2)
+        r["chain_stage_ms_median"] = round(float(np.median([s[1] for s in r["stage_ms"]])), 2)
+        r["round_loop_call_ms_median"] = round(float(np.median([s[2] for s in r["stage_ms"]])), 2)
+        r["call_ms_median"] = round(float(np.median(r["call_ms"])), 2)
         r["thread_cpu_ms_median"] = round(float(np.median(r["thread_cpu_ms"])), 2)
     return runs
 
@@ -214,6 +230,8 @@ def main():
     ap.add_argument("--long-reads", type=int, default=64)
     ap.add_argument("--long-seeds", default="64,128,512,3000", help="'' leaves the long-read runs out")
     ap.add_argument("--seed-plan-device", action="store_true", help="also measure the seeding stage with its plan on the host and on the device")
+    ap.add_argument("--chains-resident", action="store_true",
+                    help="add BPSW_W1_CHAINS_RESIDENT to the rotation (alone, and with the plan on the device under --seed-plan-device)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seed_throughput.json"))
     ap.add_argument("--chain-child", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -269,11 +287,11 @@ def main():
         "reads_on_device": split[0], "reads_on_host": split[1], "slices": split[2], "arena_bytes": split[3],
         "max_seeds_in_a_read": int(scnt.max()),
     }
-    if a.seed_plan_device:
-        res["seed_plan"] = seed_plan_runs(ctx, opt, so, rb, a.reps)
+    if a.seed_plan_device or a.chains_resident:
+        res["seed_plan"] = seed_plan_runs(ctx, opt, so, rb, a.reps, plan=a.seed_plan_device, resident=a.chains_resident)
         for name, r in res["seed_plan"].items():
-            print(f"{name}: stages (seeding, chaining, round loop) ms {r['stage_ms']}; thread CPU ms {r['thread_cpu_ms']}; "
-                  f"seeding stage H2D / D2H bytes {r['seed_bytes_h2d_d2h']}", file=sys.stderr)
+            print(f"{name}: stages (seeding, chaining, round loop) ms {r['stage_ms']}; call ms {r['call_ms']}; thread CPU ms {r['thread_cpu_ms']}; "
+                  f"seeding stage H2D / D2H bytes {r['seed_bytes_h2d_d2h']}; chain stage H2D / D2H bytes {r['chain_bytes_h2d_d2h']}", file=sys.stderr)
     if a.long_seeds:
         res["chain_batch_with_long_reads"] = dict(threshold_runs(scnt, sv, l_pac, a.long_reads, [int(x) for x in a.long_seeds.split(",")], a.reps),
                                                   long_reads=a.long_reads)
