@@ -418,7 +418,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, BPSW_EXT_WAVES_PER_SIMD) void
   RingWorker W;
   for (;;) {
     uint32_t unit = 0, word = 0;
-    if (!ring_next_unit(A, lane, W, unit, word)) break;
+    uint32_t taken = 1;  // (always one unit per ticket here)
+    if (!ring_next_unit(A, lane, W, unit, word, taken, false)) break;
     const auto f32 = [&](const int k) { return (uint32_t)__builtin_amdgcn_readlane((int)word, k); };
     const auto f64 = [&](const int k) { return ((unsigned long long)f32(k + 1) << 32) | (unsigned long long)f32(k); };
     // the payload (ExtRingPayload, words 8..) as the arguments a launch would have got
@@ -456,7 +457,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, BPSW_EXT_WAVES_PER_SIMD) void
         ext_do_task<false, 1, true>(task, 0, lane, wire, out, sc, mat_lds[wave], oDel, eDel, oIns, eIns, penClip5, penClip3, wBand, exact_a, amax, nullptr, nullptr, ts, pl,
                                     nullptr, 255, nullptr, 0);
     }
-    ring_unit_done(A, lane, W, word);
+    ring_unit_done(A, lane, W, word, taken);
   }
 }
 

@@ -140,6 +140,12 @@ void launch_ref_fetch(const uint8_t* d_pac, long long l_pac, int n, const long l
 size_t sw_scratch_bytes_per_wave(int max_tlen);
 bool sw_quad_enabled();  // four rescue jobs per wavefront for mates <= 160 bases (BPSW_SW_QUAD=0 disables)
 int sw_resident_waves(int num_cu);
+// The half-wave packed form (bpsw_swalign.hip: four jobs per wavefront, a packed pair in each 32-lane half) takes batches whose longest
+// mate has at most 150 bases, as a launch and behind the ring.  BPSW_SW_HALVES=0, read once per process: never (the A/B switch).
+inline bool sw_halves_for(int max_qlen) {
+  static const bool off = getenv("BPSW_SW_HALVES") && atoi(getenv("BPSW_SW_HALVES")) == 0;
+  return !off && max_qlen >= 1 && max_qlen <= 150;
+}
 // d_pre_check: as for launch_ext_kernel (the launch is sized for max_qlen / max_tlen speculatively).
 hipError_t launch_sw_kernel(const SwJobsDev& jobs, const SwScoring& sc, int max_qlen, int max_tlen, int32_t* d_out,
                             uint32_t* d_scratch, int num_cu, hipStream_t s, const SwPrepass* d_pre_check = nullptr, KernelEvents kev = KernelEvents());

@@ -47,9 +47,9 @@ struct RingService {
 };
 
 // one service per device and ring class
-constexpr int kRingClasses = 3;  // 3: SW jobs with mates up to 171 bases, 5: up to 256, RING_CLASS_EXT: small extension batches
+constexpr int kRingClasses = 4;  // 3: SW jobs with mates up to 171 bases, 5: up to 256, RING_CLASS_EXT: small extension batches, RING_CLASS_SW_HALVES: two units per ticket
 RingService g_rings[64][kRingClasses];
-RingService& service(int device, int c_class) { return g_rings[device >= 0 && device < 64 ? device : 0][c_class == 3 ? 0 : c_class == RING_CLASS_EXT ? 2 : 1]; }
+RingService& service(int device, int c_class) { return g_rings[device >= 0 && device < 64 ? device : 0][c_class == 3 ? 0 : c_class == RING_CLASS_SW_HALVES ? 3 : c_class == RING_CLASS_EXT ? 2 : 1]; }
 
 int hip_fail_ring(hipError_t e, const char* what) { return fail(BPSW_ERR_DEVICE, std::string("ring: ") + what + ": " + hipGetErrorString(e)); }
 #define RING_TRY(expr)                                      \
@@ -130,7 +130,7 @@ int start_epoch(RingService& S) {
     // 16 384 batches or 2 ms after the last one).  BPSW_RING_WG_PER_CU fixes it.
     const bool alone = ext_call_age_ms(S.device) > 20.0;
     // (the extension ring serves small batches only: one workgroup per CU, idle unless such calls are being made)
-    const double dflt = S.c_class == RING_CLASS_EXT ? 1.0 : S.c_class == 3 ? 1.0 : (alone ? 2.0 : 0.5);
+    const double dflt = S.c_class == RING_CLASS_EXT ? 1.0 : (S.c_class == 3 || S.c_class == RING_CLASS_SW_HALVES) ? 1.0 : (alone ? 2.0 : 0.5);
     const double per_cu = getenv("BPSW_RING_WG_PER_CU") ? atof(getenv("BPSW_RING_WG_PER_CU")) : dflt;
     const int blocks = (int)(S.num_cu * (per_cu > 0.0 ? per_cu : 1.0));
     S.blocks = blocks < 2 ? 2 : blocks;

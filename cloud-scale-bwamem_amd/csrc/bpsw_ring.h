@@ -113,6 +113,16 @@ struct SwRingPayload {
   uint64_t mat_row[5];
   int32_t a, b, o_del, e_del, o_ins, e_ins, xtra, pad;
 };
+// The rescue kernel's ring classes: 3 and 5 (columns per lane: mates up to 171 / 256 bases, a job pair per ticket), and the HALF-WAVE class
+// for batches whose longest mate has at most 150 bases: its workers take TWO consecutive units with one ticket and run them as a quartet
+// (bpsw_swalign.hip, swh_do_quartet).  Two units per ticket buy throughput -- a quartet costs a worker about 1.5 times a pair -- and cost
+// latency while workers stand idle: a call of 64 pairs (four units) took 0.24 ms instead of 0.19 with its units paired
+// (tests/small_call_table.py).  So the host sends a batch to the half-wave class from SW_RING_PAIR_MIN_UNITS units on -- 15 jobs, the
+// largest batch a lone caller sends through the ring at all (sw_stage_run's lone-launch rule), and every batch that reaches the ring
+// because others are in flight -- and smaller ones to class 3, whose kernel and single-unit path are what they were: a kernel that
+// carried both forms made every small call 2-4 us slower.
+constexpr int RING_CLASS_SW_HALVES = 4;
+constexpr uint32_t SW_RING_PAIR_MIN_UNITS = 8;
 static_assert(sizeof(RingDescHead) + sizeof(SwRingPayload) <= sizeof(RingDesc), "rescue payload fits a descriptor");
 
 // payload of the EXTENSION kernel's descriptors (words 8..): a wire batch (either format) in device-visible memory whose flanks all have at

@@ -111,7 +111,12 @@ struct RingWorker {
 // relaxed loads (sc1: served at the device's point of coherence, nothing invalidated) with a back-off to ~7 us; ONE invalidate of the
 // CU's vector cache per unit taken (the staging blocks the unit reads are pinned host memory that callers reuse); and a unit's
 // results are written through with system-scope stores, so that "visible to the host" is `s_waitcnt vmcnt(0)`, not a write-back.
-__device__ inline bool ring_next_unit(const RingArgs& A, const int lane, RingWorker& W, uint32_t& unit, uint32_t& word) {
+//
+// `may_pair` (the rescue kernel's half-wave class): a wave that sees at least two units left takes TWO consecutive units, `unit` and
+// `unit + 1`, with one add of 2.  `taken` is what it got: 2, or 1 -- one unit was left, or another wave's add came in between and the
+// ticket was the descriptor's last.  Without it the function is what it was.
+__device__ inline bool ring_next_unit(const RingArgs& A, const int lane, RingWorker& W, uint32_t& unit, uint32_t& word, uint32_t& taken,
+                                      const bool may_pair) {
   int naps = 0;
   for (;;) {
     // tail, cur, quit with one load (lanes 0-2 a word each; a waiting wave costs the device one request per look)
@@ -152,13 +157,17 @@ __device__ inline bool ring_next_unit(const RingArgs& A, const int lane, RingWor
     if (lane < 2) cw = __hip_atomic_load(&A.ctr[W.d].next + lane, __ATOMIC_RELAXED, RING_DEV);
     const uint32_t handed = (uint32_t)__builtin_amdgcn_readlane((int)cw, 0), n_units = (uint32_t)__builtin_amdgcn_readlane((int)cw, 1);
     if (handed >= n_units) { W.d += 1u; continue; }
+    uint32_t take = 1u;
+    if (may_pair && n_units - handed >= 2u) take = 2u;
     uint32_t k = 0;
-    if (lane == 0) k = __hip_atomic_fetch_add(&A.ctr[W.d].next, 1u, __ATOMIC_RELAXED, RING_DEV);
+    if (lane == 0) k = __hip_atomic_fetch_add(&A.ctr[W.d].next, take, __ATOMIC_RELAXED, RING_DEV);
     k = ring_uni(k);
     if (k >= n_units) { W.d += 1u; continue; }
-    if (k + 1u == n_units && lane == 0) __hip_atomic_fetch_max(&A.D->cur, W.d + 1u, __ATOMIC_RELAXED, RING_DEV);  // one per descriptor
+    if (k + take > n_units) take = n_units - k;  // asked for two, the last one was left
+    if (k + take == n_units && lane == 0) __hip_atomic_fetch_max(&A.D->cur, W.d + 1u, __ATOMIC_RELAXED, RING_DEV);  // one per descriptor
     word = __hip_atomic_load(&A.d_desc[W.d].w[lane], __ATOMIC_RELAXED, RING_DEV);
     unit = k;
+    taken = take;
     if (lane == 0) {
       if (k == 0u) __hip_atomic_store((unsigned long long*)&A.ctr[W.d].t0, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, RING_DEV);
       if (!W.counted) __hip_atomic_fetch_add(&A.D->workers, 1u, __ATOMIC_RELAXED, RING_DEV);
@@ -168,7 +177,7 @@ __device__ inline bool ring_next_unit(const RingArgs& A, const int lane, RingWor
     W.diag_t_claim = wall_clock64();
     if (lane == 0) {
       const unsigned long long t_pub = __hip_atomic_load((unsigned long long*)&A.ctr[W.d].t_pub, __ATOMIC_RELAXED, RING_DEV);
-      __hip_atomic_fetch_add(&A.D->diag_claim_ticks, W.diag_t_claim - t_pub, __ATOMIC_RELAXED, RING_DEV);
+      __hip_atomic_fetch_add(&A.D->diag_claim_ticks, (W.diag_t_claim - t_pub) * take, __ATOMIC_RELAXED, RING_DEV);  // (per unit taken)
     }
 #endif
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // nothing this CU's vector cache holds of an earlier batch's staging block
@@ -180,7 +189,9 @@ __device__ inline bool ring_next_unit(const RingArgs& A, const int lane, RingWor
 // descriptor -- write the caller's completion record.  `word` as ring_next_unit returned it.  Every store of this lane has been
 // acknowledged (s_waitcnt vmcnt(0)) before the count moves, the counts are one atomic sequence, so the lane that sees the last count
 // writes the record after every unit's results.
-__device__ inline void ring_unit_done(const RingArgs& A, const int lane, const RingWorker& W, const uint32_t word) {
+// `taken`: the units this wave took with one ticket (ring_next_unit) and has finished: one add of that many.  The adds of a descriptor
+// still form one atomic sequence whose values end at n_units, so exactly one wave sees its add reach n_units.
+__device__ inline void ring_unit_done(const RingArgs& A, const int lane, const RingWorker& W, const uint32_t word, const uint32_t taken) {
   const uint32_t n_units = (uint32_t)__builtin_amdgcn_readlane((int)word, 0);
   const uint32_t done_value = (uint32_t)__builtin_amdgcn_readlane((int)word, 1);
   const unsigned long long done_ptr = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)word, 3) << 32) |
@@ -189,10 +200,10 @@ __device__ inline void ring_unit_done(const RingArgs& A, const int lane, const R
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef BPSW_RING_DIAG
     __hip_atomic_fetch_add(&A.D->diag_unit_ticks, (unsigned long long)wall_clock64() - W.diag_t_claim, __ATOMIC_RELAXED, RING_DEV);
-    __hip_atomic_fetch_add(&A.D->diag_units, 1ull, __ATOMIC_RELAXED, RING_DEV);
+    __hip_atomic_fetch_add(&A.D->diag_units, (unsigned long long)taken, __ATOMIC_RELAXED, RING_DEV);
 #endif
-    const uint32_t before = __hip_atomic_fetch_add(&A.ctr[W.d].done, 1u, __ATOMIC_RELAXED, RING_DEV);
-    if (before + 1u == n_units) {
+    const uint32_t before = __hip_atomic_fetch_add(&A.ctr[W.d].done, taken, __ATOMIC_RELAXED, RING_DEV);
+    if (before + taken == n_units) {
       RingDone* r = (RingDone*)done_ptr;
       const unsigned long long t0 = __hip_atomic_load((unsigned long long*)&A.ctr[W.d].t0, __ATOMIC_RELAXED, RING_DEV);
       __hip_atomic_store((unsigned long long*)&r->t_first, t0, __ATOMIC_RELAXED, RING_SYS);

@@ -88,6 +88,8 @@ int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st
   // packed kernel does not cover, mates above 256 bases, windows longer than its key rows) and BPSW_RING=0 go through a launch.
   int ring_bias = 0;
   int ring_class = (ring_enabled() && zc_in && zc_out) ? sw_ring_class(sc, mq, mt, &ring_bias) : 0;
+  // (the half-wave class, two units per ticket: mates of <= 150 bases and enough units that throughput, not latency, is what counts -- bpsw_ring.h)
+  if (ring_class == 3 && sw_halves_for(mq) && (uint32_t)((n + 1) / 2) >= SW_RING_PAIR_MIN_UNITS) ring_class = RING_CLASS_SW_HALVES;
   if (ring_class && !ring_usable(c->device, ring_class)) ring_class = 0;  // a ring that failed earlier: a launch per batch, as before round 5
   // A LONE caller with a sizeable batch -- no other SW batch in flight on the device, no extension call on it for 20 ms -- is better off
   // with a launch of its own: the epoch's grid is one or two waves per SIMD, a launch fills the device (256 / 1 024 / 4 096 pairs per
@@ -301,7 +303,8 @@ int bpsw_swalign2_batch_device(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_
     // Asynchronous: the launch is sized for the geometry the previous call on this context was verified to have (the kernel
     // template by mate length, the scratch rows by window length) and checks the scan on the device; the scan is read back
     // at the next call on this context or at bpsw_last_kernel_ms, where a batch that outgrew the guess is launched again.
-    const int cap_q = (c->sw_geom_qlen <= 160 && sw_quad_enabled()) ? 160 : 64 * ((c->sw_geom_qlen + 63) / 64);  // quad-job / sw_kernel<C>
+    const int cap_q = sw_halves_for(c->sw_geom_qlen) ? 150                                          // the half-wave packed form
+                      : (c->sw_geom_qlen <= 160 && sw_quad_enabled()) ? 160 : 64 * ((c->sw_geom_qlen + 63) / 64);  // quad-job / sw_kernel<C>
     const int cap_t = (int)(c->d_sw_scratch.cap / ((size_t)sw_resident_waves(c->num_cu) * 16)) & ~63;  // rows the scratch holds per job
     if (cap_t >= c->sw_geom_tlen) {
       HIP_TRY(hipEventRecord(c->ev[6], s));

@@ -8,11 +8,14 @@
 // How.  The band is static, so the row dependency can be skewed: lane l owns C consecutive query columns and at step t works on
 // target row t - l (a systolic anti-diagonal); everything a cell needs from its left neighbour -- F(i,j), the diagonal H(i-1,j-1), the
 // running row key and the row's target selector -- arrives with one DPP wave_shr:1 from the previous step: no in-row scan, no LDS
-// traffic in the inner loop.  Three forms of it live here:
+// traffic in the inner loop.  Four forms of it live here:
 //   * swp_kernel<C> / swp_resident_kernel<C> (what runs): TWO jobs per wavefront, one in each 16-bit half of every DP register
 //     (v_pk_*_u16; exact because a pass stops at the 255 score cap), the query right-aligned, the row keys booked by the lanes
 //     behind the last column eight rows at a time, the second best rebuilt from the stored row maxima (see "Packed form" below).
 //     The resident kernel is the same job pair taken from the device's submission ring (bpsw_ring.h) instead of one launch's table.
+//   * swh_kernel<KL> (what runs for mates of up to 150 bases, i.e. every 2x150 bp rescue): the packed form with FOUR jobs per
+//     wavefront, a packed pair in each 32-lane half, five columns per lane (see "Half-wave packed form" below); the resident
+//     kernel of the ring's half-wave class runs it on two units at a time.
 //   * sw_kernel<C>: one job per wavefront in int32, the per-row bookkeeping of SWUtil.scala:517-538 on the scalar unit -- for
 //     scorings the packed form cannot take (max(mat) > |b| + 1, scores beyond a byte) and mates above 256 bases.
 //   * sw4_kernel: four jobs per wavefront (one per 16-lane DPP row, ten columns per lane) in int32, for such scorings in large batches.
@@ -538,13 +541,18 @@ struct PkCols {  // per lane: C columns of both jobs
 struct PkConst {
   u16x2 eDel, eIns, oeDel, oeIns, biasv, k256;
   bool tail;
+  bool head = false, last = false;  // half-wave form: lane 32 (first lane of the upper half), and the lane of a half's last query column
   bool same_oe;  // oDel + eDel == oIns + eIns (the default): E and F share `H - oe`
 };
 
 // one anti-diagonal of both jobs (SWUtil.scala:484-505)
-template <int C, bool HASN, bool SAME_OE>
+// HALF (the half-wave form below): the two 32-lane halves are separate pipes -- `ch` is the half's own selector word, lane 32 starts
+// its half's row like lane 0, and the two lanes behind a half's last column hand zeros on (their H / E / F are zero by their
+// per-lane constants, see swh_pass) instead of keys.
+template <int C, bool HASN, bool SAME_OE, bool HALF = false>
 __device__ __forceinline__ void swp_step(PkCols<C>& S, const PkConst& K, const int ch) {
   S.sel = wave_shr1(ch, S.sel);                    // lane 0 starts a row of each job, lane l continues the row lane l-1 had
+  if (HALF) S.sel = K.head ? ch : S.sel;
   const int din = shr1_zero(S.hlast_old);          // H(i-1, l*C-1)
   const int fin = shr1_zero(S.fout);               // F(i, l*C)
   const int kin = shr1_zero(S.keyout);             // row maxima so far
@@ -574,7 +582,7 @@ __device__ __forceinline__ void swp_step(PkCols<C>& S, const PkConst& K, const i
   }
   S.hlast_cur = S.Hp[C - 1];
   S.fout = unpk(f);
-  S.keyout = K.tail ? kin : unpk(key);
+  S.keyout = K.tail ? (HALF ? 0 : kin) : unpk(key);
 }
 
 // The second-best score of SWUtil.scala:549-567 from the row maxima m[0..n_rows) of one pass.  The list logic of :517-529
@@ -873,6 +881,354 @@ __device__ __forceinline__ void swp_do_duo(const SwJobsDev& jobs, const SwScorin
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Half-wave packed form, for mates of up to 150 bases (every 2x150 bp rescue): FOUR jobs per wavefront.  Each 32-lane half is a
+// systolic pipe of its own that carries a job pair in the 16-bit halves of its registers exactly as above: 30 lanes x 5 columns,
+// the mate right-aligned so that its last column is the last column of the half's lane 29.  Why: a 150-base mate fills 50 of the
+// 57 query lanes of swp_kernel<3>, every step pays its four shifts, move and select for three cells, and a pass fills a pipe of
+// ~49 steps; here all 150 column slots of a half work, the per-step instructions are shared by five cells and four jobs, and the
+// pipe is ~29 steps deep.
+//   * The half boundary.  wave_shr:1 hands lane 32 what lane 31 holds.  Lanes 30 and 31 of a half hold no column; their gap,
+//     extension and bias constants are 0xffff per lane, so every clamped subtraction in them gives 0: whatever F and diagonal
+//     lane 30 receives from lane 29 dies within its first column, and both lanes hand on H = F = 0 (and a zero key, by the select
+//     that used to pass the key on).  Lane 32 takes its half's selector word with one select per step.
+//   * Booking.  There is no room for eight tail lanes, so the lane of the last column stores its packed key every step (one word
+//     per step and half: keys[half][step]), and every PK_G steps eight lanes of each half read the group's eight words back and
+//     fold them into the running best / frozen / stop logic of swp_pass, unchanged.  The key of row i of a job sits at step
+//     i + D of its half's row, as before.
+//   * Everything that is wave-uniform per pair in swp_pass (L0, D, nsteps, stop, tLen, on, qCols) is per half here: a scalar per
+//     half and job, selected per lane once in the set-up.  The loop runs until all four jobs have stopped.
+constexpr int HW_C = 5;                        // query columns per lane
+constexpr int HW_LANES = 30;                   // lanes of a half that hold query columns
+constexpr int HW_QMAX = HW_LANES * HW_C;       // 150: the longest mate
+constexpr int HW_LAST = HW_LANES - 1;          // lane (within the half) of the last query column
+constexpr int HW_MATE_LDS = 160;               // bytes per staged mate
+constexpr int HW_TBUF = PK_TBUF + PK_G;        // selector words per half and wave
+static_assert(4 * HW_MATE_LDS == 2 * PK_MATE_LDS, "the resident kernel's two forms share the mate buffer");
+
+struct Quad {  // wave-uniform: the four jobs a wave works on, [half][16-bit slot]
+  int qLenRaw[2][2], qrev[2][2], tLen[2][2];
+  const uint8_t* t_pool;  // the windows' byte pool, or null: windows of the 2-bit reference
+  long long rb[2][2];     // a window's offset in the pool / its first coordinate
+};
+
+// One SWAlign pass for the four jobs of a quartet in lock step (see swp_pass).  `mate`: the four staged mates, 2 * half + slot.
+// `keys`: two rows of `key_stride` words, one per half; KL: they are in LDS and hold every step of the pass (stores to scratch
+// rows in HBM are bounded by key_stride).
+template <bool KL>
+__device__ void swh_pass(const int lane, const Quad& J, const uint8_t (*mate)[HW_MATE_LDS], const int (&on)[2][2], const int (&qCols)[2][2],
+                         const bool pass2, const int (&qEnd)[2][2], const int (&tEnd)[2][2], const uint8_t* __restrict__ pac,
+                         const long long l_pac, const SwScoring& sc, const int bias, const int (&stopScore)[2][2],
+                         uint32_t* __restrict__ tbuf, uint32_t* __restrict__ keys, const int key_stride, int (&D)[2][2], PkRes (&res)[2][2]) {
+  constexpr int C = HW_C;
+  const bool hi = lane >= 32;
+  const int ll = lane & 31;
+  const bool dead = ll > HW_LAST;  // the two lanes behind a half's last column
+  const auto sat16 = [](int v) { return v > 0xffff ? 0xffff : v; };
+  PkConst K;
+  K.eDel = pk(dead ? -1 : sat16(sc.e_del) * 0x10001); K.eIns = pk(dead ? -1 : sat16(sc.e_ins) * 0x10001);
+  K.oeDel = pk(dead ? -1 : sat16(sc.o_del + sc.e_del) * 0x10001); K.oeIns = pk(dead ? -1 : sat16(sc.o_ins + sc.e_ins) * 0x10001);
+  K.biasv = pk(dead ? -1 : bias * 0x10001);
+  int k256 = 256 * 0x10001;
+  asm volatile("" : "+v"(k256));  // opaque: a multiply-add (v_pk_mad_u16), not a shift and an add
+  K.k256 = pk(k256);
+  K.tail = dead;
+  K.head = lane == 32;
+  K.last = ll == HW_LAST;
+  K.same_oe = sc.o_del + sc.e_del == sc.o_ins + sc.e_ins;
+  PkCols<C> S;
+  int L0[2][2], nsteps[2][2], maxsteps = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int pad = HW_QMAX - qCols[h][g];            // unused columns, at the left
+      L0[h][g] = on[h][g] ? pad / C : 0;                // first lane of the half with a query column: where row t enters at step t
+      D[h][g] = HW_LAST - L0[h][g];                     // row i leaves lane HW_LAST at step i + D
+      nsteps[h][g] = on[h][g] ? J.tLen[h][g] + D[h][g] : 0;
+      maxsteps = max(maxsteps, nsteps[h][g]);
+    }
+  maxsteps = (maxsteps + PK_G - 1) / PK_G * PK_G;
+  int tLenOn[2][2];  // (a job that is off has no rows)
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) tLenOn[h][g] = on[h][g] ? J.tLen[h][g] : 0;
+  // this lane's half: what the column set-up needs
+  int myOn[2], myQCols[2], myQEnd[2], myQLen[2], myQrev[2], myD[2];
+  const uint8_t* myQ[2];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    myOn[g] = hi ? on[1][g] : on[0][g];
+    myQCols[g] = hi ? qCols[1][g] : qCols[0][g];
+    myQEnd[g] = hi ? qEnd[1][g] : qEnd[0][g];
+    myQLen[g] = hi ? J.qLenRaw[1][g] : J.qLenRaw[0][g];
+    myQrev[g] = hi ? J.qrev[1][g] : J.qrev[0][g];
+    myD[g] = hi ? D[1][g] : D[0][g];
+    myQ[g] = hi ? mate[2 + g] : mate[g];
+  }
+  // What the loop needs of its half now and then (the rows' geometry when selector words are staged, the stop scores when a group is
+  // booked) it selects from the scalars THEN, behind an opaque copy of the half bit: held per lane across the loop these are twenty
+  // VGPRs the step does not have.
+  const auto half_bit = [&]() { int b = hi ? 1 : 0; asm volatile("" : "+v"(b)); return b != 0; };
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    int nrow[2];
+    S.ckey[c] = 0;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int j = ll * C + c - (HW_QMAX - myQCols[g]);
+      const bool valid = myOn[g] && !dead && j >= 0 && j < myQCols[g];
+      int w = 0;
+      nrow[g] = 0;
+      if (valid) {
+        const int fc = pass2 ? myQEnd[g] - j : j;
+        const int raw = myQrev[g] ? myQLen[g] - 1 - fc : fc;
+        int code = myQ[g][raw];
+        if (myQrev[g]) code = code < 4 ? 3 - code : 4;  // MemSamPe.scala:1178-1181
+        if (code > 4) code = 4;
+        const int sh = 8 * code;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w |= (((int)(int8_t)(sc.mat.row[r] >> sh) + bias) & 0xff) << (8 * r);
+        nrow[g] = ((int)(int8_t)(sc.mat.row[4] >> sh) + bias) & 0xff;
+        S.ckey[c] |= (255 - j) << (16 * g);
+      }
+      S.prof[g][c] = w;   // an unused column scores -bias against everything: it stays 0
+    }
+    S.pn[c] = nrow[0] | (nrow[1] << 16);
+    S.Hp[c] = 0;
+    S.E[c] = 0;
+  }
+  S.hlast_cur = S.hlast_old = S.fout = S.keyout = 0;
+  // the v_perm_b32 selector word of rows k + L0 (k - L0 when `before`) of the jobs of the half `up`
+  const auto selector = [&](const bool up, const int k, const bool before) {
+    int s2[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int l0 = up ? L0[1][g] : L0[0][g], tl = up ? tLenOn[1][g] : tLenOn[0][g], te = up ? tEnd[1][g] : tEnd[0][g];
+      const long long rb = up ? J.rb[1][g] : J.rb[0][g];
+      const TgSrc tg = {J.t_pool ? J.t_pool + rb : nullptr, pac, l_pac, rb};
+      const int r = before ? l0 - k : k + l0;
+      s2[g] = PK_SEL_OFF;
+      if (r >= 0 && r < tl) {
+        const int code = tg.at((pass2 && r <= te) ? te - r : r);
+        s2[g] = code < 4 ? 4 * g + code : PK_SEL_N;
+      }
+    }
+    return s2[0] | (PK_SEL_OFF << 8) | (s2[1] << 16) | (PK_SEL_OFF << 24);
+  };
+  const auto has_n = [](const int w) { return (w & 0xff) == PK_SEL_N || ((w >> 16) & 0xff) == PK_SEL_N; };
+  // (as in swp_pass: the first lane of the half is fed row t + L0 at step t, the L0 rows before it start out in the lanes below L0)
+  S.sel = selector(half_bit(), 1 + ll, true);
+  bool nPrev = __builtin_amdgcn_ballot_w64(has_n(S.sel)) != 0;
+
+  // per booking lane (the first PK_G lanes of a half): the row whose key it reads back at the end of the first group -- the key
+  // stored at step x -- and its running best m<<24 | (0xffff - row)<<8 | (255 - j)
+  const int x = ll;
+  const bool booker = x < PK_G;
+  int row[2] = {x - myD[0], x - myD[1]};
+  unsigned best[2] = {0u, 0u};
+  const unsigned long long half_mask[2] = {0xffffffffull, 0xffffffff00000000ull};
+  bool hasN = false;
+  int stop[2][2] = {{on[0][0] ? 0 : 1, on[0][1] ? 0 : 1}, {on[1][0] ? 0 : 1, on[1][1] ? 0 : 1}};
+  uint32_t* tb_me = tbuf + (hi ? HW_TBUF : 0);
+  uint32_t* keys_me = keys + (hi ? key_stride : 0);
+
+  for (int t = 0; t < maxsteps; t += PK_G) {
+    if ((t & (PK_TBUF - 1)) == 0) {  // each half stages the selector words of its next window of target rows
+      int t0 = t;
+      asm volatile("" : "+s"(t0));
+      __builtin_amdgcn_wave_barrier();
+      bool anyN = false;
+      const bool up = half_bit();
+      for (int k = ll; k < PK_TBUF; k += 32) {
+        const int w = selector(up, t0 + k, false);
+        anyN |= has_n(w);
+        tb_me[k] = (uint32_t)w;
+      }
+      const bool nCur = __builtin_amdgcn_ballot_w64(anyN) != 0;
+      hasN = nCur || nPrev;  // rows of the previous window are still in the pipe for 31 steps
+      nPrev = nCur;
+      __builtin_amdgcn_wave_barrier();
+    }
+    const uint32_t* w8 = tb_me + (t & (PK_TBUF - 1));
+    // the key of the row that leaves a half's pipe goes to the half's key row, one word per step
+#define BPSW_SWH_STEPS(HASN, SAME_OE)                                                             \
+  _Pragma("unroll") for (int u = 0; u < PK_G; ++u) {                                              \
+    swp_step<C, HASN, SAME_OE, true>(S, K, (int)w8[u]);                                           \
+    if (K.last && (KL || t + u < key_stride)) keys_me[t + u] = (uint32_t)S.keyout;                \
+  }
+    if (hasN) {
+      BPSW_SWH_STEPS(true, false)
+    } else if (K.same_oe) {
+      BPSW_SWH_STEPS(false, true)
+    } else {
+      BPSW_SWH_STEPS(false, false)
+    }
+#undef BPSW_SWH_STEPS
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the keys written by the last-column lanes -> the booking lanes
+    // the PK_G rows that have just left each pipe: SWUtil.scala:532-538 per booking lane
+    unsigned kv = 0u;
+    if (booker && (KL || t + x < key_stride)) kv = keys_me[t + x];
+    int all_stop = 1;
+    const bool up = half_bit();
+    unsigned thr[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      thr[g] = (unsigned)min(up ? stopScore[1][g] : stopScore[0][g], 255) << 24;
+      const int myTLen = up ? tLenOn[1][g] : tLenOn[0][g];
+      const unsigned k16 = g ? kv >> 16 : kv & 0xffffu;
+      const unsigned cand = ((k16 & 0xff00u) << 16) | ((unsigned)(0xffff - row[g]) << 8) | (k16 & 0xffu);
+      // a lane's best is frozen once it holds a row that reached the stop score (0: nothing held yet)
+      if (booker && row[g] >= 0 && row[g] < myTLen && (best[g] == 0u || best[g] < thr[g])) best[g] = max(best[g], cand);
+      row[g] += PK_G;
+      const unsigned long long fz = __builtin_amdgcn_ballot_w64(best[g] != 0u && best[g] >= thr[g]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (!stop[h][g] && ((fz & half_mask[h]) != 0 || t + PK_G >= nsteps[h][g])) stop[h][g] = 1;
+        all_stop &= stop[h][g];
+      }
+    }
+    if (all_stop) break;
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      // the first row that reached the stop score, if any; else the best row (SWUtil.scala:532-538) -- over the lanes of half h
+      const unsigned bh = hi == (h == 1) ? best[g] : 0u;
+      const bool frozen = bh != 0u && bh >= ((unsigned)min(stopScore[h][g], 255) << 24);
+      const unsigned long long fz = __builtin_amdgcn_ballot_w64(frozen);
+      unsigned pick = fz ? (frozen ? ((bh >> 8) & 0xffffu) | 0x10000u : 0u) : 0u;   // (0xffff - row): the earliest row wins
+      int src;
+      if (fz) {
+        const int top = wave_max((int)pick);
+        src = __builtin_ctzll(__builtin_amdgcn_ballot_w64((int)pick == top));
+      } else {
+        const int top = wave_max((int)(bh >> 1));   // unsigned order, without the lowest bit
+        // rows differ between lanes, so at most the lowest bit (of the column) cannot decide; candidates are the same row -> same lane
+        src = __builtin_ctzll(__builtin_amdgcn_ballot_w64((int)(bh >> 1) == top));
+      }
+      const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)bh, src);
+      const bool any = on[h][g] && J.tLen[h][g] > 0;
+      const int m = (int)(b >> 24);
+      res[h][g].max = any ? m : MINUS_INF;
+      res[h][g].max_i = any ? 0xffff - (int)((b >> 8) & 0xffffu) : -1;
+      res[h][g].max_j = (any && m) ? 255 - (int)(b & 0xffu) : -1;
+      res[h][g].n_rows = any ? (fz ? res[h][g].max_i + 1 : J.tLen[h][g]) : 0;
+    }
+}
+
+// Two consecutive pairs of a job table (pair `duo` in the lower half of the wave, pair duo + 1 -- when `second` -- in the upper) by
+// one wavefront: the half-wave counterpart of swp_do_duo.  The four jobs' records are neighbours in the table and in `out`.
+template <bool KL>
+__device__ __forceinline__ void swh_do_quartet(const SwJobsDev& jobs, const SwScoring& sc, const int bias, int32_t* __restrict__ out,
+                                               const int duo, const bool second, const int lane, uint32_t* __restrict__ tbuf,
+                                               uint32_t* __restrict__ keys, const int key_stride, uint8_t (*mate_lds)[HW_MATE_LDS],
+                                               DuoDiag& diag) {
+  const int maxScore = 255 - abs(sc.b);  // SWUtil.scala:423
+  const int xtra = sc.xtra;
+  const int minScore = (xtra & BPSW_KSW_XSUBO) ? (xtra & 0xffff) : 0x10000;  // SWUtil.scala:434-437
+  const int endScore0 = (xtra & BPSW_KSW_XSTOP) ? (xtra & 0xffff) : 0x10000;
+  Quad J;
+  J.t_pool = jobs.t_pool;
+  int on[2][2], qCols[2][2], zero4[2][2] = {{0, 0}, {0, 0}}, stop1[2][2], D[2][2];
+  const int job0 = 2 * duo;
+  // the four job records with one load (see swp_do_duo): lanes 8 k .. 8 k + 7 hold job job0 + k
+  uint32_t recw = 0;
+  if (jobs.packed && lane < (second ? 32 : 16) && job0 + (lane >> 3) < jobs.n) recw = jobs.packed[8 * (size_t)job0 + lane];
+  __builtin_amdgcn_wave_barrier();
+  int n_on = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int k = 2 * h + g;
+      on[h][g] = ((h == 0 || second) && job0 + k < jobs.n) ? 1 : 0;
+      n_on += on[h][g];
+      const int jj = on[h][g] ? job0 + k : 0;
+      long long qoff, toff;
+      if (jobs.packed) {
+        const auto field = [&](const int f) { return (unsigned)__builtin_amdgcn_readlane((int)recw, 8 * k + f); };
+        qoff = (long long)(((unsigned long long)field(1) << 32) | field(0));
+        toff = (long long)(((unsigned long long)field(3) << 32) | field(2));
+        J.qLenRaw[h][g] = (int)field(4); J.tLen[h][g] = (int)field(5); J.qrev[h][g] = (int)field(6);
+      } else {
+        J.qLenRaw[h][g] = uni(jobs.q_len[jj]);
+        J.tLen[h][g] = uni(jobs.t_len[jj]);
+        J.qrev[h][g] = uni((int)jobs.q_rev[jj]);
+        qoff = jobs.q_off[jj];
+        toff = jobs.t_off[jj];
+      }
+      uint8_t* mate = mate_lds[k];
+      const uint8_t* src = jobs.q_pool + qoff;
+      const int ncopy = on[h][g] ? min(J.qLenRaw[h][g], HW_MATE_LDS) : 0;
+      for (int i = lane; i < ncopy; i += 64) mate[i] = src[i];
+      J.rb[h][g] = toff;
+      qCols[h][g] = on[h][g] ? min(J.qLenRaw[h][g], HW_QMAX) : 0;
+      stop1[h][g] = min(endScore0, maxScore);  // SWUtil.scala:537
+    }
+  __builtin_amdgcn_wave_barrier();
+  PkRes f[2][2];
+  swh_pass<KL>(lane, J, mate_lds, on, qCols, false, zero4, zero4, jobs.pac, jobs.l_pac, sc, bias, stop1, tbuf, keys, key_stride, D, f);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the keys written by the last-column lanes -> all lanes
+  int score[2][2], te[2][2], qe[2][2], score2[2][2], te2[2][2], tb[2][2], qb[2][2], on2[2][2], qCols2[2][2], stop2[2][2];
+  int any2 = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      score[h][g] = f[h][g].max >= maxScore ? 255 : f[h][g].max;  // SWUtil.scala:544
+      te[h][g] = f[h][g].max_i;
+      qe[h][g] = -1; score2[h][g] = -1; te2[h][g] = -1; tb[h][g] = -1; qb[h][g] = -1;
+      if (on[h][g] && score[h][g] != 255) {  // SWUtil.scala:549-567
+        qe[h][g] = f[h][g].max_j;
+        const int tmp = (score[h][g] + sc.a - 1) / sc.a;
+        second_best(lane, keys + h * key_stride, 16 * g, D[h][g], f[h][g].n_rows, minScore, te[h][g] - tmp, te[h][g] + tmp,
+                    score2[h][g], te2[h][g]);
+      }
+      // SWUtil.scala:586-598
+      const bool want_start = (xtra & BPSW_KSW_XSTART) && !((xtra & BPSW_KSW_XSUBO) && score[h][g] < (xtra & 0xffff));
+      on2[h][g] = (on[h][g] && want_start && qe[h][g] >= 0 && te[h][g] >= 0) ? 1 : 0;
+      any2 |= on2[h][g];
+      qCols2[h][g] = on2[h][g] ? qe[h][g] + 1 : 0;
+      stop2[h][g] = min(score[h][g] & 0xffff, maxScore);
+    }
+  diag.d0 = (unsigned)((on[0][0] ? J.tLen[0][0] : 0) | ((on[0][1] ? J.tLen[0][1] : 0) << 16));
+  diag.d1 = (unsigned)((on[0][0] ? f[0][0].n_rows : 0) | ((on[0][1] ? f[0][1].n_rows : 0) << 16));
+  diag.d2 = (unsigned)((on2[0][0] ? te[0][0] + 1 : 0) | ((on2[0][1] ? te[0][1] + 1 : 0) << 16));
+  diag.d3 = (unsigned)((on[0][0] ? score[0][0] : 0) | ((on[0][1] ? score[0][1] : 0) << 16));
+  if (any2) {
+    PkRes r[2][2];
+    __builtin_amdgcn_wave_barrier();
+    swh_pass<KL>(lane, J, mate_lds, on2, qCols2, true, qe, te, jobs.pac, jobs.l_pac, sc, bias, stop2, tbuf, keys, key_stride, D, r);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        if (on2[h][g]) {
+          const int rscore = r[h][g].max >= maxScore ? 255 : r[h][g].max;
+          if (score[h][g] == rscore) { tb[h][g] = te[h][g] - r[h][g].max_i; qb[h][g] = qe[h][g] - r[h][g].max_j; }
+        }
+      }
+  }
+  {
+    // the four result records with ONE store instruction, a field per lane (see swp_do_duo): the jobs that are on are the first
+    // n_on of the quartet
+    int v = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const int fld[7] = {score[h][g], te[h][g], qe[h][g], score2[h][g], te2[h][g], tb[h][g], qb[h][g]};
+#pragma unroll
+        for (int k = 0; k < 7; ++k) v = lane == 7 * (2 * h + g) + k ? fld[k] : v;
+      }
+    if (lane < 7 * n_on) __hip_atomic_store(out + 7 * (size_t)job0 + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // KL: the packed row keys (one word per step and wave, written by the booking lanes, read once by second_best) stay in LDS --
 // scratch_per_job + PK_KEY_PAD words per wave of dynamic shared memory -- instead of making a round trip through HBM, which was
 // 4.5x the kernel's compulsory traffic (profiles/pmc_traffic.json, round 1).  The launcher picks KL for windows up to
@@ -916,13 +1272,47 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, C <= 3 ? BPSW_SWP_WAVES : 4) 
   BPSW_DIAG_WAVE_END_DUO(3, out, lane);
 }
 
+// The half-wave form of the launch: a wavefront steps over quartets (two consecutive pairs); a trailing single pair runs with the
+// upper half off.  Keys: two rows per wave -- scratch_per_job + PK_KEY_PAD words each in LDS (KL), or the halves of the wave's
+// 4 * scratch_per_job scratch words in HBM.
+template <bool KL>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void swh_kernel(const SwJobsDev jobs, const SwScoring sc, const int bias,
+                                                                     int32_t* __restrict__ out, uint32_t* __restrict__ scratch,
+                                                                     const int scratch_per_job, const SwPrepass* __restrict__ pre) {
+  __shared__ uint32_t tbuf_all[WAVES_PER_BLOCK][2 * HW_TBUF];
+  __shared__ uint8_t mate_all[WAVES_PER_BLOCK][4][HW_MATE_LDS];
+  extern __shared__ uint32_t key_rows[];
+  BPSW_DIAG_WAVE_BEGIN();
+  BPSW_DIAG_DUO_DECL();
+  if (BPSW_SWP_PRIO) __builtin_amdgcn_s_setprio(BPSW_SWP_PRIO);
+  if (pre && (pre->error != 0 || pre->max_qlen > HW_QMAX || ((pre->max_tlen + 63) & ~63) > scratch_per_job)) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = uni((int)(threadIdx.x >> 6));
+  const int slot = uni((int)blockIdx.x * WAVES_PER_BLOCK + wave);
+  const int key_stride = KL ? scratch_per_job + PK_KEY_PAD : 2 * scratch_per_job;
+  uint32_t* keys = KL ? key_rows + (size_t)wave * 2 * (size_t)key_stride : scratch + (size_t)slot * 4 * (size_t)scratch_per_job;
+  const int stride = gridDim.x * WAVES_PER_BLOCK;
+  const int nduo = (jobs.n + 1) >> 1;
+  const int nquad = (nduo + 1) >> 1;
+  DuoDiag diag;
+  for (int quad = slot; quad < nquad; quad += stride)
+    swh_do_quartet<KL>(jobs, sc, bias, out, 2 * quad, 2 * quad + 1 < nduo, lane, tbuf_all[wave], keys, key_stride, mate_all[wave], diag);
+  // (diagnostics builds: the wave log keeps the four words of the last quartet's LOWER pair, as swp_kernel keeps its last pair's)
+  BPSW_DIAG_DUO_SET(diag.d0, diag.d1, diag.d2, diag.d3);
+  BPSW_DIAG_WAVE_END_DUO(3, out, lane);
+}
+
 // The resident form (bpsw_ring.h): the same job pairs, taken one at a time from the descriptors task threads append to the device's
 // submission ring instead of from one launch's table.  Wavefront 0 of workgroup 0 is the ring's poller; every other wavefront is a
 // worker.  The row keys always stay in LDS: `key_rows_cap` rows per wave, fixed for the epoch -- the host sends a call whose longest
 // window has more rows through a launch of its own (swp_kernel).
-template <int C>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, C <= 3 ? BPSW_SWP_WAVES : 4) void swp_resident_kernel(const RingArgs A, const int key_rows_cap) {
-  __shared__ uint32_t tbuf_all[WAVES_PER_BLOCK][PK_TBUF + PK_G];
+// HALVES: the kernel of the half-wave ring class (RING_CLASS_SW_HALVES, bpsw_ring.h): a worker takes two units with one ticket where two are
+// left and runs them as a quartet (swh_do_quartet); a last single unit runs swp_do_duo<3>.  Four waves per SIMD, 128 VGPRs: it holds five
+// columns per lane like class 5.  Without HALVES the kernels of classes 3 and 5 are what they were.
+template <int C, bool HALVES>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (C <= 3 && !HALVES) ? BPSW_SWP_WAVES : 4) void swp_resident_kernel(const RingArgs A, const int key_rows_cap) {
+  // (HALVES: two selector rows and two key rows per wave; the quartet's four mates share the pair's two buffers)
+  __shared__ uint32_t tbuf_all[WAVES_PER_BLOCK][HALVES ? 2 * HW_TBUF : PK_TBUF + PK_G];
   __shared__ uint8_t mate_all[WAVES_PER_BLOCK][2][PK_MATE_LDS];
   extern __shared__ uint32_t key_rows[];
 #ifndef BPSW_RING_PRIO
@@ -936,12 +1326,13 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, C <= 3 ? BPSW_SWP_WAVES : 4) 
     return;
   }
   uint32_t* tbuf = tbuf_all[wave];
-  uint32_t* keys = key_rows + (size_t)wave * (size_t)(key_rows_cap + PK_KEY_PAD);
+  const int key_stride = key_rows_cap + PK_KEY_PAD;
+  uint32_t* keys = key_rows + (size_t)wave * (size_t)(HALVES ? 2 : 1) * (size_t)key_stride;
   RingWorker W;
   DuoDiag diag;
   for (;;) {
-    uint32_t unit = 0, word = 0;
-    if (!ring_next_unit(A, lane, W, unit, word)) break;
+    uint32_t unit = 0, word = 0, taken = 1;
+    if (!ring_next_unit(A, lane, W, unit, word, taken, HALVES)) break;
     const auto f32 = [&](const int k) { return (uint32_t)__builtin_amdgcn_readlane((int)word, k); };
     const auto f64 = [&](const int k) { return ((unsigned long long)f32(k + 1) << 32) | (unsigned long long)f32(k); };
     // the payload (SwRingPayload, words 8..) as the arguments a launch would have got
@@ -960,8 +1351,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, C <= 3 ? BPSW_SWP_WAVES : 4) 
     for (int r = 0; r < 5; ++r) sc.mat.row[r] = f64(22 + 2 * r);
     sc.a = (int)f32(32); sc.b = (int)f32(33); sc.o_del = (int)f32(34); sc.e_del = (int)f32(35);
     sc.o_ins = (int)f32(36); sc.e_ins = (int)f32(37); sc.xtra = (int)f32(38);
-    swp_do_duo<C>(jobs, sc, bias, out, (int)unit, lane, tbuf, keys, mate_all[wave], diag);
-    ring_unit_done(A, lane, W, word);
+    if (HALVES && taken == 2u)
+      swh_do_quartet<true>(jobs, sc, bias, out, (int)unit, true, lane, tbuf, keys, key_stride, (uint8_t (*)[HW_MATE_LDS])mate_all[wave], diag);
+    else
+      swp_do_duo<C>(jobs, sc, bias, out, (int)unit, lane, tbuf, keys, mate_all[wave], diag);
+    ring_unit_done(A, lane, W, word, taken);
   }
 }
 
@@ -1024,6 +1418,19 @@ hipError_t launch_pk(const SwJobsDev& jobs, const SwScoring& sc, int bias, int32
     BPSW_LAUNCH(kev, (swp_kernel<C, true>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, jobs, sc, bias, d_out, d_scratch, per_job, pre);
   } else {
     BPSW_LAUNCH(kev, (swp_kernel<C, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, jobs, sc, bias, d_out, d_scratch, per_job, pre);
+  }
+  return hipGetLastError();
+}
+
+// the half-wave form (swh_kernel): `blocks` workgroups of four waves, a quartet per wave at a time
+hipError_t launch_halves(const SwJobsDev& jobs, const SwScoring& sc, int bias, int32_t* d_out, uint32_t* d_scratch, int per_job,
+                         int blocks, hipStream_t s, const SwPrepass* pre, KernelEvents kev) {
+  static const bool keys_hbm = getenv("BPSW_SW_KEYS_LDS") && atoi(getenv("BPSW_SW_KEYS_LDS")) == 0;  // A/B switch
+  if (per_job <= PK_KEYS_LDS_MAX && !keys_hbm) {
+    const size_t lds = sizeof(uint32_t) * WAVES_PER_BLOCK * 2 * (size_t)(per_job + PK_KEY_PAD);  // <= 52 KB, 63 KB with the static part
+    BPSW_LAUNCH(kev, (swh_kernel<true>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, jobs, sc, bias, d_out, d_scratch, per_job, pre);
+  } else {
+    BPSW_LAUNCH(kev, (swh_kernel<false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, jobs, sc, bias, d_out, d_scratch, per_job, pre);
   }
   return hipGetLastError();
 }
@@ -1107,6 +1514,11 @@ hipError_t launch_sw_kernel(const SwJobsDev& jobs, const SwScoring& sc, int max_
   if (bias >= 0 && max_qlen <= 256 && max_tlen < 65536 && jobs.n > 1) {  // two jobs per wavefront, packed 16-bit
     int pblocks = ((jobs.n + 1) / 2 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (pblocks > max_blocks) pblocks = max_blocks;
+    if (sw_halves_for(max_qlen) && jobs.n > 2) {  // four jobs per wavefront, a packed pair per 32-lane half: mates of <= 150 bases
+      int hblocks = ((jobs.n + 3) / 4 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+      if (hblocks > max_blocks) hblocks = max_blocks;
+      return launch_halves(jobs, sc, bias, d_out, d_scratch, per_job, hblocks, s, d_pre_check, kev);
+    }
     const int pc = (max_qlen + PK_LAST) / (PK_LAST + 1);  // columns per lane over the 64 - PK_TAIL lanes that hold the query
     if (pc <= 1) return launch_pk<1>(jobs, sc, bias, d_out, d_scratch, per_job, pblocks, s, d_pre_check, kev);
     if (pc == 2) return launch_pk<2>(jobs, sc, bias, d_out, d_scratch, per_job, pblocks, s, d_pre_check, kev);
@@ -1134,7 +1546,7 @@ hipError_t launch_sw_kernel(const SwJobsDev& jobs, const SwScoring& sc, int max_
 // ---- the resident form behind the submission ring (bpsw_ring.h) -------------------------------------------------------
 // Rows of packed keys a worker wave keeps in LDS, fixed for an epoch of class c (columns per lane): the windows of 2x150 bp pairs
 // have 500-700 rows, those of 2x250 bp pairs up to ~1200; a call with a longer window takes a launch of its own.
-int swp_resident_key_rows(int c_class) { return c_class <= 3 ? 1024 : PK_KEYS_LDS_MAX; }
+int swp_resident_key_rows(int c_class) { return c_class <= RING_CLASS_SW_HALVES ? 1024 : PK_KEYS_LDS_MAX; }  // (class 5: 1 536)
 
 // The ring class of a batch (= the packed kernel's columns per lane, 1..5), or 0 when it has to be launched on its own: a scoring the
 // packed kernel cannot take, mates above 256 bases, windows longer than the resident kernel's key rows.
@@ -1151,9 +1563,10 @@ int sw_ring_class(const SwScoring& sc, int max_qlen, int max_tlen, int* bias_out
 
 hipError_t launch_swp_resident(int c_class, const RingArgs& A, int blocks, hipStream_t s) {
   const int cap = swp_resident_key_rows(c_class);
-  const size_t lds = sizeof(uint32_t) * WAVES_PER_BLOCK * (size_t)(cap + PK_KEY_PAD);
-  if (c_class == 3) hipLaunchKernelGGL((swp_resident_kernel<3>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
-  else if (c_class == 5) hipLaunchKernelGGL((swp_resident_kernel<5>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
+  const size_t lds = sizeof(uint32_t) * WAVES_PER_BLOCK * (size_t)(cap + PK_KEY_PAD) * (c_class == RING_CLASS_SW_HALVES ? 2 : 1);  // a key row per half
+  if (c_class == 3) hipLaunchKernelGGL((swp_resident_kernel<3, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
+  else if (c_class == RING_CLASS_SW_HALVES) hipLaunchKernelGGL((swp_resident_kernel<3, true>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
+  else if (c_class == 5) hipLaunchKernelGGL((swp_resident_kernel<5, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
