@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "bpsw_chain_batch_ex", "bpsw_last_chain_bytes",
     "bpsw_sam_se_batch", "bpsw_align_se_batch", "bpsw_last_sam_se_times",
     "bpsw_sam_pe_batch_ex", "bpsw_align_pe_batch", "bpsw_last_sam_pe_times",
+    "bpsw_fastq_parse", "bpsw_align_fastq_se", "bpsw_align_fastq_pe", "bpsw_last_fastq_times",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -269,6 +270,16 @@ def _bind_seeding(lib):
         "bpsw_align_pe_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p], C.c_int),
         "bpsw_last_sam_pe_times": ([C.c_void_p], None),
+        # FASTQ text to reads, and to SAM text (bpsw_fastq.hip)
+        "bpsw_fastq_parse": ([C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.c_int64, C.c_size_t, C.c_size_t, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p], C.c_int),
+        "bpsw_align_fastq_se": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int64, C.c_int32, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_int64),
+                                 C.c_void_p], C.c_int),
+        "bpsw_align_fastq_pe": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,
+                                 C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64,
+                                 C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p], C.c_int),
+        "bpsw_last_fastq_times": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -1116,6 +1127,116 @@ def last_sam_pe_times():
     return tuple(ms)
 
 
+# ---- FASTQ text to reads, and to SAM text (bpsw_fastq.hip) ------------------------------------------------------------------------
+FASTQ_FINAL, FASTQ_INTERLEAVED, FASTQ_PAIR_NAMES, FASTQ_HOST = 1, 2, 4, 8   # BPSW_FASTQ_*
+
+
+class FastqError(BpswError):
+    """a failed bpsw_fastq_parse / bpsw_align_fastq_*: rc is the library's code, needed its (reads, pool bytes, name bytes), n_reads what an
+    align entry reported"""
+
+    def __init__(self, msg, rc, needed=(0, 0, 0), n_reads=0):
+        super().__init__(msg)
+        self.rc, self.needed, self.n_reads = rc, tuple(needed), n_reads
+
+
+@dataclass
+class FastqReads:
+    """what bpsw_fastq_parse wrote: the reads in the form SeReadsSoA / TailGroupSoA take, and how far each text was consumed"""
+    n_reads: int
+    consumed: tuple
+    needed: tuple
+    read_len: np.ndarray   # int32 [n]
+    read_off: np.ndarray   # int64 [n]
+    read_pool: np.ndarray  # uint8 codes 0..4
+    qual_pool: np.ndarray  # uint8, same offsets
+    name_off: np.ndarray   # int64 [names + 1]
+    name_pool: np.ndarray  # uint8
+
+
+def fastq_parse(text1: bytes, text2: bytes | None = None, flags: int = 0, max_reads: int | None = None, pool_cap: int | None = None,
+                name_cap: int | None = None, ctx: "Context | None" = None) -> FastqReads:
+    """bpsw_fastq_parse.  Without capacities the arrays are sized from the texts (no record has fewer than four newlines, no pool more
+    bytes than the text); without a context the call needs FASTQ_HOST."""
+    lib = load_library() if ctx is None else ctx.lib
+    size = len(text1 or b"") + len(text2 or b"")
+    mr = (text1 or b"").count(b"\n") // 4 + (text2 or b"").count(b"\n") // 4 + 2 if max_reads is None else int(max_reads)
+    pc = size if pool_cap is None else int(pool_cap)
+    nc = size if name_cap is None else int(name_cap)
+    read_len, read_off, name_off = np.zeros(mr + 1, np.int32), np.zeros(mr + 1, np.int64), np.zeros(mr + 2, np.int64)
+    read_pool, qual_pool, name_pool = np.full(pc + 1, 0xee, np.uint8), np.full(pc + 1, 0xee, np.uint8), np.full(nc + 1, 0xee, np.uint8)
+    n, consumed, needed = C.c_int64(0), np.zeros(2, np.int64), np.zeros(3, np.int64)
+    rc = lib.bpsw_fastq_parse(None if ctx is None else ctx.h, text1, len(text1 or b""), text2, len(text2 or b""), int(flags), mr, pc, nc,
+                              _ptr(read_len), _ptr(read_off), _ptr(read_pool), _ptr(qual_pool), _ptr(name_off), _ptr(name_pool), C.byref(n),
+                              _ptr(consumed), _ptr(needed))
+    if rc != BPSW_OK:
+        raise FastqError(f"bpsw_fastq_parse failed ({rc}): {lib.bpsw_last_error().decode()}", rc, [int(x) for x in needed])
+    # (nothing is written past a capacity: the guard bytes behind each pool are as they were)
+    assert read_pool[pc] == 0xee and qual_pool[pc] == 0xee and name_pool[nc] == 0xee
+    k = int(n.value)
+    pairs = text2 is not None or bool(flags & FASTQ_PAIR_NAMES)
+    names = k // 2 if pairs else k
+    return FastqReads(k, (int(consumed[0]), int(consumed[1])), tuple(int(x) for x in needed), read_len[:k], read_off[:k],
+                      read_pool[: int(needed[1])], qual_pool[: int(needed[1])], name_off[: names + 1], name_pool[: int(needed[2])])
+
+
+def _fastq_text_call(lib, what, texts, call, text_cap, max_reads):
+    """the text protocol of the fastq align entries: call(buf, cap, off, max_reads, need, n_reads) -> (per-read byte strings, n_reads)"""
+    mr = sum(t.count(b"\n") // 4 + 1 for t in texts if t) if max_reads is None else int(max_reads)
+    off = np.zeros(mr + 1, np.int64)
+    need, n = C.c_size_t(0), C.c_int64(0)
+    cap = 512 * max(1, mr) if text_cap is None else int(text_cap)
+    while True:
+        buf = np.empty(max(cap, 1), np.uint8)
+        rc = call(_ptr(buf), cap, _ptr(off), mr, C.byref(need), C.byref(n))
+        if rc == -3 and text_cap is None and need.value > cap:
+            cap = int(need.value)
+            continue
+        if rc != BPSW_OK:
+            raise FastqError(f"{what} failed ({rc}): {lib.bpsw_last_error().decode()}", rc, n_reads=int(n.value))
+        break
+    k = int(n.value)
+    text = buf[: int(off[k])].tobytes()
+    return [text[int(off[i]):int(off[i + 1])] for i in range(k)]
+
+
+def _ctx_align_fastq_se(self, opt: Opt, sopt, topt: "TailOpt", text: bytes, fastq_flags: int = FASTQ_FINAL, id0: int = 0, id_step: int = 1,
+                        zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0, flags: int = 0, text_cap: int | None = None,
+                        max_reads: int | None = None):
+    """FASTQ text -> (SAM texts (bytes) per read, bytes of the text consumed): fastq_parse, then align_se_batch, in one call"""
+    consumed = np.zeros(2, np.int64)
+    texts = _fastq_text_call(self.lib, "bpsw_align_fastq_se", [text],
+                             lambda buf, cap, off, mr, need, n: self.lib.bpsw_align_fastq_se(
+                                 self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text, len(text), int(fastq_flags), int(id0), int(id_step),
+                                 zdrop_mode, w1_flags, flags, buf, cap, off, mr, need, n, _ptr(consumed)), text_cap, max_reads)
+    return texts, int(consumed[0])
+
+
+def _ctx_align_fastq_pe(self, opt: Opt, sopt, topt: "TailOpt", text1: bytes, text2: bytes | None = None, fastq_flags: int = FASTQ_FINAL,
+                        id0: int = 0, pes0=None, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0, rescue_mode: int = RESCUE_C, flags: int = 0,
+                        text_cap: int | None = None, max_reads: int | None = None):
+    """FASTQ texts of pairs (two, or one with FASTQ_INTERLEAVED) -> (SAM texts per read, the statistics used, bytes consumed of each
+    text): fastq_parse, then align_pe_batch, in one call"""
+    consumed = np.zeros(2, np.int64)
+    pes_in = None if pes0 is None else _pes_struct(pes0)
+    pes = (PeStat * 4)()
+    texts = _fastq_text_call(self.lib, "bpsw_align_fastq_pe", [text1, text2],
+                             lambda buf, cap, off, mr, need, n: self.lib.bpsw_align_fastq_pe(
+                                 self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text1, len(text1), text2, len(text2 or b""),
+                                 int(fastq_flags), int(id0), pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, cap, off, mr, need, pes, n,
+                                 _ptr(consumed)), text_cap, max_reads)
+    return (texts, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)],
+            (int(consumed[0]), int(consumed[1])))
+
+
+def last_fastq_times():
+    """(fastq_count_kernel, fastq_lines_kernel, fastq_record_kernel, fastq_emit_kernel, the parse's round trip) in ms of this thread's
+    last fastq_parse / align_fastq_*"""
+    ms = (C.c_double * 5)()
+    load_library().bpsw_last_fastq_times(ms)
+    return tuple(ms)
+
+
 TAIL_POOL_TAIL_ONLY = -1
 
 
@@ -1199,6 +1320,9 @@ Context.last_tail_resubmitted = _ctx_last_tail_resubmitted
 Context.sam_se_batch = _ctx_sam_se_batch
 Context.align_se_batch = _ctx_align_se_batch
 Context.align_pe_batch = _ctx_align_pe_batch
+Context.fastq_parse = lambda self, text1, text2=None, flags=0, **kw: fastq_parse(text1, text2, flags, ctx=self, **kw)
+Context.align_fastq_se = _ctx_align_fastq_se
+Context.align_fastq_pe = _ctx_align_fastq_pe
 Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute units of the context's device
 
 

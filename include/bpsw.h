@@ -667,6 +667,58 @@ int bpsw_align_pe_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_
  * bpsw_align_pe_batch: its worker1 stage, the statistics, the rescue, the tail. */
 void bpsw_last_sam_pe_times(double ms[8]);
 
+/* ---- FASTQ text to reads, and FASTQ text to SAM text (bpsw_fastq.hip) --------------------------------------------------------
+ *
+ * bpsw_fastq_parse turns a chunk of four-line FASTQ text in memory into the form the entries above take: base codes 0..4 and
+ * qualities in two pools at the same offsets, read_len / read_off (one entry per read), names in a pool with name_off (one more
+ * entry than names).  The record rules are csrc/bpsw_fastq_core.h's and follow the reference's C (kseq_read and bseq_read with
+ * trim_readno): a line ends at '\n' and loses one '\r' in front of it when it has more than one byte; line 4r begins with '@', line
+ * 4r + 2 with '+' (its rest is ignored), line 4r + 3 is as long as line 4r + 1, which is not empty; the name is what follows '@' up
+ * to the first isspace byte, without a trailing "/" + digit when it is longer than 2 bytes, and not empty; Aa Cc Gg Tt are 0..3 and
+ * every other base is 4, except '-' and bytes below 4, which are refused; qualities are copied.  gzip, multi-line records, blank
+ * lines between records and the comment field are not handled (the first three are refused as "not four-line FASTQ").
+ *
+ * text1 / bytes1, text2 / bytes2: one text (text2 NULL, bytes2 0), or the two texts of paired reads -- record k of text1 is read 2k,
+ * record k of text2 read 2k + 1, as bseq_read interleaves them.  Only whole records are parsed: consumed[i] is the offset just
+ * behind the last parsed record of text i + 1, for the caller to carry the remainder into its next chunk.  With two texts the number
+ * of records is the smaller of the two, and both consumed values stop there.  An empty text is *n_reads == 0.  flags:
+ *   BPSW_FASTQ_FINAL        the text ends here: a last line without '\n' counts as a line, and a trailing part that is still not a
+ *                           whole record is refused.  Without it such a part is just left unconsumed.
+ *   BPSW_FASTQ_INTERLEAVED  one text whose records alternate between the two ends; an odd record count leaves the last unconsumed.
+ *   BPSW_FASTQ_PAIR_NAMES   one name per pair, the first end's (what bpsw_pairs_t takes); the second end's name, after the same
+ *                           rules, must equal it.  Implied by two texts; with one text it needs BPSW_FASTQ_INTERLEAVED.
+ *   BPSW_FASTQ_HOST         apply the same rules serially on the calling thread: nothing is launched, ctx may be NULL.
+ * Any other flag is BPSW_ERR_ARG.  Capacities: read_len and read_off have max_reads entries, name_off max_reads + 1, the two pools
+ * pool_cap bytes each, name_pool name_cap bytes.  When any of them is too small the call returns BPSW_ERR_CAPACITY with needed[3] =
+ * {reads, pool bytes, name bytes} of this text, all three, and writes nothing; needed is also set when the call succeeds.  A
+ * malformed record is BPSW_ERR_ARG and wins over a capacity: the call reports the lowest such read, and the error text names the
+ * entry, the record, the text (1 or 2) and the reason.  A text of 2^31 bytes or more is BPSW_ERR_LIMIT.
+ *
+ * bpsw_align_fastq_se / bpsw_align_fastq_pe: the parse, then bpsw_align_se_batch / bpsw_align_pe_batch on its result, in one call.
+ * fastq_flags are the parse's (the paired entry takes two texts, or one with BPSW_FASTQ_INTERLEAVED; one name per pair either way);
+ * every other argument, the text contract (out_text, text_cap, out_off, *out_needed, BPSW_ERR_CAPACITY) and the refusals are the
+ * align entry's.  Single-end reads are hashed as id0 + r * id_step, pairs as id0 + k.  out_off has max_reads + 1 entries: a text
+ * with more reads is BPSW_ERR_CAPACITY with *n_reads set.  *n_reads and consumed come back as from the parse. */
+#define BPSW_FASTQ_FINAL 1
+#define BPSW_FASTQ_INTERLEAVED 2
+#define BPSW_FASTQ_PAIR_NAMES 4
+#define BPSW_FASTQ_HOST 8
+int bpsw_fastq_parse(bpsw_ctx_t *ctx, const char *text1, size_t bytes1, const char *text2, size_t bytes2, int flags, int64_t max_reads,
+                     size_t pool_cap, size_t name_cap, int32_t *read_len, int64_t *read_off, uint8_t *read_pool, uint8_t *qual_pool,
+                     int64_t *name_off, char *name_pool, int64_t *n_reads, int64_t consumed[2], int64_t needed[3]);
+int bpsw_align_fastq_se(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                        const char *text, size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags,
+                        int flags, char *out_text, size_t text_cap, int64_t *out_off, int64_t max_reads, size_t *out_needed,
+                        int64_t *n_reads, int64_t *consumed);
+int bpsw_align_fastq_pe(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                        const char *text1, size_t bytes1, const char *text2, size_t bytes2, int fastq_flags, int64_t id0,
+                        const bpsw_pestat_t *pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char *out_text,
+                        size_t text_cap, int64_t *out_off, int64_t max_reads, size_t *out_needed, bpsw_pestat_t *out_pes,
+                        int64_t *n_reads, int64_t consumed[2]);
+/* Diagnostics, of the calling thread's most recent parse (ms): fastq_count_kernel, fastq_lines_kernel, fastq_record_kernel,
+ * fastq_emit_kernel (events on the stream around each; 0 under BPSW_FASTQ_HOST), and the parse's round trip with the copies. */
+void bpsw_last_fastq_times(double ms[5]);
+
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {
   uint64_t ext_calls, ext_tasks, ext_wire_bytes;
