@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "bpsw_set_ext_scoring", "bpsw_set_ext_shortcuts", "bpsw_extend_batch", "bpsw_extend_stage", "bpsw_extend_commit", "bpsw_extend_batch_classify", "bpsw_extend_batch_device", "bpsw_wire_size", "bpsw_wire_pack", "bpsw_wire_coords_size", "bpsw_wire_coords_pack",
     "bpsw_opt_default", "bpsw_swalign2_batch", "bpsw_swalign2_batch_device", "bpsw_matesw_group", "bpsw_global_batch",
     "bpsw_get_stats", "bpsw_reset_stats", "bpsw_last_kernel_ms", "bpsw_ring_stats", "bpsw_sw_batches_in_flight", "bpsw_ring_integrity",
+    "bpsw_ext_group_waiting", "bpsw_ext_group_counts",
     "bpsw_ref_load", "bpsw_ref_unload", "bpsw_ref_length", "bpsw_ref_fetch", "bpsw_chain2aln_batch",
     "bpsw_tail_opt_default", "bpsw_bns_load", "bpsw_reg2aln_batch", "bpsw_sam_pe_batch", "bpsw_worker2_batch", "bpsw_last_tail_times", "bpsw_last_tail_resubmitted",
     "bpsw_tail_pool_create", "bpsw_tail_pool_destroy", "bpsw_tail_pool_submit", "bpsw_tail_pool_wait", "bpsw_tail_pool_workers",
@@ -195,6 +196,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.bpsw_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.bpsw_ring_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.bpsw_sw_batches_in_flight.argtypes = [C.c_int]
+    lib.bpsw_ext_group_waiting.argtypes = [C.c_int]
+    lib.bpsw_ext_group_counts.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
     lib.bpsw_ring_integrity.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bpsw_chain2aln_batch.argtypes = [C.c_void_p, C.POINTER(Opt), C.POINTER(Chains), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.POINTER(C.c_int64)]
@@ -685,6 +688,16 @@ class Context:
     def sw_batches_in_flight(self):
         """gauge: SW batches of any context in their device phase on this context's device (include/bpsw.h)"""
         return int(self.lib.bpsw_sw_batches_in_flight(self.lib.bpsw_device_of(self.h)))
+
+    def ext_group_waiting(self):
+        """gauge: extension calls of the grouped plan waiting for a pooled stream of this context's device (include/bpsw.h)"""
+        return int(self.lib.bpsw_ext_group_waiting(self.lib.bpsw_device_of(self.h)))
+
+    def ext_group_counts(self):
+        """(launch chains of the grouped plan, their members summed, the largest group) on this context's device, process-wide"""
+        out = (C.c_uint64 * 3)()
+        _chk(self.lib, self.lib.bpsw_ext_group_counts(self.lib.bpsw_device_of(self.h), out), "bpsw_ext_group_counts")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def ring_epoch_times(self):
         """(summed duration in ms, count) of the device's ring epochs that are over: each the resident kernel's launch as a kernel trace times it"""

@@ -22,6 +22,7 @@
 // flanks above 255 bases) for what the host lists.  A task's body is ext_do_task, shared with ext_resident_kernel: the
 // short kernel's resident form behind the device's extension ring (bpsw_ring.h), which takes the small batches without a launch.
 #include <stdlib.h>
+#include <string.h>
 
 #include <atomic>
 
@@ -246,22 +247,24 @@ __device__ __forceinline__ void ext_do_task(const int task, const int sifted, co
 // far, defer[1..] = task indices), which the full kernel, launched behind this one on the stream, reads its task count from -- only by
 // the asynchronous device entry, where no host has listed the long tasks, and by the test hook below.
 // SHORT = 0: the full kernel (slot sweeps for wide bands, an LDS-row sweep for flanks above 255 bases).
-template <bool COORD, int SHORT>
 #ifndef BPSW_EXT_SHORT_WAVES_PER_SIMD
 #define BPSW_EXT_SHORT_WAVES_PER_SIMD 8
 #endif
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, SHORT ? BPSW_EXT_SHORT_WAVES_PER_SIMD : BPSW_EXT_WAVES_PER_SIMD) void ext_kernel(const uint32_t* __restrict__ wire, const int n_tasks_arg,
-                                                                     int16_t* __restrict__ out, const ExtScoring sc,
-                                                                     const int qcap, const int rcap,
-                                                                     const int lds_per_wave, const int chunk, const int guide_cap,
-                                                                     int* __restrict__ next_task,
-                                                                     const int* __restrict__ task_list_arg,
-                                                                     const ExtPrepass* __restrict__ pre,
-                                                                     int* __restrict__ defer, const int short_qmax,
-                                                                     const uint8_t* __restrict__ sift_flag,
-                                                                     const uint4* __restrict__ sift_recs,
-                                                                     int* __restrict__ defer_post,
-                                                                     const int* __restrict__ todo_list, const int inject_defer) {
+// One batch's share of a launch: the workgroups of one `y` slice of the grid (ext_kernel below), gridDim.x of them, over that batch's
+// own queue words, lists and results.
+template <bool COORD, int SHORT>
+__device__ __forceinline__ void ext_batch_body(const uint32_t* __restrict__ wire, const int n_tasks_arg,
+                                               int16_t* __restrict__ out, const ExtScoring& sc,
+                                               const int qcap, const int rcap,
+                                               const int lds_per_wave, const int chunk, const int guide_cap,
+                                               int* __restrict__ next_task,
+                                               const int* __restrict__ task_list_arg,
+                                               const ExtPrepass* __restrict__ pre,
+                                               int* __restrict__ defer, const int short_qmax,
+                                               const uint8_t* __restrict__ sift_flag,
+                                               const uint4* __restrict__ sift_recs,
+                                               int* __restrict__ defer_post,
+                                               const int* __restrict__ todo_list, const int inject_defer) {
   extern __shared__ __align__(16) unsigned char smem[];
   BPSW_DIAG_WAVE_BEGIN();
   BPSW_DIAG_TASKS_DECL();
@@ -357,6 +360,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, SHORT ? BPSW_EXT_SHORT_WAVES_
     BPSW_DIAG_TASK_END();
   }
   BPSW_DIAG_WAVE_END_TASKS(SHORT ? 1 : 0, next_task, lane);
+}
+
+// The launch: gridDim.y batches (ExtGroupArgs, bpsw_internal.h: the descriptors travel by value in the kernel arguments and are read
+// with scalar loads, as the arguments of a single batch were), gridDim.x persistent workgroups for each.  A workgroup serves the batch
+// of its `y` slice; everything per batch -- the self-resetting queue, the count of waves that have left, the posted defer length --
+// counts the gridDim.x workgroups of that slice alone.  The LDS geometry belongs to the launch: the largest any member needs.
+template <bool COORD, int SHORT>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, SHORT ? BPSW_EXT_SHORT_WAVES_PER_SIMD : BPSW_EXT_WAVES_PER_SIMD) void ext_kernel(const ExtGroupArgs G, const int qcap, const int rcap,
+                                                                     const int lds_per_wave, const int chunk, const int guide_cap,
+                                                                     const int inject_defer) {
+  const ExtMember& M = G.m[blockIdx.y];
+  ext_batch_body<COORD, SHORT>(M.wire, M.n_tasks, M.out, M.sc, qcap, rcap, lds_per_wave, chunk, guide_cap, M.queue, M.task_list, M.pre, M.defer,
+                               M.short_qmax, M.sift_flag, M.sift_recs, M.defer_post, M.todo_list, inject_defer);
 }
 
 // ---- table scan: validates the batch and finds the LDS capacities the main launch needs --------
@@ -483,15 +499,13 @@ void launch_ext_prepass(const uint32_t* d_wire, size_t wire_words, int n_tasks, 
                      n_tasks, d_pre);
 }
 
-hipError_t launch_ext_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int qcap,
-                             int rcap, int num_cu, int* d_counter, const int* d_task_list, hipStream_t s,
-                             const ExtPrepass* d_pre_check, bool counter_zeroed, KernelEvents kev, bool short_kernel, int* d_defer,
-                             int short_qmax, const uint8_t* d_sift_flag, const uint4* d_sift_recs, int* d_defer_post, const int* d_todo_list) {
-  if (n_tasks <= 0) return hipSuccess;  // (the full kernel behind a SHORT launch: n_tasks = the most its device-side list can hold)
-  if (short_kernel && !d_defer) return hipErrorInvalidValue;  // the deferring build needs somewhere to defer to
+// One launch of ext_kernel over k batches (k = 1: what every launch was before the calls that wait for a stream were grouped).  qcap / rcap:
+// the largest any member needs; n_grid: the largest task count, which sizes the gridDim.x workgroups every member gets.
+static hipError_t launch_ext_members(const ExtMember* m, int k, int n_grid, int qcap, int rcap, int num_cu, hipStream_t s, KernelEvents kev, bool short_kernel) {
+  if (k < 1 || k > EXT_GROUP_SLOTS) return hipErrorInvalidValue;
   static const int inject_env = getenv("BPSW_EXT_INJECT_DEFER") ? atoi(getenv("BPSW_EXT_INJECT_DEFER")) : 0;  // test hook (tests/test_extend_gpu.py)
   const int inject_defer = short_kernel ? inject_env : 0;
-  const bool coord = sc.pac != nullptr;  // a coordinate batch (the caller sets ExtScoring::pac only for those)
+  const bool coord = m[0].sc.pac != nullptr;  // a coordinate batch (the caller sets ExtScoring::pac only for those)
   const int variant = short_kernel ? 1 : 0;
   const void* fn = variant == 0 ? (coord ? reinterpret_cast<const void*>(ext_kernel<true, 0>) : reinterpret_cast<const void*>(ext_kernel<false, 0>))
                                 : (coord ? reinterpret_cast<const void*>(ext_kernel<true, 1>) : reinterpret_cast<const void*>(ext_kernel<false, 1>));
@@ -532,17 +546,18 @@ hipError_t launch_ext_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out
   static const double cap_per_cu_short = getenv("BPSW_EXT_SHORT_BLOCKS_PER_CU") ? atof(getenv("BPSW_EXT_SHORT_BLOCKS_PER_CU")) : 1.25;
   double per_cu_f = per_cu < 1 ? 1.0 : (double)per_cu;
   if (per_cu_f > (short_kernel ? cap_per_cu_short : cap_per_cu)) per_cu_f = short_kernel ? cap_per_cu_short : cap_per_cu;
-  int blocks = (n_tasks + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+  // (per member: the members of a group are the launches that would have been resident together on streams of their own)
+  int blocks = (n_grid + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
   int max_blocks = (int)(num_cu * per_cu_f);
   if (max_blocks < 1) max_blocks = 1;
   if (blocks > max_blocks) blocks = max_blocks;
-  (void)counter_zeroed;  // the queue head (d_counter[0], [1]) is zero between launches: the kernel's last wave resets it
   // tasks per dequeue: 0 = guided (see the kernel), n > 0 = fixed chunks of n (1 balances a lone launch best)
   static const int chunk = [] { const int v = getenv("BPSW_EXT_CHUNK") ? atoi(getenv("BPSW_EXT_CHUNK")) : 0; return v < 0 ? 0 : (v > 64 ? 64 : v); }();  // 0: guided
   constexpr int guide_cap = 8;
+  ExtGroupArgs G;
+  for (int i = 0; i < EXT_GROUP_SLOTS; ++i) G.m[i] = m[i < k ? i : 0];  // (the slots past k are never read: no workgroup has their y)
 #define BPSW_EXT_GO(CO, SH)                                                                                                     \
-  BPSW_LAUNCH(kev, (ext_kernel<CO, SH>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, d_wire, n_tasks, d_out, sc, qcap, rcap, \
-              (int)per_wave, chunk, guide_cap, d_counter, d_task_list, d_pre_check, d_defer, short_qmax, d_sift_flag, d_sift_recs, d_defer_post, d_todo_list, inject_defer)
+  BPSW_LAUNCH(kev, (ext_kernel<CO, SH>), dim3(blocks, k), dim3(64 * WAVES_PER_BLOCK), lds, s, G, qcap, rcap, (int)per_wave, chunk, guide_cap, inject_defer)
   if (variant == 1) {
     if (coord) BPSW_EXT_GO(true, 1); else BPSW_EXT_GO(false, 1);
   } else {
@@ -550,6 +565,42 @@ hipError_t launch_ext_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out
   }
 #undef BPSW_EXT_GO
   return hipGetLastError();
+}
+
+hipError_t launch_ext_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int qcap,
+                             int rcap, int num_cu, int* d_counter, const int* d_task_list, hipStream_t s,
+                             const ExtPrepass* d_pre_check, bool counter_zeroed, KernelEvents kev, bool short_kernel, int* d_defer,
+                             int short_qmax, const uint8_t* d_sift_flag, const uint4* d_sift_recs, int* d_defer_post, const int* d_todo_list) {
+  if (n_tasks <= 0) return hipSuccess;  // (the full kernel behind a SHORT launch: n_tasks = the most its device-side list can hold)
+  if (short_kernel && !d_defer) return hipErrorInvalidValue;  // the deferring build needs somewhere to defer to
+  (void)counter_zeroed;  // the queue head (d_counter[0], [1]) is zero between launches: the kernel's last wave resets it
+  ExtMember m;  // a group of one
+  memset(&m, 0, sizeof m);
+  m.wire = d_wire; m.n_tasks = n_tasks; m.out = d_out; m.sc = sc; m.queue = d_counter; m.task_list = d_task_list; m.pre = d_pre_check;
+  m.defer = d_defer; m.short_qmax = short_qmax; m.sift_flag = const_cast<uint8_t*>(d_sift_flag); m.sift_recs = const_cast<uint4*>(d_sift_recs);
+  m.defer_post = d_defer_post; m.todo_list = const_cast<int*>(d_todo_list);
+  return launch_ext_members(&m, 1, n_tasks, qcap, rcap, num_cu, s, kev, short_kernel);
+}
+
+// The calls that waited for a stream together (bpsw_ext_group.h): the sift kernel, then the short kernel, one launch each over the
+// k members.  Byte batches behind the sift only (the plan extend_batch_impl calls compatible).  kev: start rides on the sift kernel's
+// dispatch, stop on the short kernel's.
+hipError_t launch_ext_group(const ExtGroupMember* members, int k, int num_cu, hipStream_t s, KernelEvents kev) {
+  if (k < 1 || k > EXT_GROUP_SLOTS) return hipErrorInvalidValue;
+  ExtMember m[EXT_GROUP_SLOTS];
+  int qcap = 0, rcap = 0, n_grid = 0;
+  for (int i = 0; i < k; ++i) {
+    m[i] = members[i].m;
+    if (m[i].n_tasks <= 0 || !m[i].defer || !m[i].sift_flag || !m[i].todo_list || m[i].sc.pac) return hipErrorInvalidValue;
+    qcap = members[i].qcap > qcap ? members[i].qcap : qcap;
+    rcap = members[i].rcap > rcap ? members[i].rcap : rcap;
+    n_grid = m[i].n_tasks > n_grid ? m[i].n_tasks : n_grid;
+  }
+  KernelEvents sev, xev;
+  sev.start = kev.start; xev.stop = kev.stop;
+  hipError_t e = launch_ext_sift_members(m, k, n_grid, s, sev);
+  if (e != hipSuccess) return e;
+  return launch_ext_members(m, k, n_grid, qcap, rcap, num_cu, s, xev, true);
 }
 
 }  // namespace bpsw

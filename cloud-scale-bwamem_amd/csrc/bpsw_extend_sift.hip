@@ -32,6 +32,8 @@
 // the verdicts side by side).
 // Cites: the forms follow SWUtil.scala:61-230 / MemChainToAlignBatched.scala:789-883 exactly as bpsw_extend_core.h derives them;
 // the chaining of the two sides mirrors ext_kernel (bpsw_extend.hip).
+#include <string.h>
+
 #include "bpsw_extend_core.h"
 #include "bpsw_extend_sift_core.h"
 
@@ -88,12 +90,22 @@ __device__ __forceinline__ uint4 pack_rec(const SideRec& r) {
 
 constexpr int SIFT_T_WORDS = 21;  // a coordinate task's staged target flank: 127 + SIFT_MAX_SHIFTS + 4 bases and a spare word, odd (LDS banks)
 
-// one wavefront per workgroup, 64 consecutive tasks
+// one wavefront per workgroup, 64 consecutive tasks of the batch of the workgroup's `y` slice (ExtGroupArgs, bpsw_internal.h: gridDim.y
+// batches a launch, as for ext_kernel; gridDim.x covers the largest of them)
 template <bool COORD>
-__global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict__ wire, const int n_tasks, int16_t* __restrict__ out,
-                                                      const ExtScoring sc, const int dm, const int dn, const int qmax, uint8_t* __restrict__ flag,
-                                                      uint4* __restrict__ recs, const ExtPrepass* __restrict__ pre,
-                                                      int* __restrict__ todo_count, int* __restrict__ todo_list, const int heavy_min) {
+__global__ __launch_bounds__(64) void ext_sift_kernel(const ExtGroupArgs G) {
+  const ExtMember& M = G.m[blockIdx.y];
+  const uint32_t* __restrict__ wire = M.wire;
+  const int n_tasks = M.n_tasks;
+  if ((int)blockIdx.x * 64 >= n_tasks) return;  // a smaller batch than the one the grid was sized for
+  int16_t* __restrict__ out = M.out;
+  const ExtScoring& sc = M.sc;
+  const int dm = M.sift_dm, dn = M.sift_dn, qmax = M.sift_qmax, heavy_min = M.heavy_min;
+  uint8_t* __restrict__ flag = M.sift_flag;
+  uint4* __restrict__ recs = M.sift_recs;
+  const ExtPrepass* __restrict__ pre = M.pre;
+  int* __restrict__ todo_count = M.todo_count;
+  int* __restrict__ todo_list = M.todo_list;
   // asynchronous entry (bpsw_extend_batch_device): the table scan ran just before on the same stream and nobody has read it back
   // yet -- a malformed batch is left untouched (ext_kernel behind this launch does the same and never looks at the flags)
   if (pre && pre->error != 0) return;
@@ -288,15 +300,25 @@ __global__ __launch_bounds__(64) void ext_sift_kernel(const uint32_t* __restrict
 
 }  // namespace
 
+hipError_t launch_ext_sift_members(const ExtMember* m, int k, int n_grid, hipStream_t s, KernelEvents kev) {
+  if (k < 1 || k > EXT_GROUP_SLOTS || n_grid <= 0) return hipErrorInvalidValue;
+  const int blocks = (n_grid + 63) / 64;
+  ExtGroupArgs G;
+  for (int i = 0; i < EXT_GROUP_SLOTS; ++i) G.m[i] = m[i < k ? i : 0];
+  if (m[0].sc.pac) BPSW_LAUNCH(kev, ext_sift_kernel<true>, dim3(blocks, k), dim3(64), 0, s, G);
+  else BPSW_LAUNCH(kev, ext_sift_kernel<false>, dim3(blocks, k), dim3(64), 0, s, G);
+  return hipGetLastError();
+}
+
 hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* d_out, const ExtScoring& sc, int dmn, int qmax,
                                   uint8_t* d_flag, uint4* d_recs, hipStream_t s, KernelEvents kev, const ExtPrepass* d_pre_check,
                                   int* d_todo_count, int* d_todo_list, int heavy_min) {
   if (n_tasks <= 0) return hipSuccess;
-  const int blocks = (n_tasks + 63) / 64;
-  const int dm = dmn & 0xffff, dn = dmn >> 16;
-  if (sc.pac) BPSW_LAUNCH(kev, ext_sift_kernel<true>, dim3(blocks), dim3(64), 0, s, d_wire, n_tasks, d_out, sc, dm, dn, qmax, d_flag, d_recs, d_pre_check, d_todo_count, d_todo_list, heavy_min);
-  else BPSW_LAUNCH(kev, ext_sift_kernel<false>, dim3(blocks), dim3(64), 0, s, d_wire, n_tasks, d_out, sc, dm, dn, qmax, d_flag, d_recs, d_pre_check, d_todo_count, d_todo_list, heavy_min);
-  return hipGetLastError();
+  ExtMember m;  // a group of one
+  memset(&m, 0, sizeof m);
+  m.wire = d_wire; m.n_tasks = n_tasks; m.out = d_out; m.sc = sc; m.sift_dm = dmn & 0xffff; m.sift_dn = dmn >> 16; m.sift_qmax = qmax;
+  m.sift_flag = d_flag; m.sift_recs = d_recs; m.pre = d_pre_check; m.todo_count = d_todo_count; m.todo_list = d_todo_list; m.heavy_min = heavy_min;
+  return launch_ext_sift_members(&m, 1, n_tasks, s, kev);
 }
 
 }  // namespace bpsw

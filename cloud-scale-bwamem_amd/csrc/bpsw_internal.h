@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "bpsw.h"
+#include "bpsw_ext_group.h"
 #include "bpsw_ring.h"
 
 struct bpsw_ctx;
@@ -100,6 +101,42 @@ hipError_t launch_ext_sift_kernel(const uint32_t* d_wire, int n_tasks, int16_t* 
 // a flank the sift does not examine.  launch_ext_kernel with the same list takes its tickets from it, the back first.  The
 // counts are the third and fourth word of the queue heads, d_counter[2..3]: zero between launches, ext_kernel's last wave puts
 // them back.)
+// One batch as the extension kernels see it: what the arguments of a launch held for its one batch, as a descriptor.  A launch takes
+// up to EXT_GROUP_SLOTS of them by value in its kernel arguments (ExtGroupArgs) and gridDim.y = the number it was given; a workgroup
+// serves the batch of its `y` slice.  The LDS geometry belongs to the launch.  queue: the four queue words of the batch's context
+// (head, waves gone, to-do counts); todo_count: queue + 2 where the sift kernel lists what it leaves (null: it lists nothing).
+struct ExtMember {
+  const uint32_t* wire;
+  int16_t* out;
+  int* queue;
+  const int* task_list;
+  const ExtPrepass* pre;
+  int* defer;
+  int* defer_post;
+  uint8_t* sift_flag;
+  uint4* sift_recs;
+  int* todo_count;
+  int* todo_list;
+  ExtScoring sc;
+  int n_tasks, short_qmax;
+  int sift_dm, sift_dn, sift_qmax, heavy_min;  // the sift kernel's: launch_ext_sift_kernel's dmn, qmax, heavy_min
+};
+constexpr int EXT_GROUP_SLOTS = 8;
+struct ExtGroupArgs {
+  ExtMember m[EXT_GROUP_SLOTS];
+};
+static_assert(sizeof(ExtGroupArgs) <= 2048, "the descriptors travel in the kernel arguments (4 KB in all)");
+// a member of a group on the host: its descriptor and the LDS capacities its short kernel would have been launched with
+struct ExtGroupMember {
+  ExtMember m;
+  int qcap, rcap;
+};
+hipError_t launch_ext_sift_members(const ExtMember* m, int k, int n_grid, hipStream_t s, KernelEvents kev);  // bpsw_extend_sift.hip
+// The calls that waited for a stream together (bpsw_ext_group.h), as ONE launch chain: the sift kernel, then the short kernel, each over
+// the k members (1 <= k <= EXT_GROUP_SLOTS; byte batches behind the sift only).  kev.start rides on the sift kernel's dispatch, kev.stop
+// on the short kernel's.  Referenced weakly (bpsw_runtime.cpp): a library made of the host sources alone has no such entry, and every
+// call there is a group of one through the two entries above.
+extern "C" hipError_t launch_ext_group(const ExtGroupMember* members, int k, int num_cu, hipStream_t s, KernelEvents kev);  // (C linkage: `#pragma weak` names it)
 int sift_uniform_dm(const int8_t mat[25], int exact_a);  // > 0 when all twelve base-vs-other-base entries equal exact_a - dm, else 0
 int sift_uniform_dn(const int8_t mat[25], int exact_a);  // > 0 when all nine entries that involve N equal exact_a - dn, else 0
 // ---- local SW (boundary 1) ---------------------------------------------------------------------
@@ -407,13 +444,17 @@ DeviceRef& device_ref(int device);
 // 131, 18: 136, 20: 138, 22: 141 M reads/s, 24: 59, 32: 34).  So the device phases of all contexts of a device
 // share a pool of BPSW_STREAM_POOL streams (default 20; 0 = every context uses its own stream): an executor may run more
 // task threads than the device has queues, and their host phases overlap the others' device phases.
+// A caller that finds every pooled stream busy waits in the pool's queue (bpsw_ext_group.h), oldest first.  An extension call of the
+// grouped plan passes its waiter: it may come back as the leader of the waiters in members[0..*n_members) (room for EXT_GROUP_SLOTS - 1),
+// whose batches it launches with its own, or `led`: another caller's launch chain has served it and it holds no stream.
 struct StreamLease {
   int device;
   hipStream_t s;
   bool pooled;
+  bool led = false;
   int slot = -1;   // index of the pooled stream
   double wait_ms;  // time spent waiting for a free stream
-  explicit StreamLease(bpsw_ctx* c);
+  explicit StreamLease(bpsw_ctx* c, ExtGroupWaiter* w = nullptr, ExtGroupWaiter** members = nullptr, int* n_members = nullptr);
   ~StreamLease();
   StreamLease(const StreamLease&) = delete;
   StreamLease& operator=(const StreamLease&) = delete;
@@ -426,6 +467,10 @@ struct CopyLane {
 };
 CopyLane& copy_lane(int device);
 double wall_ms();  // the monotonic clock, in ms
+int ext_group_max();                 // BPSW_EXT_GROUP_MAX: the largest group of extension calls on one launch chain (1: none)
+int ext_group_waiting(int device);   // extension calls of the grouped plan in the pool's queue right now
+void ext_group_counts(int device, unsigned long long out[3]);  // groups launched, members summed, largest group
+void ext_group_complete(int device, ExtGroupWaiter** members, int n_members, int status, float span_ms);  // the leader's, after its wait
 void ext_call_mark(int device);      // an extension call of the device begins / ends now (bpsw_runtime.cpp)
 double ext_call_age_ms(int device);  // ms since the last such mark (huge: never)
 double stat_ms();  // wall_ms, or the thread CPU clock with BPSW_STATS_CLOCK=cpu (bpsw_runtime.cpp)

@@ -13,6 +13,10 @@
 #include <atomic>
 #include <condition_variable>
 
+// launch_ext_group (bpsw_extend.hip) is referenced weakly, as bpsw_jni.cpp references the seeding entries: it is absent from a library
+// made of the host sources alone -- the sanitizer builds of tests/host_san --, where every extension call is a group of one through
+// launch_ext_sift_kernel / launch_ext_kernel.  (Ahead of its declaration: the name has C linkage but is declared in a namespace.)
+#pragma weak launch_ext_group
 #include "bpsw_internal.h"
 
 namespace bpsw {
@@ -94,6 +98,8 @@ int make_scoring(const char* who, const bpsw_opt_t* opt, int xtra, int min_gap_e
 // the executor should be started with GPU_MAX_HW_QUEUES=20 in its environment (bench.py sets it before the
 // runtime initialises).  The library does not set it itself: setenv from a library constructor inside a multi-threaded JVM
 // races with every getenv of the process.  24 or more queues oversubscribe the hardware and throughput collapses.
+// Where the variable is not set (four queues, four pooled streams) the extension calls that wait for a stream ride one launch
+// chain (bpsw_ext_group.h), so the rate no longer hangs on it.
 
 // 1: single gap (deficit below two gap opens); 2: also a deficit of two gap opens (+1), for matrices with match score 1 and every
 // other entry <= -1 (flank_closed_form, "Two gap opens"); 3: also flank_start_gap_form
@@ -255,8 +261,7 @@ double wall_ms() {
 // ---- the per-device stream pool behind StreamLease (bpsw_internal.h) -------------------------------------------------
 namespace {
 struct StreamPool {
-  std::mutex mu;
-  std::condition_variable cv;
+  ExtGroupQueue q;  // its lock guards the two vectors; the callers that find every stream busy wait in it, oldest first
   std::vector<hipStream_t> streams;
   std::vector<int> pending;  // calls that have taken the stream and not finished waiting for their work
 };
@@ -317,43 +322,66 @@ CopyLane& copy_lane(int device) {
   return table[device >= 0 && device < 64 ? device : 0];
 }
 
-StreamLease::StreamLease(bpsw_ctx* c) : device(c->device), s(c->stream), pooled(false), wait_ms(0.) {
+// BPSW_EXT_GROUP_MAX (default 8, the descriptors a launch holds; 1: no grouping, every call a launch chain of its own as before)
+int ext_group_max() {
+  static const int n = [] {
+    const char* e = getenv("BPSW_EXT_GROUP_MAX");
+    const int v = e ? atoi(e) : EXT_GROUP_SLOTS;
+    return v < 1 ? 1 : (v > EXT_GROUP_SLOTS ? EXT_GROUP_SLOTS : v);
+  }();
+  return n;
+}
+int ext_group_waiting(int device) { return stream_pool(device).q.waiting_compatible(); }
+void ext_group_counts(int device, unsigned long long out[3]) { stream_pool(device).q.counts(out); }
+void ext_group_complete(int device, ExtGroupWaiter** members, int n_members, int status, float span_ms) {
+  stream_pool(device).q.complete(members, n_members, status, span_ms);
+}
+
+// a pooled stream for the caller, with the queue's lock held: an idle one, a new one while the pool may grow, or -- BPSW_STREAM_SHARE -- a
+// place behind the least loaded one
+static int pool_take(StreamPool& P, int cap) {
+  if (P.streams.capacity() < 64) { P.streams.reserve(64); P.pending.reserve(64); }  // (never moved: a holder reads its own entry without the lock)
+  int best = -1;
+  for (size_t k = 0; k < P.streams.size(); ++k)
+    if (best < 0 || P.pending[k] < P.pending[(size_t)best]) best = (int)k;
+  if (best >= 0 && P.pending[(size_t)best] == 0) { ++P.pending[(size_t)best]; return best; }  // an idle stream
+  if ((int)P.streams.size() < cap) {
+    hipStream_t ns = nullptr;
+    if (hipStreamCreateWithFlags(&ns, hipStreamNonBlocking) == hipSuccess) {
+      P.streams.push_back(ns);
+      P.pending.push_back(1);
+      return (int)P.streams.size() - 1;
+    }
+    if (best < 0) return ExtGroupQueue::OWN_SLOT;  // no pooled stream at all: the context's own stream for this call
+  }
+  if (best >= 0 && P.pending[(size_t)best] < stream_share()) { ++P.pending[(size_t)best]; return best; }  // queue behind the least loaded stream
+  return ExtGroupQueue::NO_SLOT;
+}
+
+StreamLease::StreamLease(bpsw_ctx* c, ExtGroupWaiter* w, ExtGroupWaiter** members, int* n_members)
+    : device(c->device), s(c->stream), pooled(false), wait_ms(0.) {
+  int none = 0;
+  if (n_members) *n_members = 0;
   const int cap = stream_pool_cap();
   if (cap == 0) return;
   StreamPool& P = stream_pool(device);
   const double t0 = wall_ms();
-  std::unique_lock<std::mutex> lk(P.mu);
-  for (;;) {
-    int best = -1;
-    for (size_t k = 0; k < P.streams.size(); ++k)
-      if (best < 0 || P.pending[k] < P.pending[(size_t)best]) best = (int)k;
-    if (best >= 0 && P.pending[(size_t)best] == 0) { slot = best; break; }  // an idle stream
-    if ((int)P.streams.size() < cap) {
-      hipStream_t ns = nullptr;
-      if (hipStreamCreateWithFlags(&ns, hipStreamNonBlocking) == hipSuccess) {
-        P.streams.push_back(ns);
-        P.pending.push_back(0);
-        slot = (int)P.streams.size() - 1;
-        break;
-      }
-      if (best < 0) { wait_ms = wall_ms() - t0; return; }  // no pooled stream at all: the context's own stream for this call
-    }
-    if (best >= 0 && P.pending[(size_t)best] < stream_share()) { slot = best; break; }  // queue behind the least loaded stream
-    P.cv.wait(lk);
-  }
-  ++P.pending[(size_t)slot];
-  s = P.streams[(size_t)slot];
-  pooled = true;
+  ExtGroupWaiter alone;  // (a caller that groups with nobody: the rescue launches, the extension calls outside the grouped plan)
+  if (!w) w = &alone;
+  ExtGroupWaiter* no_members[1];
+  const bool leads = P.q.acquire(*w, members ? ext_group_max() : 1, [&] { return pool_take(P, cap); }, members ? members : no_members, n_members ? n_members : &none);
   wait_ms = wall_ms() - t0;
+  if (!leads) { led = true; return; }  // another caller's launch chain has served this one: no stream to hold
+  if (w->slot < 0) return;
+  slot = w->slot;
+  s = P.streams[(size_t)slot];  // (without the lock: the entry was there when the slot was taken, and the vector is never moved)
+  pooled = true;
 }
 StreamLease::~StreamLease() {
   if (!pooled) return;
   StreamPool& P = stream_pool(device);
-  {
-    std::lock_guard<std::mutex> lk(P.mu);
-    --P.pending[(size_t)slot];
-  }
-  P.cv.notify_one();
+  const int cap = stream_pool_cap();
+  P.q.release([&] { --P.pending[(size_t)slot]; }, [&] { return pool_take(P, cap); });
 }
 
 }  // namespace bpsw
@@ -626,6 +654,16 @@ int bpsw_extend_batch_classify(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_b
   return extend_batch_impl(c, wire, wire_bytes, out, out_len, side_how);
 }
 
+// what a call in the pool's queue leaves for the caller that may lead it (ExtGroupWaiter::item): its descriptor, the copy of its batch
+// if that is still to be made, and -- back from the leader -- when the chain was enqueued (wall_ms)
+struct ExtCallItem {
+  ExtGroupMember gm;
+  void* copy_dst = nullptr;
+  const void* copy_src = nullptr;
+  size_t copy_bytes = 0;
+  double enqueued_at = 0.;
+};
+
 // wire == the context's pinned staging block (bpsw_extend_stage): the batch is already where the copy engine reads it, nothing is
 // copied in.  out_view: the caller takes the results where the kernel wrote them (the pinned result block), nothing is copied out.
 static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_bytes, int16_t* out, size_t out_len, uint8_t* side_how,
@@ -711,6 +749,9 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
   const double t_staged = stat_ms();
   double t_dev0, t_dev1, copy_first_ms = 0.;
   bool kernel_was_last = false, relaunched = false;
+  bool grouped = false;  // the call shared its launch chain (bpsw_ext_group.h): as the leader, or led
+  int group_n = 1;
+  float group_span_ms = 0.f;
   // The submission ring (bpsw_ring.h, class RING_CLASS_EXT): a SMALL batch -- no task for the full kernel, too few for the sift kernel to
   // pay, every flank within the resident kernel's fixed LDS geometry -- becomes one descriptor of the device's resident extension kernel:
   // one bulk copy on the copy lane, no stream, no launch, no event; its tasks are taken by the same wave population as every other
@@ -806,90 +847,187 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
       }
       copy_first_ms = stat_ms() - t_c0;  // (booked as the call's H2D time below)
     }
-    StreamLease lease(c);  // a device stream for the device phase only (bpsw_internal.h)
-    hipStream_t s = lease.s;
-    t_dev0 = stat_ms();
-    HIP_TRY(hipEventRecord(c->ev[0], s));
-    if (!copy_first) HIP_TRY(hipMemcpyAsync(c->d_wire.ptr, c->h_stage_in.ptr, stage_bytes, hipMemcpyHostToDevice, s));
-    bool on_dispatch = false;  // ev[1] / ev[2] ride on the kernel's own dispatch (KernelEvents, bpsw_internal.h)
     // results: written by the kernel straight into the pinned staging buffer (20 B per task, posted PCIe writes), or into
     // device memory and copied back
     const bool zc_out = (zerocopy_mask() & 1) != 0;
     int16_t* k_out = zc_out ? (int16_t*)c->h_stage_out.ptr : (int16_t*)c->d_out.ptr;
-    ExtScoring c_sc_full = c->ext_sc;  // what a late launch of the full kernel gets (lazy_full)
-    {
-      ExtScoring sc = c->ext_sc;
-      if (coord) { sc.pac = d_pac; sc.l_pac = l_pac; }
-      c_sc_full = sc;
-      if (side_how) {  // diagnostics: the kernel notes per side whether a shortcut or the DP produced the result
-        HIP_TRY(c->d_ext_lists.reserve(2 * (size_t)n + 16));
-        HIP_TRY(hipMemsetAsync(c->d_ext_lists.ptr, 0, 2 * (size_t)n, s));
-        sc.side_how = (uint8_t*)c->d_ext_lists.ptr;
-      }
-      on_dispatch = true;
-      int* d_queue = (int*)((char*)c->d_pre.ptr + 128);
-      int* d_list = use_short ? (int*)((char*)c->d_wire.ptr + list_off) : nullptr;
-      if (use_short) {
-        KernelEvents kev;
-        kev.start = c->ev[1]; kev.stop = (use_full && !lazy_full) ? nullptr : c->ev[2];
-        uint8_t* d_sflag = use_sift ? (uint8_t*)c->d_sift.ptr : nullptr;
-        uint4* d_srecs = use_sift ? (uint4*)((char*)c->d_sift.ptr + sift_rec_off) : nullptr;
-        int* d_todo = use_sift ? (int*)((char*)c->d_sift.ptr + todo_off) : nullptr;
-        // (should anything fail between the sift kernel, which fills the to-do counters d_queue[2..3], and the short kernel, whose last
-        // wave puts them back to zero, they are cleared here: the next call's sift kernel adds to what it finds)
-        struct TodoGuard {
-          int* q; hipStream_t s; bool armed;
-          ~TodoGuard() { if (armed) { (void)hipMemsetAsync(q, 0, 4 * sizeof(int), s); (void)hipStreamSynchronize(s); } }
-        } todo_guard{d_queue, s, false};
-        if (use_sift) {  // the kernel time of the call starts with it
-          KernelEvents sev;
-          sev.start = kev.start; kev.start = nullptr;
-          todo_guard.armed = true;
-          HIP_TRY(launch_ext_sift_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, sift_dm | (sift_uniform_dn(c->ext_mat, c->ext_sc.exact_a) << 16), 127, d_sflag, d_srecs, s, sev, nullptr,
-                                         d_queue + 2, d_todo, heavy_min));
-        }
-        HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, std::min(mq, 255), mr_short, c->num_cu, d_queue, nullptr, s,
-                                  nullptr, false, kev, true, d_list, 255, d_sflag, d_srecs, lazy_full ? (int*)(k_out + 10 * (size_t)n) : nullptr, d_todo));
-        todo_guard.armed = false;
-      }
-      if (use_full && !lazy_full) {
-        KernelEvents kev;
-        kev.start = use_short ? nullptr : c->ev[1]; kev.stop = c->ev[2];
-        // behind the short kernel: the list it completed on the device (what it may have deferred is unknown to the host
-        // -- a subset of the mid tasks, normally a small one: a quarter of them sizes the grid; an empty list costs a launch that
-        // returns at once)
-        // (a batch with few mid tasks -- 2x150 bp reads: the flanks of 128-131 bases -- defers next to nothing: one workgroup, whose
-        // four persistent waves take whatever the list holds, gets its wave slots sooner than a grid sized for a quarter of them, and
-        // the call holds its stream for that long)
-        // (this is the launch that is NOT late -- the classify entry, BPSW_EXT_LAZY_FULL=0, or tasks the host listed itself: a quarter of
-        // the mid tasks sizes it, at least one workgroup; the late launch below is sized by the posted length of the list)
-        const int grid_tasks = !use_short ? n : n_long + 4;  // (a wide band defers nothing since round 5: room for the unexpected only)
-        HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, grid_tasks, k_out, sc, mq, mr, c->num_cu, d_queue, nullptr, s,
-                                  nullptr, false, kev, false, use_short ? d_list : nullptr));
-      }
-      if (side_how) HIP_TRY(hipMemcpyAsync(side_how, c->d_ext_lists.ptr, 2 * (size_t)n, hipMemcpyDeviceToHost, s));
+    int* const d_queue_words = (int*)((char*)c->d_pre.ptr + 128);
+    // The calls that find every pooled stream busy wait in the pool's queue (bpsw_ext_group.h), and the ones whose plan is the common
+    // one -- a byte batch behind the sift kernel, the full kernel only if the short one posts a list, results written where the caller
+    // reads them -- ride ONE launch chain when a stream frees: the oldest of them leads, the others sleep until it hands them their
+    // status.  Everything else (coordinate batches, the classify entry, a batch with a listed long task or below the sift threshold)
+    // runs alone, as does every call with BPSW_EXT_GROUP_MAX=1 or that finds a free stream.
+    ExtCallItem me;
+    memset(&me.gm, 0, sizeof me.gm);
+    const bool groupable = &launch_ext_group != nullptr && ext_group_max() > 1 && !coord && use_sift && lazy_full && zc_out && !side_how;
+    if (groupable) {
+      ExtMember& m = me.gm.m;
+      m.wire = (const uint32_t*)c->d_wire.ptr; m.n_tasks = n; m.out = k_out; m.sc = c->ext_sc; m.queue = d_queue_words;
+      m.defer = (int*)((char*)c->d_wire.ptr + list_off); m.defer_post = (int*)(k_out + 10 * (size_t)n); m.short_qmax = 255;
+      m.sift_flag = (uint8_t*)c->d_sift.ptr; m.sift_recs = (uint4*)((char*)c->d_sift.ptr + sift_rec_off);
+      m.todo_count = d_queue_words + 2; m.todo_list = (int*)((char*)c->d_sift.ptr + todo_off);
+      m.sift_dm = sift_dm; m.sift_dn = sift_uniform_dn(c->ext_mat, c->ext_sc.exact_a); m.sift_qmax = 127; m.heavy_min = heavy_min;
+      me.gm.qcap = std::min(mq, 255); me.gm.rcap = mr_short;
+      if (!copy_first) { me.copy_dst = c->d_wire.ptr; me.copy_src = c->h_stage_in.ptr; me.copy_bytes = stage_bytes; }
     }
-    if (!on_dispatch) HIP_TRY(hipEventRecord(c->ev[2], s));
-    const bool kernel_is_last = on_dispatch && zc_out && !side_how;  // then the call waits for the kernel's own stop event
-    kernel_was_last = kernel_is_last;
-    if (!zc_out) HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, c->d_out.ptr, out_post_bytes, hipMemcpyDeviceToHost, s));
-    if (!kernel_is_last) HIP_TRY(hipEventRecord(c->ev[3], s));
-    HIP_TRY(wait_event(c, kernel_is_last ? c->ev[2] : c->ev[3], 0));  // the last operation of the call on this stream
-    if (lazy_full && *(volatile int*)((char*)c->h_stage_out.ptr + out_bytes) > 0) {  // the short kernel left a list: the full kernel, now
+    ExtGroupWaiter gw;
+    gw.compatible = groupable;
+    gw.item = &me;
+    ExtGroupWaiter* led[EXT_GROUP_SLOTS];
+    int n_led = 0;
+    const double t_ready = stat_ms();
+    StreamLease lease(c, &gw, groupable ? led : nullptr, groupable ? &n_led : nullptr);  // a device stream for the device phase only (bpsw_internal.h)
+    hipStream_t s = lease.s;
+    t_dev0 = stat_ms();
+    // (the full kernel over what the short one listed: the call's own duty, in a lease of its own, also where a group served the call)
+    const auto late_full = [&](hipStream_t ls) -> int {
       // (events of its own: the call's kernel time is the first launches' span plus this one's, not the host's round trip in between)
       KernelEvents kev;
       kev.start = c->ev[4]; kev.stop = c->ev[5];
       relaunched = true;
+      ExtScoring sc_full = c->ext_sc;
+      if (coord) { sc_full.pac = d_pac; sc_full.l_pac = l_pac; }
       const int listed = *(volatile int*)((char*)c->h_stage_out.ptr + out_bytes);
-      HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, listed, k_out, c_sc_full, mq, mr, c->num_cu, (int*)((char*)c->d_pre.ptr + 128), nullptr, s,
+      HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, listed, k_out, sc_full, mq, mr, c->num_cu, d_queue_words, nullptr, ls,
                                 nullptr, false, kev, false, (int*)((char*)c->d_wire.ptr + list_off)));
-      if (!zc_out) HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, c->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, s));
-      if (!kernel_is_last) HIP_TRY(hipEventRecord(c->ev[3], s));
-      HIP_TRY(wait_event(c, kernel_is_last ? c->ev[5] : c->ev[3], 0));
+      if (!zc_out) HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, c->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, ls));
+      if (!zc_out || side_how) HIP_TRY(hipEventRecord(c->ev[3], ls));
+      HIP_TRY(wait_event(c, (!zc_out || side_how) ? c->ev[3] : c->ev[5], 0));
       c->stats.ext_full_relaunches++;
+      return BPSW_OK;
+    };
+    if (lease.led || n_led > 0) {
+      // ---- a group: this call was served by another's launch chain, or leads the waiters in led[] ----
+      grouped = true;
+      kernel_was_last = true;
+      if (lease.led) {
+        group_n = gw.group_n; group_span_ms = gw.span_ms;
+        const double now = stat_ms();
+        // ready until enqueued / enqueued until woken, on the leader's stamp (wall clock) of its enqueue
+        const double since_enq = std::max(0., wall_ms() - me.enqueued_at);
+        t_dev0 = std::max(t_ready, now - since_enq);
+        c->stats.ext_wait_ms += t_dev0 - t_ready;
+        if (gw.status != (int)hipSuccess) {
+          // the group's launch failed somewhere between its sift kernel, which fills this context's to-do counters, and its short
+          // kernel, whose last wave puts them back: cleared here, the next call's sift kernel adds to what it finds
+          (void)hipMemsetAsync(d_queue_words, 0, 4 * sizeof(int), c->stream);
+          (void)hipStreamSynchronize(c->stream);
+          return hip_fail((hipError_t)gw.status, "extend: the launch chain this call shared with others");
+        }
+      } else {
+        const int k = 1 + n_led;
+        group_n = k;
+        struct GroupDone {  // whatever happens on the way, nobody is left sleeping
+          int dev; ExtGroupWaiter** m; int n; int status; float span; int* q; hipStream_t s; bool clear;
+          ~GroupDone() {
+            if (clear) { (void)hipMemsetAsync(q, 0, 4 * sizeof(int), s); (void)hipStreamSynchronize(s); }
+            if (n) ext_group_complete(dev, m, n, status, span);
+          }
+        } done{c->device, led, n_led, (int)hipErrorUnknown, 0.f, d_queue_words, s, true};
+        ExtGroupMember gms[EXT_GROUP_SLOTS];
+        gms[0] = me.gm;
+        HIP_TRY(hipEventRecord(c->ev[0], s));
+        if (me.copy_bytes) HIP_TRY(hipMemcpyAsync(me.copy_dst, me.copy_src, me.copy_bytes, hipMemcpyHostToDevice, s));
+        for (int i = 0; i < n_led; ++i) {
+          ExtCallItem* it = (ExtCallItem*)led[i]->item;
+          gms[1 + i] = it->gm;
+          if (it->copy_bytes) HIP_TRY(hipMemcpyAsync(it->copy_dst, it->copy_src, it->copy_bytes, hipMemcpyHostToDevice, s));
+        }
+        KernelEvents kev;
+        kev.start = c->ev[1]; kev.stop = c->ev[2];
+        hipError_t ge = launch_ext_group(gms, k, c->num_cu, s, kev);
+        const double enq = wall_ms();
+        for (int i = 0; i < n_led; ++i) ((ExtCallItem*)led[i]->item)->enqueued_at = enq;
+        if (ge == hipSuccess) ge = wait_event(c, c->ev[2], 3);  // (an estimate of its own: a group's chain runs longer than a lone call's)
+        done.status = (int)ge;
+        if (ge != hipSuccess) return hip_fail(ge, "extend: launch chain of a group");
+        done.clear = false;
+        float span = 0.f;
+        (void)hipEventElapsedTime(&span, c->ev[1], c->ev[2]);
+        group_span_ms = done.span = span;
+        c->stats.ext_wait_ms += lease.wait_ms;
+      }
     }
-    t_dev1 = stat_ms();
-    c->stats.ext_wait_ms += lease.wait_ms;
+    if (grouped) {
+      if (*(volatile int*)((char*)c->h_stage_out.ptr + out_bytes) > 0) {
+        if (lease.led) {
+          StreamLease late(c);
+          const int lrc = late_full(late.s);
+          if (lrc != BPSW_OK) return lrc;
+        } else {
+          const int lrc = late_full(s);
+          if (lrc != BPSW_OK) return lrc;
+        }
+      }
+      t_dev1 = stat_ms();
+    } else {
+      HIP_TRY(hipEventRecord(c->ev[0], s));
+      if (!copy_first) HIP_TRY(hipMemcpyAsync(c->d_wire.ptr, c->h_stage_in.ptr, stage_bytes, hipMemcpyHostToDevice, s));
+      bool on_dispatch = false;  // ev[1] / ev[2] ride on the kernel's own dispatch (KernelEvents, bpsw_internal.h)
+      {
+        ExtScoring sc = c->ext_sc;
+        if (coord) { sc.pac = d_pac; sc.l_pac = l_pac; }
+        if (side_how) {  // diagnostics: the kernel notes per side whether a shortcut or the DP produced the result
+          HIP_TRY(c->d_ext_lists.reserve(2 * (size_t)n + 16));
+          HIP_TRY(hipMemsetAsync(c->d_ext_lists.ptr, 0, 2 * (size_t)n, s));
+          sc.side_how = (uint8_t*)c->d_ext_lists.ptr;
+        }
+        on_dispatch = true;
+        int* d_queue = (int*)((char*)c->d_pre.ptr + 128);
+        int* d_list = use_short ? (int*)((char*)c->d_wire.ptr + list_off) : nullptr;
+        if (use_short) {
+          KernelEvents kev;
+          kev.start = c->ev[1]; kev.stop = (use_full && !lazy_full) ? nullptr : c->ev[2];
+          uint8_t* d_sflag = use_sift ? (uint8_t*)c->d_sift.ptr : nullptr;
+          uint4* d_srecs = use_sift ? (uint4*)((char*)c->d_sift.ptr + sift_rec_off) : nullptr;
+          int* d_todo = use_sift ? (int*)((char*)c->d_sift.ptr + todo_off) : nullptr;
+          // (should anything fail between the sift kernel, which fills the to-do counters d_queue[2..3], and the short kernel, whose last
+          // wave puts them back to zero, they are cleared here: the next call's sift kernel adds to what it finds)
+          struct TodoGuard {
+            int* q; hipStream_t s; bool armed;
+            ~TodoGuard() { if (armed) { (void)hipMemsetAsync(q, 0, 4 * sizeof(int), s); (void)hipStreamSynchronize(s); } }
+          } todo_guard{d_queue, s, false};
+          if (use_sift) {  // the kernel time of the call starts with it
+            KernelEvents sev;
+            sev.start = kev.start; kev.start = nullptr;
+            todo_guard.armed = true;
+            HIP_TRY(launch_ext_sift_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, sift_dm | (sift_uniform_dn(c->ext_mat, c->ext_sc.exact_a) << 16), 127, d_sflag, d_srecs, s, sev, nullptr,
+                                           d_queue + 2, d_todo, heavy_min));
+          }
+          HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, n, k_out, sc, std::min(mq, 255), mr_short, c->num_cu, d_queue, nullptr, s,
+                                    nullptr, false, kev, true, d_list, 255, d_sflag, d_srecs, lazy_full ? (int*)(k_out + 10 * (size_t)n) : nullptr, d_todo));
+          todo_guard.armed = false;
+        }
+        if (use_full && !lazy_full) {
+          KernelEvents kev;
+          kev.start = use_short ? nullptr : c->ev[1]; kev.stop = c->ev[2];
+          // behind the short kernel: the list it completed on the device (what it may have deferred is unknown to the host
+          // -- a subset of the mid tasks, normally a small one: a quarter of them sizes the grid; an empty list costs a launch that
+          // returns at once)
+          // (a batch with few mid tasks -- 2x150 bp reads: the flanks of 128-131 bases -- defers next to nothing: one workgroup, whose
+          // four persistent waves take whatever the list holds, gets its wave slots sooner than a grid sized for a quarter of them, and
+          // the call holds its stream for that long)
+          // (this is the launch that is NOT late -- the classify entry, BPSW_EXT_LAZY_FULL=0, or tasks the host listed itself: a quarter of
+          // the mid tasks sizes it, at least one workgroup; the late launch below is sized by the posted length of the list)
+          const int grid_tasks = !use_short ? n : n_long + 4;  // (a wide band defers nothing since round 5: room for the unexpected only)
+          HIP_TRY(launch_ext_kernel((const uint32_t*)c->d_wire.ptr, grid_tasks, k_out, sc, mq, mr, c->num_cu, d_queue, nullptr, s,
+                                    nullptr, false, kev, false, use_short ? d_list : nullptr));
+        }
+        if (side_how) HIP_TRY(hipMemcpyAsync(side_how, c->d_ext_lists.ptr, 2 * (size_t)n, hipMemcpyDeviceToHost, s));
+      }
+      if (!on_dispatch) HIP_TRY(hipEventRecord(c->ev[2], s));
+      const bool kernel_is_last = on_dispatch && zc_out && !side_how;  // then the call waits for the kernel's own stop event
+      kernel_was_last = kernel_is_last;
+      if (!zc_out) HIP_TRY(hipMemcpyAsync(c->h_stage_out.ptr, c->d_out.ptr, out_post_bytes, hipMemcpyDeviceToHost, s));
+      if (!kernel_is_last) HIP_TRY(hipEventRecord(c->ev[3], s));
+      HIP_TRY(wait_event(c, kernel_is_last ? c->ev[2] : c->ev[3], 0));  // the last operation of the call on this stream
+      if (lazy_full && *(volatile int*)((char*)c->h_stage_out.ptr + out_bytes) > 0) {  // the short kernel left a list: the full kernel, now
+        const int lrc = late_full(s);
+        if (lrc != BPSW_OK) return lrc;
+      }
+      t_dev1 = stat_ms();
+      c->stats.ext_wait_ms += lease.wait_ms;
+    }
   }
   if (out_view) {
     *out_view = (const int16_t*)c->h_stage_out.ptr;  // valid until the next call on this context
@@ -902,8 +1040,12 @@ static int extend_batch_impl(bpsw_ctx_t* c, const uint8_t* wire, size_t wire_byt
     b = ring_kernel_ms;  // first task taken -> last task finished, on the device's clock
     t_dev0 += copy_first_ms;  // (booked once below, with the copy)
   } else {
-    (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
+    if (!grouped) {
+      (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
+      (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
+    } else {
+      b = group_span_ms / (float)group_n;  // the group's kernel span, shared out
+    }
     if (relaunched) { float b2 = 0; (void)hipEventElapsedTime(&b2, c->ev[4], c->ev[5]); b += b2; }
     if (!kernel_was_last) (void)hipEventElapsedTime(&d, relaunched ? c->ev[5] : c->ev[2], c->ev[3]);
   }
@@ -1023,6 +1165,15 @@ int bpsw_extend_batch_device(bpsw_ctx_t* c, const void* d_wire, size_t wire_byte
     c->pend_ext.d_out = d_out; c->pend_ext.s = s;
     return BPSW_OK;
   }
+}
+
+int bpsw_ext_group_waiting(int device) { return device >= 0 && device < 64 ? bpsw::ext_group_waiting(device) : -1; }
+int bpsw_ext_group_counts(int device, uint64_t out[3]) {
+  if (!out || device < 0 || device >= 64) return fail(BPSW_ERR_ARG, "ext_group_counts: bad argument");
+  unsigned long long v[3];
+  bpsw::ext_group_counts(device, v);
+  for (int i = 0; i < 3; ++i) out[i] = (uint64_t)v[i];
+  return BPSW_OK;
 }
 
 int bpsw_get_stats(bpsw_ctx_t* c, bpsw_stats_t* out) {

@@ -762,6 +762,15 @@ int bpsw_ring_integrity(uint64_t *checked, uint64_t *faults);
  * (BPSW_RING_LONE_LAUNCH).  Diagnostics (an executor's metrics page; tests/test_ring_gpu.py waits on it to make
  * "a batch that has company" a deterministic state instead of a matter of thread timing).  -1 for a device index outside 0..63. */
 int bpsw_sw_batches_in_flight(int device);
+/* The extension calls that wait for a stream ride one launch chain (csrc/bpsw_ext_group.h; BPSW_EXT_GROUP_MAX).
+ * A gauge: the extension calls of the grouped plan (a byte batch behind the sift kernel, results read where the kernel wrote them) that are
+ * waiting for a pooled stream of `device` right now; calls that run alone (coordinate batches, the classify entry, rescue launches) wait in the
+ * same queue and are not counted.  Diagnostics (tests/test_ext_group_gpu.py waits on it to make "k calls behind one stream" a state instead of a matter of
+ * thread timing).  -1 for a device index outside 0..63. */
+int bpsw_ext_group_waiting(int device);
+/* out[0] = launch chains of the grouped plan so far on `device` (a call that found a free stream is a group of one), out[1] = their members
+ * summed, out[2] = the largest group.  Process-wide, never reset. */
+int bpsw_ext_group_counts(int device, uint64_t out[3]);
 
 #ifdef __cplusplus
 }
