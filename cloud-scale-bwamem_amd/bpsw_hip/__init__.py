@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "bpsw_sam_se_batch", "bpsw_align_se_batch", "bpsw_last_sam_se_times",
     "bpsw_sam_pe_batch_ex", "bpsw_align_pe_batch", "bpsw_last_sam_pe_times",
     "bpsw_fastq_parse", "bpsw_align_fastq_se", "bpsw_align_fastq_pe", "bpsw_last_fastq_times",
+    "bpsw_bam_se_batch", "bpsw_bam_pe_batch", "bpsw_align_bam_se_batch", "bpsw_align_bam_pe_batch", "bpsw_align_fastq_bam_se", "bpsw_align_fastq_bam_pe",
+    "bpsw_sam_header", "bpsw_bam_header", "bpsw_bam_eof", "bpsw_bam_set_block_payload", "bpsw_last_bam_times",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -283,6 +285,28 @@ def _bind_seeding(lib):
                                  C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p], C.c_int),
         "bpsw_last_fastq_times": ([C.c_void_p], None),
+        # alignments out as BAM (bpsw_bam.hip): the twins of the entries above, without out_off (and max_reads)
+        "bpsw_bam_se_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                               C.c_void_p], C.c_int),
+        "bpsw_bam_pe_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                               C.c_void_p], C.c_int),
+        "bpsw_align_bam_se_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+        "bpsw_align_bam_pe_batch": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p], C.c_int),
+        "bpsw_align_fastq_bam_se": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int64, C.c_int32,
+                                     C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.c_void_p],
+                                    C.c_int),
+        "bpsw_align_fastq_bam_pe": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,
+                                     C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                     C.c_void_p, C.POINTER(C.c_int64), C.c_void_p], C.c_int),
+        "bpsw_sam_header": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+                            C.c_int),
+        "bpsw_bam_header": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+                            C.c_int),
+        "bpsw_bam_eof": ([C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+        "bpsw_bam_set_block_payload": ([C.c_int], C.c_int),
+        "bpsw_last_bam_times": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -1250,6 +1274,130 @@ def last_fastq_times():
     return tuple(ms)
 
 
+# ---- alignments out as BAM (bpsw_bam.hip) -------------------------------------------------------------------------------------------
+BGZF_PAYLOAD = 65280   # the payload bytes of a BGZF block unless bam_set_block_payload says otherwise
+
+
+def _bytes_call(lib, what, call, cap=None, start=1 << 16):
+    """the capacity protocol of the entries that hand out one block of bytes: call(buf, cap, need) until it fits -> bytes.  A cap is
+    tried once."""
+    need = C.c_size_t(0)
+    size = start if cap is None else int(cap)
+    while True:
+        buf = np.empty(max(size, 1), np.uint8)
+        rc = call(_ptr(buf), size, C.byref(need))
+        if rc == -3 and cap is None and need.value > size:   # BPSW_ERR_CAPACITY
+            size = int(need.value)
+            continue
+        _chk(lib, rc, what)
+        return buf[: int(need.value)].tobytes()
+
+
+def _ctx_bam_se_batch(self, opt: Opt, topt: "TailOpt", g: "SeReadsSoA", flags: int = 0, cap: int | None = None):
+    """sam_se_batch's lines as BAM records in BGZF blocks -> (bytes, the region lists after mark-primary)"""
+    st, keep, n_regs = _se_struct(g, True)
+    out_regs = np.zeros(max(n_regs, 1), ALNREG_DTYPE)
+    out = _bytes_call(self.lib, "bpsw_bam_se_batch",
+                      lambda buf, size, need: self.lib.bpsw_bam_se_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, buf, size, need,
+                                                                         _ptr(out_regs)), cap, 512 * max(1, g.n_reads))
+    return out, out_regs[:n_regs]
+
+
+def _ctx_bam_pe_batch(self, opt: Opt, topt: "TailOpt", g: "TailGroupSoA", flags: int = 0, cap: int | None = None):
+    """sam_pe_batch's lines as BAM records in BGZF blocks -> (bytes, regions as the tail leaves them)"""
+    st, keep, regs = _pairs_struct(g)
+    out_regs = np.zeros(max(regs.shape[0], 1), ALNREG_DTYPE)
+    out = _bytes_call(self.lib, "bpsw_bam_pe_batch",
+                      lambda buf, size, need: self.lib.bpsw_bam_pe_batch(self.h, C.byref(opt), C.byref(topt), C.byref(st), flags, buf, size, need,
+                                                                         _ptr(out_regs)), cap, 1024 * max(1, g.group_size))
+    return out, out_regs[: regs.shape[0]]
+
+
+def _ctx_align_bam_se_batch(self, opt: Opt, sopt, topt: "TailOpt", g: "SeReadsSoA", zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0,
+                            flags: int = 0, cap: int | None = None):
+    """reads -> BAM records in BGZF blocks (bytes): align_se_batch with the other writer"""
+    st, keep, _ = _se_struct(g, False)
+    return _bytes_call(self.lib, "bpsw_align_bam_se_batch",
+                       lambda buf, size, need: self.lib.bpsw_align_bam_se_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
+                                                                                zdrop_mode, w1_flags, flags, buf, size, need), cap)
+
+
+def _ctx_align_bam_pe_batch(self, opt: Opt, sopt, topt: "TailOpt", g: "TailGroupSoA", pes0=None, zdrop_mode: int = ZDROP_SCALA,
+                            w1_flags: int = 0, rescue_mode: int = RESCUE_C, flags: int = 0, cap: int | None = None):
+    """paired reads -> (BAM records in BGZF blocks (bytes), the insert-size statistics used): align_pe_batch with the other writer"""
+    st, keep, _ = _pairs_struct(g, False)
+    pes_in = None if pes0 is None else _pes_struct(pes0)
+    pes = (PeStat * 4)()
+    out = _bytes_call(self.lib, "bpsw_align_bam_pe_batch",
+                      lambda buf, size, need: self.lib.bpsw_align_bam_pe_batch(self.h, C.byref(opt), C.byref(sopt), C.byref(topt), C.byref(st),
+                                                                               pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, size, need,
+                                                                               pes), cap)
+    return out, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)]
+
+
+def _ctx_align_fastq_bam_se(self, opt: Opt, sopt, topt: "TailOpt", text: bytes, fastq_flags: int = FASTQ_FINAL, id0: int = 0, id_step: int = 1,
+                            zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0, flags: int = 0, cap: int | None = None):
+    """FASTQ text -> (BAM records in BGZF blocks (bytes), reads parsed, bytes of the text consumed)"""
+    consumed, n = np.zeros(2, np.int64), C.c_int64(0)
+    out = _bytes_call(self.lib, "bpsw_align_fastq_bam_se",
+                      lambda buf, size, need: self.lib.bpsw_align_fastq_bam_se(
+                          self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text, len(text), int(fastq_flags), int(id0), int(id_step), zdrop_mode,
+                          w1_flags, flags, buf, size, need, C.byref(n), _ptr(consumed)), cap)
+    return out, int(n.value), int(consumed[0])
+
+
+def _ctx_align_fastq_bam_pe(self, opt: Opt, sopt, topt: "TailOpt", text1: bytes, text2: bytes | None = None, fastq_flags: int = FASTQ_FINAL,
+                            id0: int = 0, pes0=None, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0, rescue_mode: int = RESCUE_C,
+                            flags: int = 0, cap: int | None = None):
+    """FASTQ texts of pairs -> (BAM records in BGZF blocks (bytes), the statistics used, reads parsed, bytes consumed of each text)"""
+    consumed, n = np.zeros(2, np.int64), C.c_int64(0)
+    pes_in = None if pes0 is None else _pes_struct(pes0)
+    pes = (PeStat * 4)()
+    out = _bytes_call(self.lib, "bpsw_align_fastq_bam_pe",
+                      lambda buf, size, need: self.lib.bpsw_align_fastq_bam_pe(
+                          self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text1, len(text1), text2, len(text2 or b""), int(fastq_flags),
+                          int(id0), pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, size, need, pes, C.byref(n), _ptr(consumed)), cap)
+    return (out, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)],
+            int(n.value), (int(consumed[0]), int(consumed[1])))
+
+
+def _header_call(entry: str, ctx, lens, names, extra: bytes, cap):
+    lib = load_library() if ctx is None else ctx.lib
+    ln = None if lens is None else np.ascontiguousarray(lens, np.int32)
+    blob = None if names is None else b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
+    fn = getattr(lib, entry)
+    return _bytes_call(lib, entry, lambda buf, size, need: fn(None if ctx is None else ctx.h, 0 if ln is None else int(ln.shape[0]), _ptr(ln), blob,
+                                                             extra or None, len(extra or b""), buf, size, need), cap, 4096)
+
+
+def sam_header(lens=None, names=None, extra: bytes = b"", ctx: "Context | None" = None, cap: int | None = None) -> bytes:
+    """bpsw_sam_header: @HD, an @SQ per contig -- of the table loaded on ctx, or of lens / names without one -- then `extra` verbatim"""
+    return _header_call("bpsw_sam_header", ctx, lens, names, extra, cap)
+
+
+def bam_header(lens=None, names=None, extra: bytes = b"", ctx: "Context | None" = None, cap: int | None = None) -> bytes:
+    """bpsw_bam_header: BAM\\1, that text and the reference list, in BGZF blocks"""
+    return _header_call("bpsw_bam_header", ctx, lens, names, extra, cap)
+
+
+def bam_eof(cap: int | None = None) -> bytes:
+    """bpsw_bam_eof: the 28-byte end-of-file block"""
+    lib = load_library()
+    return _bytes_call(lib, "bpsw_bam_eof", lambda buf, size, need: lib.bpsw_bam_eof(buf, size, need), cap, 28)
+
+
+def bam_set_block_payload(n: int) -> int:
+    """bpsw_bam_set_block_payload: 1 .. 65280, 0 for the default; -> the library's return code (a refusal changes nothing)"""
+    return int(load_library().bpsw_bam_set_block_payload(int(n)))
+
+
+def last_bam_times():
+    """(bam_len_kernel, bam_write_kernel, bgzf_frame_kernel, line table, round trip) in ms of this thread's last BAM entry"""
+    ms = (C.c_double * 5)()
+    load_library().bpsw_last_bam_times(ms)
+    return tuple(ms)
+
+
 TAIL_POOL_TAIL_ONLY = -1
 
 
@@ -1336,6 +1484,15 @@ Context.align_pe_batch = _ctx_align_pe_batch
 Context.fastq_parse = lambda self, text1, text2=None, flags=0, **kw: fastq_parse(text1, text2, flags, ctx=self, **kw)
 Context.align_fastq_se = _ctx_align_fastq_se
 Context.align_fastq_pe = _ctx_align_fastq_pe
+Context.bam_se_batch = _ctx_bam_se_batch
+Context.bam_pe_batch = _ctx_bam_pe_batch
+Context.align_bam_se_batch = _ctx_align_bam_se_batch
+Context.align_bam_pe_batch = _ctx_align_bam_pe_batch
+Context.align_fastq_bam_se = _ctx_align_fastq_bam_se
+Context.align_fastq_bam_pe = _ctx_align_fastq_bam_pe
+Context.sam_header = lambda self, extra=b"", cap=None: sam_header(extra=extra, ctx=self, cap=cap)
+Context.bam_header = lambda self, extra=b"", cap=None: bam_header(extra=extra, ctx=self, cap=cap)
+Context.bam_eof = lambda self: bam_eof()
 Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute units of the context's device
 
 

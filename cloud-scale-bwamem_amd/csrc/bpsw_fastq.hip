@@ -1,5 +1,6 @@
 // bpsw_fastq.hip -- four-line FASTQ text to the library's read pools on the device: bpsw_fastq_parse, and the two entries that go from
-// FASTQ text to SAM text in one call, bpsw_align_fastq_se and bpsw_align_fastq_pe.
+// FASTQ text to SAM text in one call, bpsw_align_fastq_se and bpsw_align_fastq_pe, with their twins that end in BAM
+// (bpsw_align_fastq_bam_se / _pe: the same two bodies, fastq_se and fastq_pe, ending in bpsw_bam.hip's align entries).
 //
 // The record rules are bpsw_fastq_core.h's; this file is who applies them.  With BPSW_FASTQ_HOST that is parse_serial of the same
 // header on the calling thread (nothing is launched, no device is needed).  Otherwise the text goes to the device in one staged block
@@ -392,6 +393,69 @@ struct Parsed {
   }
 };
 
+// the bodies of the align entries: the parse, then the align entry of the form asked for (bam: the BAM twin, which has no out_off)
+int fastq_se(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
+             size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out_text, size_t text_cap,
+             int64_t* out_off, int64_t max_reads, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
+  const std::string w(who);
+  if (!c || !opt || !sopt || !topt || (!bam && !out_off) || !n_reads || !consumed || max_reads < 0) return fail(BPSW_ERR_ARG, w + ": null argument");
+  if (fastq_flags & (BPSW_FASTQ_INTERLEAVED | BPSW_FASTQ_PAIR_NAMES)) return fail(BPSW_ERR_ARG, w + ": a pair flag in a single-end call");
+  Caller A;
+  int rc = check_texts(who, text, bytes, nullptr, 0, fastq_flags, &A);
+  if (rc != BPSW_OK) return rc;
+  thread_local Parsed P;  // (grown, never shrunk: fresh pools of a 30 MB chunk cost the call more than its parse)
+  fq::Result res;
+  int how = fq::PARSE_OK;
+  *n_reads = 0; *consumed = 0;
+  rc = parse_any(c, A, P, &res, &how);
+  if (rc != BPSW_OK) return rc;
+  *n_reads = res.n_reads;
+  if (!bam && res.n_reads > max_reads) return fail(BPSW_ERR_CAPACITY, w + ": out_off has room for fewer reads than the text holds (*n_reads)");
+  if (res.n_reads > 0x7fffffffll) return fail(BPSW_ERR_LIMIT, w + ": more than 2^31 - 1 reads");
+  bpsw_se_reads_t g;
+  memset(&g, 0, sizeof g);
+  g.n_reads = (int32_t)res.n_reads; g.id0 = id0; g.id_step = id_step;
+  g.read_len = P.read_len.data(); g.read_off = P.read_off.data(); g.read_pool = P.read_pool.data(); g.qual_pool = P.qual_pool.data();
+  g.read_pool_bytes = (size_t)res.needed[1];
+  g.name_off = P.name_off.data(); g.name_pool = P.name_pool.data();
+  rc = bam ? bpsw_align_bam_se_batch(c, opt, sopt, topt, &g, zdrop_mode, w1_flags, flags, out_text, text_cap, out_needed)
+           : bpsw_align_se_batch(c, opt, sopt, topt, &g, zdrop_mode, w1_flags, flags, out_text, text_cap, out_off, out_needed);
+  if (rc == BPSW_OK || rc == BPSW_ERR_CAPACITY) *consumed = res.consumed[0];
+  return rc;
+}
+
+int fastq_pe(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text1,
+             size_t bytes1, const char* text2, size_t bytes2, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags,
+             int rescue_mode, int flags, char* out_text, size_t text_cap, int64_t* out_off, int64_t max_reads, size_t* out_needed,
+             bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
+  const std::string w(who);
+  if (!c || !opt || !sopt || !topt || (!bam && !out_off) || !n_reads || !consumed || max_reads < 0) return fail(BPSW_ERR_ARG, w + ": null argument");
+  if (!text2 && !(fastq_flags & BPSW_FASTQ_INTERLEAVED)) return fail(BPSW_ERR_ARG, w + ": one text without BPSW_FASTQ_INTERLEAVED");
+  if (!text2) fastq_flags |= BPSW_FASTQ_PAIR_NAMES;
+  Caller A;
+  int rc = check_texts(who, text1, bytes1, text2, bytes2, fastq_flags, &A);
+  if (rc != BPSW_OK) return rc;
+  thread_local Parsed P;
+  fq::Result res;
+  int how = fq::PARSE_OK;
+  *n_reads = 0; consumed[0] = consumed[1] = 0;
+  rc = parse_any(c, A, P, &res, &how);
+  if (rc != BPSW_OK) return rc;
+  *n_reads = res.n_reads;
+  if (!bam && res.n_reads > max_reads) return fail(BPSW_ERR_CAPACITY, w + ": out_off has room for fewer reads than the texts hold (*n_reads)");
+  if (res.n_reads / 2 > 0x7fffffffll) return fail(BPSW_ERR_LIMIT, w + ": more than 2^31 - 1 pairs");
+  bpsw_pairs_t g;
+  memset(&g, 0, sizeof g);
+  g.group_size = (int32_t)(res.n_reads / 2); g.id0 = id0;
+  g.read_len = P.read_len.data(); g.read_off = P.read_off.data(); g.read_pool = P.read_pool.data(); g.qual_pool = P.qual_pool.data();
+  g.read_pool_bytes = (size_t)res.needed[1];
+  g.name_off = P.name_off.data(); g.name_pool = P.name_pool.data();
+  rc = bam ? bpsw_align_bam_pe_batch(c, opt, sopt, topt, &g, pes0, zdrop_mode, w1_flags, rescue_mode, flags, out_text, text_cap, out_needed, out_pes)
+           : bpsw_align_pe_batch(c, opt, sopt, topt, &g, pes0, zdrop_mode, w1_flags, rescue_mode, flags, out_text, text_cap, out_off, out_needed, out_pes);
+  if (rc == BPSW_OK || rc == BPSW_ERR_CAPACITY) { consumed[0] = res.consumed[0]; consumed[1] = res.consumed[1]; }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -430,59 +494,32 @@ int bpsw_fastq_parse(bpsw_ctx_t* c, const char* text1, size_t bytes1, const char
 int bpsw_align_fastq_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
                         size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out_text,
                         size_t text_cap, int64_t* out_off, int64_t max_reads, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
-  if (!c || !opt || !sopt || !topt || !out_off || !n_reads || !consumed || max_reads < 0) return fail(BPSW_ERR_ARG, "align_fastq_se: null argument");
-  if (fastq_flags & (BPSW_FASTQ_INTERLEAVED | BPSW_FASTQ_PAIR_NAMES)) return fail(BPSW_ERR_ARG, "align_fastq_se: a pair flag in a single-end call");
-  Caller A;
-  int rc = check_texts("align_fastq_se", text, bytes, nullptr, 0, fastq_flags, &A);
-  if (rc != BPSW_OK) return rc;
-  thread_local Parsed P;  // (grown, never shrunk: fresh pools of a 30 MB chunk cost the call more than its parse)
-  fq::Result res;
-  int how = fq::PARSE_OK;
-  *n_reads = 0; *consumed = 0;
-  rc = parse_any(c, A, P, &res, &how);
-  if (rc != BPSW_OK) return rc;
-  *n_reads = res.n_reads;
-  if (res.n_reads > max_reads) return fail(BPSW_ERR_CAPACITY, "align_fastq_se: out_off has room for fewer reads than the text holds (*n_reads)");
-  if (res.n_reads > 0x7fffffffll) return fail(BPSW_ERR_LIMIT, "align_fastq_se: more than 2^31 - 1 reads");
-  bpsw_se_reads_t g;
-  memset(&g, 0, sizeof g);
-  g.n_reads = (int32_t)res.n_reads; g.id0 = id0; g.id_step = id_step;
-  g.read_len = P.read_len.data(); g.read_off = P.read_off.data(); g.read_pool = P.read_pool.data(); g.qual_pool = P.qual_pool.data();
-  g.read_pool_bytes = (size_t)res.needed[1];
-  g.name_off = P.name_off.data(); g.name_pool = P.name_pool.data();
-  rc = bpsw_align_se_batch(c, opt, sopt, topt, &g, zdrop_mode, w1_flags, flags, out_text, text_cap, out_off, out_needed);
-  if (rc == BPSW_OK || rc == BPSW_ERR_CAPACITY) *consumed = res.consumed[0];
-  return rc;
+  return fastq_se("align_fastq_se", false, c, opt, sopt, topt, text, bytes, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out_text, text_cap,
+                  out_off, max_reads, out_needed, n_reads, consumed);
 }
 
 int bpsw_align_fastq_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text1,
                         size_t bytes1, const char* text2, size_t bytes2, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0, int zdrop_mode,
                         int w1_flags, int rescue_mode, int flags, char* out_text, size_t text_cap, int64_t* out_off, int64_t max_reads,
                         size_t* out_needed, bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
-  if (!c || !opt || !sopt || !topt || !out_off || !n_reads || !consumed || max_reads < 0) return fail(BPSW_ERR_ARG, "align_fastq_pe: null argument");
-  if (!text2 && !(fastq_flags & BPSW_FASTQ_INTERLEAVED)) return fail(BPSW_ERR_ARG, "align_fastq_pe: one text without BPSW_FASTQ_INTERLEAVED");
-  if (!text2) fastq_flags |= BPSW_FASTQ_PAIR_NAMES;
-  Caller A;
-  int rc = check_texts("align_fastq_pe", text1, bytes1, text2, bytes2, fastq_flags, &A);
-  if (rc != BPSW_OK) return rc;
-  thread_local Parsed P;
-  fq::Result res;
-  int how = fq::PARSE_OK;
-  *n_reads = 0; consumed[0] = consumed[1] = 0;
-  rc = parse_any(c, A, P, &res, &how);
-  if (rc != BPSW_OK) return rc;
-  *n_reads = res.n_reads;
-  if (res.n_reads > max_reads) return fail(BPSW_ERR_CAPACITY, "align_fastq_pe: out_off has room for fewer reads than the texts hold (*n_reads)");
-  if (res.n_reads / 2 > 0x7fffffffll) return fail(BPSW_ERR_LIMIT, "align_fastq_pe: more than 2^31 - 1 pairs");
-  bpsw_pairs_t g;
-  memset(&g, 0, sizeof g);
-  g.group_size = (int32_t)(res.n_reads / 2); g.id0 = id0;
-  g.read_len = P.read_len.data(); g.read_off = P.read_off.data(); g.read_pool = P.read_pool.data(); g.qual_pool = P.qual_pool.data();
-  g.read_pool_bytes = (size_t)res.needed[1];
-  g.name_off = P.name_off.data(); g.name_pool = P.name_pool.data();
-  rc = bpsw_align_pe_batch(c, opt, sopt, topt, &g, pes0, zdrop_mode, w1_flags, rescue_mode, flags, out_text, text_cap, out_off, out_needed, out_pes);
-  if (rc == BPSW_OK || rc == BPSW_ERR_CAPACITY) { consumed[0] = res.consumed[0]; consumed[1] = res.consumed[1]; }
-  return rc;
+  return fastq_pe("align_fastq_pe", false, c, opt, sopt, topt, text1, bytes1, text2, bytes2, fastq_flags, id0, pes0, zdrop_mode, w1_flags, rescue_mode,
+                  flags, out_text, text_cap, out_off, max_reads, out_needed, out_pes, n_reads, consumed);
+}
+
+// the BAM twins (the other writer is bpsw_bam.hip's: these only end in its align entries)
+int bpsw_align_fastq_bam_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
+                            size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out,
+                            size_t cap, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
+  return fastq_se("align_fastq_bam_se", true, c, opt, sopt, topt, text, bytes, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out, cap, nullptr,
+                  0, out_needed, n_reads, consumed);
+}
+
+int bpsw_align_fastq_bam_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text1,
+                            size_t bytes1, const char* text2, size_t bytes2, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0,
+                            int zdrop_mode, int w1_flags, int rescue_mode, int flags, char* out, size_t cap, size_t* out_needed,
+                            bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
+  return fastq_pe("align_fastq_bam_pe", true, c, opt, sopt, topt, text1, bytes1, text2, bytes2, fastq_flags, id0, pes0, zdrop_mode, w1_flags,
+                  rescue_mode, flags, out, cap, nullptr, 0, out_needed, out_pes, n_reads, consumed);
 }
 
 void bpsw_last_fastq_times(double ms[5]) {

@@ -6,7 +6,8 @@
 // reads of it (rid, pos, is_rev, n_cigar and the CIGAR words); 0 is a line without a mate (m == NULL).  Here the same line is a function of a
 // LINE RECORD (SamLine) and the batch's tables (SamBatch), so that a kernel can write it: sam_line_len counts the bytes,
 // sam_line_write stores them, both through one emitter (emit_line) over a sink that either counts or stores, so the two cannot
-// drift apart.  Every store is checked against `end`; a line that would pass it, or whose byte count differs from what the caller
+// drift apart.  What the line says -- the mate copy, the flag bits and their fold, the clips, TLEN -- is resolved once
+// (resolve_line), for this emitter and for the BAM record's (bpsw_bam_core.h).  Every store is checked against `end`; a line that would pass it, or whose byte count differs from what the caller
 // expected, is reported through a status word and nothing is written past `end`.
 //
 // Numbers are formatted by counting their digits first and storing straight into the destination; the letter tables are packed
@@ -122,11 +123,31 @@ BPSW_SAM_HD int ref_len(const uint32_t* cig, int n) {  // getRlen: the bases of 
   return l;
 }
 
-template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line) {
+// What a line says once memAlnToSAM's rules are applied: the one resolution step under both emitters, the text here and the binary
+// record of bpsw_bam_core.h.  Scalars and pointers into the batch only.
+struct Resolved {
+  const SamLine* L;
+  const SamRead* R;
+  const uint32_t* cig;   // the line's CIGAR words (n_cigar of them count; a clip prints as H when `which` > 0, else as S)
+  int which;             // its place in its read's list
+  int rid, is_rev, n_cigar;   // after the mate copy: rid < 0 prints "*\t0\t0\t*"; n_cigar == 0 prints '*' and drops NM / MD
+  long long pos;
+  int folded;            // the flag as it is printed: 0x10000 folded into 0x100
+  bool hidden;           // SEQ and QUAL are '*' and there is no SA list (0x100 as the flavour sees it)
+  bool has_next;         // the mate columns are filled: m_rid, m_pos, tlen; else "*\t0\t0"
+  int m_rid;
+  long long m_pos, tlen;
+  int qb, qe;            // SEQ / QUAL are the read's bases [qb, qe), read backwards and complemented when is_rev (qe <= qb: none)
+};
+
+BPSW_SAM_HD Resolved resolve_line(const SamBatch& B, int line) {
+  Resolved v;
   const SamLine& L = B.lines[line];
-  const SamRead& R = B.reads[L.read];
-  const int which = line - L.first;
+  v.L = &L;
+  v.R = &B.reads[L.read];
+  v.which = line - L.first;
   const uint32_t* cig = B.cig + L.cig_at;
+  v.cig = cig;
   int flag = L.flag;
   // the line's and the mate's place; an unmapped one of the two is put where the other is
   int rid = L.rid, is_rev = L.is_rev, n_cigar = L.n_cigar;
@@ -147,24 +168,78 @@ template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line)
   if (has_m && m_rid < 0 && rid >= 0) { m_rid = rid; m_pos = pos; m_is_rev = is_rev; m_n_cigar = 0; }
   if (is_rev) flag |= 0x10;
   if (has_m && m_is_rev) flag |= 0x20;
+  v.folded = (flag & 0xffff) | ((flag & 0x10000) ? 0x100 : 0);
+  if (B.flavour == FLAVOUR_SCALA) flag = v.folded;  // the Scala assigns the folded flag, the C only prints it
+  v.hidden = (flag & 0x100) != 0;
+  v.rid = rid; v.is_rev = is_rev; v.n_cigar = n_cigar; v.pos = pos;
+  v.has_next = has_m && m_rid >= 0;
+  v.m_rid = m_rid; v.m_pos = m_pos;
+  v.tlen = 0;
+  if (v.has_next && rid == m_rid && m_n_cigar > 0 && n_cigar > 0) {  // the distance between the two 5' ends
+    const long long p0 = pos + (is_rev ? ref_len(cig, n_cigar) - 1 : 0);
+    const long long p1 = m_pos + (m_is_rev ? ref_len(m_cig, m_n_cigar) - 1 : 0);
+    v.tlen = -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0));
+  }
+  int qb = 0, qe = v.R->len;
+  const int nc = n_cigar;
+  const bool clip_first = nc > 0 && is_clip(cig[0]), clip_last = nc > 0 && is_clip(cig[nc - 1]);
+  if (!is_rev) {
+    if (v.which && clip_first) qb += (int)(cig[0] >> 4);
+    if (v.which && clip_last) qe -= (int)(cig[nc - 1] >> 4);
+  } else {
+    if (v.which && clip_first) qe -= (int)(cig[0] >> 4);
+    if (v.which && clip_last) qb += (int)(cig[nc - 1] >> 4);
+  }
+  v.qb = qb; v.qe = qe;
+  return v;
+}
+
+// the SA list of a line: its read's other lines that are not 0x100
+BPSW_SAM_HD bool has_sa(const SamBatch& B, const SamLine& L, int which) {
+  for (int i = 0; i < L.n_list; ++i)
+    if (i != which && !(B.lines[L.first + i].flag & 0x100)) return true;
+  return false;
+}
+template <class S> BPSW_SAM_HD void put_sa_list(S& s, const SamBatch& B, const SamLine& L, int which) {
+  for (int i = 0; i < L.n_list; ++i) {
+    const SamLine& r = B.lines[L.first + i];
+    if (i == which || (r.flag & 0x100)) continue;
+    put_contig(s, B, r.rid);
+    put_char(s, ',');
+    put_num(s, r.pos + 1);
+    put_char(s, ',');
+    put_char(s, r.is_rev ? '-' : '+');
+    put_char(s, ',');
+    const uint32_t* rc = B.cig + r.cig_at;
+    for (int k = 0; k < r.n_cigar; ++k) { put_num(s, (long long)(rc[k] >> 4)); put_char(s, op_letter((int)(rc[k] & 0xf))); }
+    put_char(s, ',');
+    put_num(s, r.mapq);
+    put_char(s, ',');
+    put_num(s, r.NM);
+    put_char(s, ';');
+  }
+}
+
+template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line) {
+  const Resolved v = resolve_line(B, line);
+  const SamLine& L = *v.L;
+  const SamRead& R = *v.R;
   put_bytes(s, B.names + R.name_at, R.name_len);
   put_char(s, '\t');
-  const int folded = (flag & 0xffff) | ((flag & 0x10000) ? 0x100 : 0);
-  if (B.flavour == FLAVOUR_SCALA) flag = folded;  // the Scala assigns the folded flag, the C only prints it
-  put_num(s, folded);
+  put_num(s, v.folded);
   put_char(s, '\t');
-  if (rid >= 0) {
-    put_contig(s, B, rid);
+  if (v.rid >= 0) {
+    put_contig(s, B, v.rid);
     put_char(s, '\t');
-    put_num(s, pos + 1);
+    put_num(s, v.pos + 1);
     put_char(s, '\t');
     put_num(s, L.mapq);
     put_char(s, '\t');
-    if (n_cigar > 0) {
-      for (int i = 0; i < n_cigar; ++i) {
-        int c = (int)(cig[i] & 0xf);
-        if (c == 3 || c == 4) c = which ? 4 : 3;  // hard clipping on every line but the read's first
-        put_num(s, (long long)(cig[i] >> 4));
+    if (v.n_cigar > 0) {
+      for (int i = 0; i < v.n_cigar; ++i) {
+        int c = (int)(v.cig[i] & 0xf);
+        if (c == 3 || c == 4) c = v.which ? 4 : 3;  // hard clipping on every line but the read's first
+        put_num(s, (long long)(v.cig[i] >> 4));
         put_char(s, op_letter(c));
       }
     } else {
@@ -174,52 +249,37 @@ template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line)
     put_bytes(s, "*\t0\t0\t*", 7);
   }
   put_char(s, '\t');
-  if (has_m && m_rid >= 0) {
-    if (rid == m_rid) put_char(s, '='); else put_contig(s, B, m_rid);
+  if (v.has_next) {
+    if (v.rid == v.m_rid) put_char(s, '='); else put_contig(s, B, v.m_rid);
     put_char(s, '\t');
-    put_num(s, m_pos + 1);
+    put_num(s, v.m_pos + 1);
     put_char(s, '\t');
-    if (rid == m_rid && m_n_cigar > 0 && n_cigar > 0) {  // the distance between the two 5' ends
-      const long long p0 = pos + (is_rev ? ref_len(cig, n_cigar) - 1 : 0);
-      const long long p1 = m_pos + (m_is_rev ? ref_len(m_cig, m_n_cigar) - 1 : 0);
-      put_num(s, -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
-    } else {
-      put_char(s, '0');
-    }
+    put_num(s, v.tlen);
   } else {
     put_bytes(s, "*\t0\t0", 5);
   }
   put_char(s, '\t');
-  if (flag & 0x100) {
+  if (v.hidden) {
     put_bytes(s, "*\t*", 3);
   } else {
-    int qb = 0, qe = R.len;
-    const int nc = n_cigar;
-    const bool clip_first = nc > 0 && is_clip(cig[0]), clip_last = nc > 0 && is_clip(cig[nc - 1]);
+    const int qb = v.qb, qe = v.qe;
     const uint8_t* seq = B.seq + R.seq_at;
-    if (!is_rev) {
-      if (which && clip_first) qb += (int)(cig[0] >> 4);
-      if (which && clip_last) qe -= (int)(cig[nc - 1] >> 4);
-    } else {
-      if (which && clip_first) qe -= (int)(cig[0] >> 4);
-      if (which && clip_last) qb += (int)(cig[nc - 1] >> 4);
-    }
     const long long n = qe > qb ? qe - qb : 0;
     char* d = s.take(n + 1 + (B.qual ? n : 1));  // bases, tab, qualities
     if (d) {
-      if (!is_rev) for (long long i = 0; i < n; ++i) d[i] = base_fwd(seq[qb + i]);
+      if (!v.is_rev) for (long long i = 0; i < n; ++i) d[i] = base_fwd(seq[qb + i]);
       else for (long long i = 0; i < n; ++i) d[i] = base_rev(seq[qe - 1 - i]);
       d[n] = '\t';
       if (!B.qual) {
         d[n + 1] = '*';
       } else {
         const uint8_t* q = B.qual + R.seq_at;
-        if (!is_rev) for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qb + i];
+        if (!v.is_rev) for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qb + i];
         else for (long long i = 0; i < n; ++i) d[n + 1 + i] = (char)q[qe - 1 - i];
       }
     }
   }
-  if (n_cigar > 0) {
+  if (v.n_cigar > 0) {
     put_bytes(s, "\tNM:i:", 6);
     put_num(s, L.NM);
     put_bytes(s, "\tMD:Z:", 6);
@@ -228,30 +288,9 @@ template <class S> BPSW_SAM_HD void emit_line(S& s, const SamBatch& B, int line)
   if (L.score >= 0) { put_bytes(s, "\tAS:i:", 6); put_num(s, L.score); }
   if (L.sub >= 0) { put_bytes(s, "\tXS:i:", 6); put_num(s, L.sub); }
   if (B.rg_len > 0) { put_bytes(s, "\tRG:Z:", 6); put_bytes(s, B.rg, B.rg_len); }
-  if (!(flag & 0x100)) {
-    bool others = false;
-    for (int i = 0; i < L.n_list; ++i)
-      if (i != which && !(B.lines[L.first + i].flag & 0x100)) { others = true; break; }
-    if (others) {
-      put_bytes(s, "\tSA:Z:", 6);
-      for (int i = 0; i < L.n_list; ++i) {
-        const SamLine& r = B.lines[L.first + i];
-        if (i == which || (r.flag & 0x100)) continue;
-        put_contig(s, B, r.rid);
-        put_char(s, ',');
-        put_num(s, r.pos + 1);
-        put_char(s, ',');
-        put_char(s, r.is_rev ? '-' : '+');
-        put_char(s, ',');
-        const uint32_t* rc = B.cig + r.cig_at;
-        for (int k = 0; k < r.n_cigar; ++k) { put_num(s, (long long)(rc[k] >> 4)); put_char(s, op_letter((int)(rc[k] & 0xf))); }
-        put_char(s, ',');
-        put_num(s, r.mapq);
-        put_char(s, ',');
-        put_num(s, r.NM);
-        put_char(s, ';');
-      }
-    }
+  if (!v.hidden && has_sa(B, L, v.which)) {
+    put_bytes(s, "\tSA:Z:", 6);
+    put_sa_list(s, B, L, v.which);
   }
   put_char(s, '\n');
 }

@@ -8,7 +8,8 @@
 // bpsw_align_pe_batch is mem_process_seqs under MEM_F_PE (native/bwamem.c:1064-1083 == FastMap.scala:262-307, :352-395) for a
 // batch: bpsw_worker1_batch on the 2n reads, the insert-size statistics (given, or bpsw_pe_stat over this batch's lists), the
 // rescue half of bpsw_worker2_batch (pe_rescue), then the tail above.  worker1 with its lists and their capacity retry is
-// worker1_lists (bpsw_sam_se.hip), as for single-end reads.
+// worker1_lists (bpsw_sam_se.hip), as for single-end reads.  Its body is align_pe, with the tail it ends in as an argument:
+// bpsw_align_bam_pe_batch (bpsw_bam.hip) is the same body with the BAM tail.
 #include <string.h>
 
 #include <vector>
@@ -24,23 +25,10 @@ thread_local double t_last[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
 
 }  // namespace
 
-extern "C" {
-
-int bpsw_sam_pe_batch_ex(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, int flags, char* out_text,
-                         size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
-  if (flags & ~BPSW_SAM_TEXT_DEVICE) return fail(BPSW_ERR_ARG, "sam_pe: unknown flag");
-  memset(t_last, 0, 4 * sizeof(double));
-  SamCall m;
-  m.paired = true;
-  if (flags & BPSW_SAM_TEXT_DEVICE) { m.on_device = text_on_device; m.times = t_last; m.n_times = 4; }
-  return sam_batch(c, opt, topt, nullptr, g, m, out_text, text_cap, out_off, out_needed, out_regs);
-}
-
-int bpsw_align_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g,
-                        const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char* out_text, size_t text_cap,
-                        int64_t* out_off, size_t* out_needed, bpsw_pestat_t* out_pes) {
+int bpsw::align_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g,
+                   const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, PeTail tail, char* out_text, size_t text_cap,
+                   int64_t* out_off, size_t* out_needed, bpsw_pestat_t* out_pes) {
   if (!c || !opt || !sopt || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "align_pe: null argument");
-  if (flags & ~BPSW_SAM_TEXT_DEVICE) return fail(BPSW_ERR_ARG, "align_pe: unknown flag");
   const int G = g->group_size;
   if (G < 0) return fail(BPSW_ERR_ARG, "align_pe: negative group size");
   memset(t_last, 0, sizeof t_last);
@@ -86,9 +74,29 @@ int bpsw_align_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_op
   const double t3 = wall_ms();
   p.reg_cnt = cnt2.data();
   p.regs = regs2.data();
-  rc = bpsw_sam_pe_batch_ex(c, opt, topt, &p, flags, out_text, text_cap, out_off, out_needed, nullptr);
+  rc = tail(c, opt, topt, &p, flags, out_text, text_cap, out_off, out_needed, nullptr);
   t_last[4] = t1 - t0; t_last[5] = t2 - t1; t_last[6] = t3 - t2; t_last[7] = wall_ms() - t3;
   return rc;
+}
+
+extern "C" {
+
+int bpsw_sam_pe_batch_ex(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, int flags, char* out_text,
+                         size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
+  if (flags & ~BPSW_SAM_TEXT_DEVICE) return fail(BPSW_ERR_ARG, "sam_pe: unknown flag");
+  memset(t_last, 0, 4 * sizeof(double));
+  SamCall m;
+  m.paired = true;
+  if (flags & BPSW_SAM_TEXT_DEVICE) { m.on_device = text_on_device; m.times = t_last; m.n_times = 4; }
+  return sam_batch(c, opt, topt, nullptr, g, m, out_text, text_cap, out_off, out_needed, out_regs);
+}
+
+int bpsw_align_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g,
+                        const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char* out_text, size_t text_cap,
+                        int64_t* out_off, size_t* out_needed, bpsw_pestat_t* out_pes) {
+  if (c && opt && sopt && topt && g && out_off && (flags & ~BPSW_SAM_TEXT_DEVICE)) return fail(BPSW_ERR_ARG, "align_pe: unknown flag");  // (after the null checks)
+  return align_pe(c, opt, sopt, topt, g, pes0, zdrop_mode, w1_flags, rescue_mode, flags, bpsw_sam_pe_batch_ex, out_text, text_cap, out_off, out_needed,
+                  out_pes);
 }
 
 void bpsw_last_sam_pe_times(double ms[8]) {

@@ -12,7 +12,9 @@
 //   sam_write_kernel  one line per lane: the line's bytes at its offset in one device block, which comes back with one copy.
 // A line depends on its read's lines (the SA:Z list) and, in a pair, on the first line of the other read; it reads both from the table.  Into the kernels go, as one
 // staged block, the line table built on the host from make_aln's results (fixed-size records, each line's CIGAR words and MD
-// bytes), the read records with the base, quality and name pools, the contig names and the read-group ID.
+// bytes), the read records with the base, quality and name pools, the contig names and the read-group ID.  Building and staging that
+// block is stage_lines, which the BAM writer (bam_on_device, bpsw_bam.hip) calls too; align_se is bpsw_align_se_batch's body with the
+// tail it ends in as an argument, so that bpsw_align_bam_se_batch is the same body with the other writer.
 #include <string.h>
 
 #include <algorithm>
@@ -48,16 +50,15 @@ thread_local double t_last[6] = {0., 0., 0., 0., 0., 0.};
 
 }  // namespace
 
-int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& sl,
-                         char* out_text, size_t text_cap, int64_t* out_off, size_t* total_out, double times[4]) {
+int bpsw::stage_lines(bpsw_ctx* c, const std::string& w, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& sl,
+                      StageIn* staged, sc::SamBatch* batch) {
   const std::vector<Aln>& aa = sl.aa;
   const std::vector<int32_t>& line_read = sl.line_read;
   const std::vector<int32_t>& read_first = sl.read_first;
   const Aln* mate = sl.mate.empty() ? nullptr : sl.mate.data();
   const JobResults& R = *sl.R;
   const int n = g.n, n_lines = (int)aa.size(), n_names = g.n >> g.name_shift;
-  const std::string w(who);
-  const double t0 = wall_ms();
+  StageIn& in = *staged;
   // ---- the line table -------------------------------------------------------------------------------------------------------
   std::vector<sc::SamLine> lines((size_t)n_lines);
   for (int i = 0; i < n_lines; ++i) {
@@ -102,7 +103,6 @@ int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const
   }
   const size_t rg_len = t.rg_id[0] ? strnlen(t.rg_id, sizeof t.rg_id) : 0;
 
-  StageIn in;
   const int i_lines = in.add(lines.data(), sizeof(sc::SamLine) * (size_t)n_lines), i_reads = in.add(reads.data(), sizeof(sc::SamRead) * (size_t)n);
   const int i_cig = in.add(R.cig.data(), 4 * R.cig.size()), i_md = in.add(R.md.data(), R.md.size());
   const int i_seq = in.add(g.read_pool + lo, (size_t)(hi - lo));
@@ -110,11 +110,8 @@ int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const
   const int i_names = in.add(g.name_pool + name_lo, (size_t)(name_hi - name_lo));
   const int i_cat = in.add(ctg_at.data(), 4 * ctg_at.size()), i_cnm = in.add(ctg_names.data(), ctg_names.size());
   const int i_rg = in.add(t.rg_id, rg_len);
-  StageOut lens;
-  const int r_len = lens.add(4 * (size_t)n_lines);
-  HIP_TRY(lens.reserve(c->h_stage_out, c->d_sw_out));
   HIP_TRY(in.stage(c->h_stage_in, c->d_sw_in, c->stream));
-  sc::SamBatch B;
+  sc::SamBatch& B = *batch;
   B.lines = in.dev<sc::SamLine>(i_lines); B.reads = in.dev<sc::SamRead>(i_reads);
   B.cig = in.dev<uint32_t>(i_cig); B.md = in.dev<char>(i_md);
   B.seq = in.dev<uint8_t>(i_seq); B.qual = i_qual >= 0 ? in.dev<uint8_t>(i_qual) : nullptr;
@@ -122,6 +119,22 @@ int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const
   B.ctg_at = in.dev<int32_t>(i_cat); B.ctg_names = in.dev<char>(i_cnm);
   B.rg = in.dev<char>(i_rg);
   B.n_ctg = (int32_t)bns.name.size(); B.rg_len = (int32_t)rg_len; B.flavour = t.flavour;
+  return BPSW_OK;
+}
+
+int bpsw::text_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& sl,
+                         char* out_text, size_t text_cap, int64_t* out_off, size_t* total_out, double times[4]) {
+  const std::vector<int32_t>& read_first = sl.read_first;
+  const int n = g.n, n_lines = (int)sl.aa.size();
+  const std::string w(who);
+  const double t0 = wall_ms();
+  StageOut lens;
+  const int r_len = lens.add(4 * (size_t)n_lines);
+  HIP_TRY(lens.reserve(c->h_stage_out, c->d_sw_out));
+  StageIn in;
+  sc::SamBatch B;
+  const int rc = stage_lines(c, w, bns, t, g, sl, &in, &B);
+  if (rc != BPSW_OK) return rc;
   const dim3 grid((unsigned)((n_lines + 63) / 64));
   const double t1 = wall_ms();
   // ---- lengths ---------------------------------------------------------------------------------------------------------------
@@ -188,20 +201,8 @@ int bpsw::worker1_lists(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_op
   return rc;
 }
 
-extern "C" {
-
-int bpsw_sam_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g, int flags,
-                      char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
-  if (c && topt && g && out_off && (flags & ~BPSW_SAM_TEXT_DEVICE)) return fail(BPSW_ERR_ARG, "sam_se: unknown flag");  // (after the null checks)
-  SamCall m;
-  m.on_device = (flags & BPSW_SAM_TEXT_DEVICE) ? text_on_device : nullptr;
-  m.times = t_last; m.n_times = 6;
-  return sam_batch(c, opt, topt, g, nullptr, m, out_text, text_cap, out_off, out_needed, out_regs);
-}
-
-int bpsw_align_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt,
-                        const bpsw_se_reads_t* g, int zdrop_mode, int w1_flags, int flags, char* out_text, size_t text_cap, int64_t* out_off,
-                        size_t* out_needed) {
+int bpsw::align_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g,
+                   int zdrop_mode, int w1_flags, int flags, SeTail tail, char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed) {
   if (!c || !opt || !sopt || !topt || !g || !out_off) return fail(BPSW_ERR_ARG, "align_se: null argument");
   const int n = g->n_reads;
   if (n < 0) return fail(BPSW_ERR_ARG, "align_se: negative number of reads");
@@ -220,9 +221,26 @@ int bpsw_align_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_op
   bpsw_se_reads_t s = *g;
   s.reg_cnt = cnt.data();
   s.regs = regs.data();
-  rc = bpsw_sam_se_batch(c, opt, topt, &s, flags, out_text, text_cap, out_off, out_needed, nullptr);
+  rc = tail(c, opt, topt, &s, flags, out_text, text_cap, out_off, out_needed, nullptr);
   t_last[4] = t1 - t0; t_last[5] = wall_ms() - t1;
   return rc;
+}
+
+extern "C" {
+
+int bpsw_sam_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g, int flags,
+                      char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs) {
+  if (c && topt && g && out_off && (flags & ~BPSW_SAM_TEXT_DEVICE)) return fail(BPSW_ERR_ARG, "sam_se: unknown flag");  // (after the null checks)
+  SamCall m;
+  m.on_device = (flags & BPSW_SAM_TEXT_DEVICE) ? text_on_device : nullptr;
+  m.times = t_last; m.n_times = 6;
+  return sam_batch(c, opt, topt, g, nullptr, m, out_text, text_cap, out_off, out_needed, out_regs);
+}
+
+int bpsw_align_se_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt,
+                        const bpsw_se_reads_t* g, int zdrop_mode, int w1_flags, int flags, char* out_text, size_t text_cap, int64_t* out_off,
+                        size_t* out_needed) {
+  return align_se(c, opt, sopt, topt, g, zdrop_mode, w1_flags, flags, bpsw_sam_se_batch, out_text, text_cap, out_off, out_needed);
 }
 
 void bpsw_last_sam_se_times(double ms[6]) {

@@ -140,4 +140,27 @@ int pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const bpsw_
 int worker1_lists(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const TextReads& g, int zdrop_mode, int w1_flags,
                   std::vector<int32_t>* cnt, std::vector<bpsw_alnreg_t>* regs);
 
+// ---- what the BAM entries (bpsw_bam.hip) share with the text's ----------------------------------------------------------------------
+// The first half of text_on_device (bpsw_sam_se.hip): the line table of `L` with its mate assertion, the read records and pools, the
+// contig names and the read group, as one block staged on c->stream; *B points into it on the device.
+namespace samcore { struct SamBatch; }
+int stage_lines(bpsw_ctx* c, const std::string& who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& L,
+                StageIn* staged, samcore::SamBatch* B);
+// bam_on_device (bpsw_bam.hip), the second writer: the records of `L` through bam_len_kernel and bam_write_kernel, their stream cut into
+// BGZF blocks by bgzf_frame_kernel.  A TextOnDevice: *total_out is the framed size, out_off gets the records' offsets in the
+// unframed stream (the entries keep them to themselves), times[5]: the three kernels, the tables, the round trip.
+int bam_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& L,
+                  char* out, size_t cap, int64_t* out_off, size_t* total_out, double times[5]);
+// The bodies of bpsw_align_se_batch (bpsw_sam_se.hip) and bpsw_align_pe_batch (bpsw_sam_pe.hip) with the tail they end in as an
+// argument: bpsw_sam_se_batch / bpsw_sam_pe_batch_ex for the text, the BAM tails for bpsw_align_bam_*.
+typedef int (*SeTail)(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g, int flags, char* out,
+                      size_t cap, int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs);
+typedef int (*PeTail)(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g, int flags, char* out, size_t cap,
+                      int64_t* out_off, size_t* out_needed, bpsw_alnreg_t* out_regs);
+int align_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const bpsw_se_reads_t* g,
+             int zdrop_mode, int w1_flags, int flags, SeTail tail, char* out_text, size_t text_cap, int64_t* out_off, size_t* out_needed);
+int align_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const bpsw_pairs_t* g,
+             const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, PeTail tail, char* out_text, size_t text_cap,
+             int64_t* out_off, size_t* out_needed, bpsw_pestat_t* out_pes);
+
 }  // namespace bpsw

@@ -719,6 +719,58 @@ int bpsw_align_fastq_pe(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_
  * fastq_emit_kernel (events on the stream around each; 0 under BPSW_FASTQ_HOST), and the parse's round trip with the copies. */
 void bpsw_last_fastq_times(double ms[5]);
 
+/* ---- alignments out as BAM (bpsw_bam.hip) -----------------------------------------------------------------------------------------
+ *
+ * Every entry above that writes SAM text on the device has a twin that writes the same lines as BAM records (SAM specification 4.2),
+ * framed as BGZF blocks: bpsw_bam_se_batch / bpsw_bam_pe_batch are bpsw_sam_se_batch / bpsw_sam_pe_batch_ex, bpsw_align_bam_*_batch
+ * are bpsw_align_*_batch, bpsw_align_fastq_bam_* are bpsw_align_fastq_* -- the same bodies with the other writer.  The record of a line
+ * holds what the line says (csrc/bpsw_bam_core.h: refID, pos, bin, the folded flag, the CIGAR with H for S on later lines, SEQ two bases a
+ * byte, QUAL - 33 or 0xff, NM MD AS XS RG SA in the text's order, integers in the narrowest type).  The records of a call, in line
+ * order, form one stream of S bytes that is cut every P bytes (P = 65280 unless bpsw_bam_set_block_payload says otherwise; records
+ * do not respect the cuts) into ceil(S / P) gzip members of one STORED deflate block each -- nothing is compressed -- with the CRC-32
+ * computed on the device.  out receives S + 31 ceil(S / P) bytes: a whole number of BGZF blocks, so that
+ *     bpsw_bam_header || the outputs of any number of calls || bpsw_bam_eof
+ * is a valid BAM file.  There is no out_off: a record carries its own length.  BPSW_ERR_CAPACITY with *out_needed set when cap is too
+ * small (nothing is written then: the size is known before the records are); an empty batch is *out_needed == 0.  flags must be 0
+ * (BPSW_ERR_ARG otherwise); the FASTQ twins keep fastq_flags, and w1_flags pass through.  A read name of more than 254 bytes cannot be
+ * a BAM record: BPSW_ERR_LIMIT, nothing written.  Everything else -- arguments, refusals, out_regs, out_pes, n_reads, consumed,
+ * bpsw_last_tail_times -- is the twin's.  Not here: deflate compression, sorting, an index. */
+int bpsw_bam_se_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_tail_opt_t *topt, const bpsw_se_reads_t *reads, int flags, char *out,
+                      size_t cap, size_t *out_needed, bpsw_alnreg_t *out_regs);
+int bpsw_bam_pe_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_tail_opt_t *topt, const bpsw_pairs_t *g, int flags, char *out,
+                      size_t cap, size_t *out_needed, bpsw_alnreg_t *out_regs);
+int bpsw_align_bam_se_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                            const bpsw_se_reads_t *reads, int zdrop_mode, int w1_flags, int flags, char *out, size_t cap,
+                            size_t *out_needed);
+int bpsw_align_bam_pe_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                            const bpsw_pairs_t *g, const bpsw_pestat_t *pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags,
+                            char *out, size_t cap, size_t *out_needed, bpsw_pestat_t *out_pes);
+int bpsw_align_fastq_bam_se(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                            const char *text, size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags,
+                            int flags, char *out, size_t cap, size_t *out_needed, int64_t *n_reads, int64_t *consumed);
+int bpsw_align_fastq_bam_pe(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                            const char *text1, size_t bytes1, const char *text2, size_t bytes2, int fastq_flags, int64_t id0,
+                            const bpsw_pestat_t *pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char *out, size_t cap,
+                            size_t *out_needed, bpsw_pestat_t *out_pes, int64_t *n_reads, int64_t consumed[2]);
+/* The header, on the calling thread (nothing is launched).  bpsw_sam_header: the text "@HD\tVN:1.6\tSO:unsorted\n", one
+ * "@SQ\tSN:<name>\tLN:<len>\n" per contig, then `extra` (extra_bytes of the caller's own lines, @RG / @PG, verbatim; NULL for none).
+ * The contigs are those loaded with bpsw_bns_load when ctx is given (n_seqs, len and names are ignored), else the table of the
+ * arguments: len[n_seqs] and names as bpsw_bns_load takes them (NULL: no names).  A contig without a name is "ctg<rid + 1>", as in the
+ * lines.  bpsw_bam_header: "BAM\1", l_text, that text, n_ref and per contig l_name, the name with its NUL and l_ref, framed as BGZF
+ * blocks like the records.  bpsw_bam_eof: the 28-byte end-of-file block of the specification.  All three: BPSW_ERR_CAPACITY with
+ * *out_needed set, and nothing written, when cap is too small. */
+int bpsw_sam_header(bpsw_ctx_t *ctx, int32_t n_seqs, const int32_t *len, const char *names, const char *extra, size_t extra_bytes, char *out,
+                    size_t cap, size_t *out_needed);
+int bpsw_bam_header(bpsw_ctx_t *ctx, int32_t n_seqs, const int32_t *len, const char *names, const char *extra, size_t extra_bytes, char *out,
+                    size_t cap, size_t *out_needed);
+int bpsw_bam_eof(char *out, size_t cap, size_t *out_needed);
+/* The payload bytes of a BGZF block, process-wide: 1 .. 65280; 0 = the default, 65280 (htslib's).  Anything else is BPSW_ERR_ARG and
+ * changes nothing.  The counterpart of bpsw_scan_set_tile: tests put block edges anywhere in a small batch with it. */
+int bpsw_bam_set_block_payload(int bytes);
+/* Diagnostics, of the calling thread's most recent call of a BAM entry (ms): bam_len_kernel, bam_write_kernel, bgzf_frame_kernel,
+ * building and staging the line table, the round trip of the three kernels with the copies. */
+void bpsw_last_bam_times(double ms[5]);
+
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {
   uint64_t ext_calls, ext_tasks, ext_wire_bytes;
