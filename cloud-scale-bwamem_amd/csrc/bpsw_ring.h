@@ -111,7 +111,8 @@ struct SwRingPayload {
   uint64_t out;                          // 7 int32 per job
   int32_t n_jobs, bias;
   uint64_t mat_row[5];
-  int32_t a, b, o_del, e_del, o_ins, e_ins, xtra, pad;
+  int32_t a, b, o_del, e_del, o_ins, e_ins, xtra;
+  int32_t pull;  // != 0: the three addresses name the caller's pinned block and each worker stages its own unit (bpsw_ring_pull_core.h)
 };
 // The rescue kernel's ring classes: 3 and 5 (columns per lane: mates up to 171 / 256 bases, a job pair per ticket), and the HALF-WAVE class
 // for batches whose longest mate has at most 150 bases: its workers take TWO consecutive units with one ticket and run them as a quartet

@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "bpsw_internal.h"
+#include "bpsw_ring_pull_core.h"
 
 using namespace bpsw;
 
@@ -45,6 +46,26 @@ int sw_stage_begin(bpsw_ctx* c, int n, size_t q_pool_bytes, size_t t_pool_bytes,
 static std::atomic<int> g_sw_in_flight[64];
 int sw_launches_in_flight(int device) { return g_sw_in_flight[device >= 0 && device < 64 ? device : 0].load(std::memory_order_relaxed); }
 void sw_launch_in_flight(int device, int delta) { g_sw_in_flight[device >= 0 && device < 64 ? device : 0].fetch_add(delta, std::memory_order_relaxed); }
+
+// Can the resident workers of `ring_class` pull this batch (bpsw_ring_pull_core.h)?  The block's parts at multiples of 16 bytes, and every
+// unit a worker may take within its slice: a pair per ticket, or -- the half-wave class -- any two consecutive pairs.
+static bool sw_pull_fits(const SwStage& st, bool pac_mode, int ring_class) {
+  if (!rp::block_ok((uint64_t)(uintptr_t)st.base, st.o_qpool, st.q_pool_bytes, st.o_tpool, pac_mode ? 0 : st.t_pool_bytes, st.o_packed, st.total)) return false;
+  const uint32_t cap = rp::slice_bytes(ring_class == 5 ? 5 : 3, ring_class == RING_CLASS_SW_HALVES);  // (what launch_swp_resident gives a worker of the class)
+  const int per_unit = ring_class == RING_CLASS_SW_HALVES ? 4 : 2;
+  const uint32_t* rec = (const uint32_t*)(st.base + st.o_packed);
+  for (int first = 0; first < st.n; first += 2) {
+    rp::Job job[rp::kMaxJobs] = {};
+    const int n_here = st.n - first < per_unit ? st.n - first : per_unit;
+    for (int k = 0; k < n_here; ++k) {
+      const uint32_t* r = rec + 8 * (size_t)(first + k);
+      job[k].q_off = ((uint64_t)r[1] << 32) | r[0]; job[k].t_off = ((uint64_t)r[3] << 32) | r[2];
+      job[k].q_len = r[4]; job[k].t_len = r[5];
+    }
+    if (!rp::plan(job, n_here, !pac_mode, cap).fits) return false;
+  }
+  return true;
+}
 
 int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st, int mq, int mt, bool pac_mode, const int32_t** results) {
   SwScoring sc;
@@ -105,13 +126,25 @@ int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st
     struct InFlight { int d; explicit InFlight(int dev) : d(dev) { sw_launch_in_flight(d, 1); } ~InFlight() { sw_launch_in_flight(d, -1); } } in_flight(c->device);
     const double t_dev0 = stat_ms();
     // Where the workers read the batch from.  A launch of its own reads it from the pinned block (zero-copy); under the resident kernel a
-    // job pair that does so pays about eight dependent round trips over PCIe and takes 160-190 us instead of 145-155 (BPSW_RING_DIAG
-    // build, one worker wave per SIMD; 390 against 320 with three), and the bench step is a fifth slower (1.73 against 2.05 x 10^8 reads/s at
-    // two worker workgroups per CU).  So a batch is copied into the context's device arena by the copy engine -- one bulk transfer,
-    // waited for before the descriptor is published -- and the workers read HBM.  Small batches (BPSW_RING_ZC_BYTES, default 16 KB) stay
-    // zero-copy: the copy's latency would be most of their call.
+    // job pair that reads the block PIECEMEAL pays about eight dependent round trips over PCIe -- the record, the mate, the window in
+    // chunks, the same again in pass 2 -- and takes 160-190 us instead of 145-155 (BPSW_RING_DIAG build, one worker wave per SIMD; 390
+    // against 320 with three), and the bench step is a fifth slower (1.73 against 2.05 x 10^8 reads/s at two worker workgroups per CU).
+    // Two answers to that.  The PULL (bpsw_ring_pull_core.h): the descriptor names the pinned block and every worker stages its own
+    // unit in LDS -- the records with one load, then each mate and window in one burst of 16-byte loads -- so a unit costs two round
+    // trips, and this call neither copies nor waits for a copy: no transfer of its own on the copy lane the extension's wire batches
+    // use.  It needs a block whose parts sit at multiples of 16 bytes (sw_stage_begin's do) and units that fit a worker's slice
+    // (sw_pull_fits looks at every unit).  The COPY, for whatever the pull does not take, for class 5 and with BPSW_RING_PULL=0: the batch goes into
+    // the context's device arena by the copy engine -- one bulk transfer, waited for before the descriptor is published -- and the
+    // workers read HBM.  Small batches (BPSW_RING_ZC_BYTES, default 16 KB) are read in place, piecemeal, as ever: neither the copy's
+    // latency nor the pull's LDS staging was measured to pay for them.
     static const size_t ring_zc_bytes = getenv("BPSW_RING_ZC_BYTES") ? (size_t)atoll(getenv("BPSW_RING_ZC_BYTES")) : 16384;
-    if (st.total > ring_zc_bytes) {
+    // BPSW_RING_PULL: 0 never, 1 every class; unset: classes 3 and half-wave (mates up to 171 bases), where it is a gain -- the bench step
+    // 2.49-2.76 -> 2.78-2.86 x 10^8 reads/s -- and not class 5, where it is none: with mates of 250 bases the step is the extension's, the
+    // rescue call's device phase falls from 4.2 to 0.65 ms all the same, and the step comes out 1.8 % BELOW the copy's (1.912-1.924 against
+    // 1.947-1.960 x 10^7, four runs each, profiles/ring_pull_ab.txt).
+    static const int ring_pull = getenv("BPSW_RING_PULL") ? atoi(getenv("BPSW_RING_PULL")) : -1;
+    const bool pull = st.total > ring_zc_bytes && (ring_pull > 0 || (ring_pull < 0 && ring_class != 5)) && sw_pull_fits(st, pac_mode, ring_class);
+    if (st.total > ring_zc_bytes && !pull) {
       HIP_TRY(c->d_sw_in.reserve(st.total));
       uint8_t* dd = (uint8_t*)c->d_sw_in.ptr;
       HIP_TRY(hipMemcpyAsync(dd, h, st.total, hipMemcpyHostToDevice, c->stream));
@@ -124,7 +157,7 @@ int sw_stage_run(bpsw_ctx* c, const bpsw_opt_t* opt, int xtra, const SwStage& st
     memset(&pl, 0, sizeof pl);
     pl.packed = (uint64_t)(uintptr_t)dev.packed; pl.q_pool = (uint64_t)(uintptr_t)dev.q_pool; pl.t_pool = (uint64_t)(uintptr_t)dev.t_pool;
     pl.pac = (uint64_t)(uintptr_t)dev.pac; pl.l_pac = dev.l_pac; pl.out = (uint64_t)(uintptr_t)k_out;
-    pl.n_jobs = n; pl.bias = ring_bias;
+    pl.n_jobs = n; pl.bias = ring_bias; pl.pull = pull ? 1 : 0;
     for (int r = 0; r < 5; ++r) pl.mat_row[r] = sc.mat.row[r];
     pl.a = sc.a; pl.b = sc.b; pl.o_del = sc.o_del; pl.e_del = sc.e_del; pl.o_ins = sc.o_ins; pl.e_ins = sc.e_ins; pl.xtra = sc.xtra;
     // (the tripwire of bpsw_ring.cpp looks at the score and qb of every record)

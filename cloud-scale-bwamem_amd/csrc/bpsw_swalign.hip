@@ -25,6 +25,7 @@
 #include "bpsw_wave.h"
 
 #include "bpsw_ring_dev.h"
+#include "bpsw_ring_pull_core.h"
 
 #include "bpsw_diag_waves.h"
 BPSW_DIAG_WAVES_DEFINE(sw)
@@ -1302,6 +1303,62 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void swh_kernel(const SwJo
   BPSW_DIAG_WAVE_END_DUO(3, out, lane);
 }
 
+// The pull (bpsw_ring_pull_core.h): a resident worker stages the unit it took -- jobs first_job .. first_job + n_here of a batch whose
+// table and pools lie in the caller's pinned block -- in `slice`, LDS of its own, and rewrites `jobs` to a table of n_here jobs that
+// lives there.  Two PCIe round trips per unit, whatever the jobs then do: the records (one load; the ranges depend on them), then
+// every mate and window byte in one burst of 16-byte loads per lane, all issued before the first is waited for.  The burst is
+// global_load_lds_dwordx4: the bytes go from the link into LDS without passing through registers -- the resident kernels have none
+// to spare (what the ring loop keeps per lane across units is live here too) -- and the plan lays the chunks out in the order the
+// instruction writes them: chunk i at rp::kRecsBytes + 16 i, lane l of round r being chunk 64 r + l.  The job code that follows
+// reads LDS only, in both passes.  Only this wave writes the slice and only this wave reads it, through LDS: no cache lies between
+// the write and the read, `s_waitcnt vmcnt(0)` (the LDS-direct loads count there) is all the ordering there is.
+// false: the unit does not fit the slice (the host checks every unit with the same plan before it asks for the pull, so this is
+// a descriptor the host did not write) -- nothing has been changed, the jobs read the block in place.
+__device__ __forceinline__ bool swp_pull_unit(SwJobsDev& jobs, const int first_job, const int n_here, const int lane, uint8_t* slice,
+                                              const uint32_t slice_cap) {
+  typedef __attribute__((address_space(1))) void* gptr;
+  typedef __attribute__((address_space(3))) uint8_t* lptr;
+  uint32_t recw = 0;
+  if (lane < 8 * n_here) recw = jobs.packed[8 * (size_t)first_job + lane];
+  rp::Job J[rp::kMaxJobs];
+#pragma unroll
+  for (int k = 0; k < rp::kMaxJobs; ++k) {
+    const auto field = [&](const int f) { return (unsigned)__builtin_amdgcn_readlane((int)recw, 8 * k + f); };
+    J[k].q_off = ((unsigned long long)field(1) << 32) | field(0);
+    J[k].t_off = ((unsigned long long)field(3) << 32) | field(2);
+    J[k].q_len = field(4); J[k].t_len = field(5);
+  }
+  const bool windows = jobs.t_pool != nullptr;
+  const rp::Plan P = rp::plan(J, n_here, windows, slice_cap);
+  if (!P.fits) return false;
+  const lptr lds = (lptr)slice;
+  int ln = lane;
+  asm volatile("" : "+v"(ln));  // opaque: what depends on the lane alone is worked out here, per unit, not kept in registers across the ring loop
+#pragma unroll
+  for (int r = 0; r < rp::kRounds; ++r) {
+    bool w = false;
+    uint64_t src = 0;
+    uint32_t d = 0;
+    if (rp::chunk_at(P, (uint32_t)(ln + 64 * r), &w, &src, &d))  // (d == rp::kRecsBytes + 16 * (64 r + lane): where the instruction puts it)
+      __builtin_amdgcn_global_load_lds((gptr)(uintptr_t)((w ? jobs.t_pool : jobs.q_pool) + src), lds + rp::kRecsBytes + 1024 * r, 16, 0, 0);
+  }
+  uint32_t rw = recw;
+#pragma unroll
+  for (int k = 0; k < rp::kMaxJobs; ++k) {
+    rw = ln == 8 * k ? P.q_at[k] : ln == 8 * k + 1 ? 0u : rw;
+    if (windows) rw = ln == 8 * k + 2 ? P.t_at[k] : ln == 8 * k + 3 ? 0u : rw;
+  }
+  if (ln < 8 * n_here) ((uint32_t*)slice)[ln] = rw;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // ... and the records' LDS stores -> all lanes of the wave
+  __builtin_amdgcn_wave_barrier();
+  jobs.packed = (const uint32_t*)slice;
+  jobs.q_pool = slice;
+  if (windows) jobs.t_pool = slice;
+  jobs.n = n_here;
+  return true;
+}
+
 // The resident form (bpsw_ring.h): the same job pairs, taken one at a time from the descriptors task threads append to the device's
 // submission ring instead of from one launch's table.  Wavefront 0 of workgroup 0 is the ring's poller; every other wavefront is a
 // worker.  The row keys always stay in LDS: `key_rows_cap` rows per wave, fixed for the epoch -- the host sends a call whose longest
@@ -1310,11 +1367,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void swh_kernel(const SwJo
 // left and runs them as a quartet (swh_do_quartet); a last single unit runs swp_do_duo<3>.  Four waves per SIMD, 128 VGPRs: it holds five
 // columns per lane like class 5.  Without HALVES the kernels of classes 3 and 5 are what they were.
 template <int C, bool HALVES>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (C <= 3 && !HALVES) ? BPSW_SWP_WAVES : 4) void swp_resident_kernel(const RingArgs A, const int key_rows_cap) {
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (C <= 3 && !HALVES) ? BPSW_SWP_WAVES : 4) void swp_resident_kernel(const RingArgs A, const int key_rows_cap, const int slice_cap) {
   // (HALVES: two selector rows and two key rows per wave; the quartet's four mates share the pair's two buffers)
   __shared__ uint32_t tbuf_all[WAVES_PER_BLOCK][HALVES ? 2 * HW_TBUF : PK_TBUF + PK_G];
   __shared__ uint8_t mate_all[WAVES_PER_BLOCK][2][PK_MATE_LDS];
-  extern __shared__ uint32_t key_rows[];
+  extern __shared__ __attribute__((aligned(16))) uint32_t ring_rows[];  // the key rows of every wave, then the pull's slice of every wave
 #ifndef BPSW_RING_PRIO
 #define BPSW_RING_PRIO BPSW_SWP_PRIO
 #endif
@@ -1327,7 +1384,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (C <= 3 && !HALVES) ? BPSW_SW
   }
   uint32_t* tbuf = tbuf_all[wave];
   const int key_stride = key_rows_cap + PK_KEY_PAD;
-  uint32_t* keys = key_rows + (size_t)wave * (size_t)(HALVES ? 2 : 1) * (size_t)key_stride;
+  uint32_t* keys = ring_rows + (size_t)wave * (size_t)(HALVES ? 2 : 1) * (size_t)key_stride;
+  uint8_t* slice = (uint8_t*)(ring_rows + (size_t)WAVES_PER_BLOCK * (size_t)(HALVES ? 2 : 1) * (size_t)key_stride) + (size_t)wave * (size_t)slice_cap;
   RingWorker W;
   DuoDiag diag;
   for (;;) {
@@ -1351,10 +1409,26 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, (C <= 3 && !HALVES) ? BPSW_SW
     for (int r = 0; r < 5; ++r) sc.mat.row[r] = f64(22 + 2 * r);
     sc.a = (int)f32(32); sc.b = (int)f32(33); sc.o_del = (int)f32(34); sc.e_del = (int)f32(35);
     sc.o_ins = (int)f32(36); sc.e_ins = (int)f32(37); sc.xtra = (int)f32(38);
+    int duo = (int)unit;
+    if (f32(39) != 0u) {  // SwRingPayload::pull: the unit's jobs become a table of their own in the slice, pair 0 of it
+      const int first_job = 2 * duo;
+      if (swp_pull_unit(jobs, first_job, min(jobs.n - first_job, (HALVES && taken == 2u) ? 4 : 2), lane, slice, (uint32_t)slice_cap)) {
+        out += 7 * (size_t)first_job;
+        duo = 0;
+      }
+      // (wave-uniform either way: the table stays in scalar registers whatever is made of the branch above)
+      const auto uni_ptr = [](const void* p) {
+        const unsigned long long a = (unsigned long long)(uintptr_t)p;
+        return (uintptr_t)(((unsigned long long)(unsigned)uni((int)(a >> 32)) << 32) | (unsigned)uni((int)a));
+      };
+      jobs.packed = (const uint32_t*)uni_ptr(jobs.packed); jobs.q_pool = (const uint8_t*)uni_ptr(jobs.q_pool);
+      jobs.t_pool = (const uint8_t*)uni_ptr(jobs.t_pool); out = (int32_t*)uni_ptr(out);
+      jobs.n = uni(jobs.n); duo = uni(duo);
+    }
     if (HALVES && taken == 2u)
-      swh_do_quartet<true>(jobs, sc, bias, out, (int)unit, true, lane, tbuf, keys, key_stride, (uint8_t (*)[HW_MATE_LDS])mate_all[wave], diag);
+      swh_do_quartet<true>(jobs, sc, bias, out, duo, true, lane, tbuf, keys, key_stride, (uint8_t (*)[HW_MATE_LDS])mate_all[wave], diag);
     else
-      swp_do_duo<C>(jobs, sc, bias, out, (int)unit, lane, tbuf, keys, mate_all[wave], diag);
+      swp_do_duo<C>(jobs, sc, bias, out, duo, lane, tbuf, keys, mate_all[wave], diag);
     ring_unit_done(A, lane, W, word, taken);
   }
 }
@@ -1561,12 +1635,24 @@ int sw_ring_class(const SwScoring& sc, int max_qlen, int max_tlen, int* bias_out
   return c_class;
 }
 
+// LDS bytes a worker wave has for the unit it pulls (bpsw_ring_pull_core.h), fixed by the class like the key rows.
+static int swp_resident_slice_bytes(int c_class) { return (int)rp::slice_bytes(c_class == 5 ? 5 : 3, c_class == RING_CLASS_SW_HALVES); }
+static_assert(rp::kKeyRows5 == PK_KEYS_LDS_MAX, "the pull's slices are sized for the classes' key rows");
+// (a workgroup's LDS, static and dynamic, stays within 64 KB: the half-wave class is the one that comes close)
+static_assert(sizeof(uint32_t) * WAVES_PER_BLOCK * 2 * HW_TBUF + WAVES_PER_BLOCK * 2 * PK_MATE_LDS + sizeof(uint32_t) * WAVES_PER_BLOCK * 2 * (1024 + PK_KEY_PAD) +
+                      WAVES_PER_BLOCK * rp::kSliceHalves <= 65536 - 128, "half-wave resident kernel: key rows and slices fit a workgroup's LDS");
+static_assert(sizeof(uint32_t) * WAVES_PER_BLOCK * (PK_TBUF + PK_G) + WAVES_PER_BLOCK * 2 * PK_MATE_LDS + sizeof(uint32_t) * WAVES_PER_BLOCK * (PK_KEYS_LDS_MAX + PK_KEY_PAD) +
+                      WAVES_PER_BLOCK * rp::slice_bytes_pair(PK_KEYS_LDS_MAX) <= 65536 - 128, "class-5 resident kernel: key rows and slices fit a workgroup's LDS");
+static_assert(rp::kSliceHalves % 16 == 0 && rp::slice_bytes_pair(1024) % 16 == 0 && rp::slice_bytes_pair(PK_KEYS_LDS_MAX) % 16 == 0 && (PK_KEY_PAD % 4) == 0, "slices start at multiples of 16");
+
 hipError_t launch_swp_resident(int c_class, const RingArgs& A, int blocks, hipStream_t s) {
   const int cap = swp_resident_key_rows(c_class);
-  const size_t lds = sizeof(uint32_t) * WAVES_PER_BLOCK * (size_t)(cap + PK_KEY_PAD) * (c_class == RING_CLASS_SW_HALVES ? 2 : 1);  // a key row per half
-  if (c_class == 3) hipLaunchKernelGGL((swp_resident_kernel<3, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
-  else if (c_class == RING_CLASS_SW_HALVES) hipLaunchKernelGGL((swp_resident_kernel<3, true>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
-  else if (c_class == 5) hipLaunchKernelGGL((swp_resident_kernel<5, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap);
+  const int slice = swp_resident_slice_bytes(c_class);
+  const size_t lds = sizeof(uint32_t) * WAVES_PER_BLOCK * (size_t)(cap + PK_KEY_PAD) * (c_class == RING_CLASS_SW_HALVES ? 2 : 1)  // a key row per half
+                     + (size_t)WAVES_PER_BLOCK * (size_t)slice;
+  if (c_class == 3) hipLaunchKernelGGL((swp_resident_kernel<3, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap, slice);
+  else if (c_class == RING_CLASS_SW_HALVES) hipLaunchKernelGGL((swp_resident_kernel<3, true>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap, slice);
+  else if (c_class == 5) hipLaunchKernelGGL((swp_resident_kernel<5, false>), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds, s, A, cap, slice);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
