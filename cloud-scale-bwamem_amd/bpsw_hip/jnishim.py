@@ -95,8 +95,9 @@ def extend(fake, wire, n, partition=-1):
     return rc, out[: 10 * n], err.value.decode()
 
 
-def matesw(fake, g, partition=-1, pac=None):
-    opt = default_opt()
+def matesw(fake, g, partition=-1, pac=None, opt=None):
+    """mateSWJNI on group g; opt: the MemOptType the call carries (None: the defaults)"""
+    opt = default_opt() if opt is None else opt
     ints = np.array([opt.a, opt.b, opt.o_del, opt.e_del, opt.o_ins, opt.e_ins, opt.pen_unpaired, opt.pen_clip5, opt.pen_clip3,
                      opt.w, opt.zdrop, opt.T, opt.flag, opt.min_seed_len, opt.max_ins, opt.max_matesw], np.int32)
     mat = np.array(list(opt.mat), np.int8)
@@ -114,9 +115,9 @@ def matesw(fake, g, partition=-1, pac=None):
     return rc, out_cnt[: 2 * g.group_size], out[: total.value], frames.value, err.value.decode()
 
 
-def matesw_flat(fake, g, partition=-1, pac=None):
+def matesw_flat(fake, g, partition=-1, pac=None, opt=None):
     """the flat-array entry mateSWFlatJNI (round 4) on the same group; pac given: windows by coordinates, no window bytes"""
-    opt = default_opt()
+    opt = default_opt() if opt is None else opt
     ints = np.array([opt.a, opt.b, opt.o_del, opt.e_del, opt.o_ins, opt.e_ins, opt.pen_unpaired, opt.pen_clip5, opt.pen_clip3,
                      opt.w, opt.zdrop, opt.T, opt.flag, opt.min_seed_len, opt.max_ins, opt.max_matesw], np.int32)
     mat = np.array(list(opt.mat), np.int8)

@@ -207,6 +207,23 @@ def window_bases(bases: np.ndarray, l_pac: int, rb: int, re: int) -> np.ndarray:
     return bases[rb:re].copy()
 
 
+def rescue_window(pes, l_pac: int, anchor_rb: int, r: int, mate_len: int):
+    """getAlnRegRefJNI (MemSamPe.scala:1810-1878): the window (rb, re) in which orientation r of the anchor starting at anchor_rb looks
+    for a mate of mate_len bases, clamped to [0, 2 l_pac]; (-1, -1) when the orientation's statistics failed"""
+    lo, hi, failed = pes[r][0], pes[r][1], pes[r][2]
+    if failed:
+        return -1, -1
+    is_rev = (r >> 1) != (r & 1)
+    is_larger = (r >> 1) == 0
+    if not is_rev:
+        rb = anchor_rb + lo if is_larger else anchor_rb - hi
+        re = (anchor_rb + hi if is_larger else anchor_rb - lo) + mate_len
+    else:
+        rb = (anchor_rb + lo if is_larger else anchor_rb - hi) - mate_len
+        re = anchor_rb + hi if is_larger else anchor_rb - lo
+    return max(rb, 0), min(re, 2 * l_pac)
+
+
 def rescue_group(n_pairs: int, read_len: int = 150, seed: int = CONFIG_SEED_BASE + 3, l_pac: int = 46_709_983,
                  p_resc: float = 0.10, all_orientations: bool = False, sub_rate: float = 0.02, indel_rate: float = 0.002,
                  p_multi_anchor: float = 0.10, p_wrong_mate: float = 0.05, max_matesw: int = 100, pen_unpaired: int = 17,
@@ -249,19 +266,8 @@ def rescue_group(n_pairs: int, read_len: int = 150, seed: int = CONFIG_SEED_BASE
         qe = L if qe is None else qe
         return (rb, rb + (qe - qb), qb, qe, score, score, 0, 0, 0, 100, (qe - qb) // 2, -1, int(rng.integers(0, 2 ** 62)))
 
-    def window_for(anchor_rb, r, mate_len):  # getAlnRegRefJNI, MemSamPe.scala:1810-1878
-        lo, hi, failed = pes[r][0], pes[r][1], pes[r][2]
-        if failed:
-            return -1, -1
-        is_rev = (r >> 1) != (r & 1)
-        is_larger = (r >> 1) == 0
-        if not is_rev:
-            rb = anchor_rb + lo if is_larger else anchor_rb - hi
-            re = (anchor_rb + hi if is_larger else anchor_rb - lo) + mate_len
-        else:
-            rb = (anchor_rb + lo if is_larger else anchor_rb - hi) - mate_len
-            re = anchor_rb + hi if is_larger else anchor_rb - lo
-        return max(rb, 0), min(re, 2 * l_pac)
+    def window_for(anchor_rb, r, mate_len):
+        return rescue_window(pes, l_pac, anchor_rb, r, mate_len)
 
     for k in range(n_pairs):
         P = int(rng.integers(2000, l_pac - 3000))

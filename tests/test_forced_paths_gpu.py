@@ -30,5 +30,5 @@ def test_extension_suites_with_the_sift_kernel_on_every_batch():
 
 
 def test_boundary_1_suites_with_every_sw_batch_on_the_ring():
-    _forced(["test_swalign_gpu.py", "test_rescue_gpu.py", "test_tail_gpu.py", "test_ring_gpu.py", "test_jni_shim.py", "test_concurrency_gpu.py",
+    _forced(["test_swalign_gpu.py", "test_rescue_gpu.py", "test_rescue_plan_gpu.py", "test_tail_gpu.py", "test_ring_gpu.py", "test_jni_shim.py", "test_concurrency_gpu.py",
              "test_host_path_gpu.py"], extra_k="not large_batch")

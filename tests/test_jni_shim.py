@@ -118,6 +118,35 @@ def test_matesw_lazy_path_steps_aside_for_arrays_in_another_order(fake, ctx, mon
     assert np.array_equal(cnt, g0.reg_cnt) and np.array_equal(regs["rb"], g0.regs["rb"]) and np.array_equal(regs["hash"], g0.regs["hash"])
 
 
+def _shim_case_names():
+    import rescue_cases
+    return [n for n in rescue_cases.CASES if n[:2] in ("A_", "B_", "C_", "F_")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", _shim_case_names())
+def test_matesw_lazy_path_selects_a_superset_at_the_limits(fake, ctx, name):
+    """mate_sw_lazy (csrc/bpsw_jni.cpp) unmarshals only the pairs it thinks may need a job: the fifth copy of the plan's decision.  The
+    option, limit, edge-of-the-reference and odd-mate cases of tests/rescue_cases.py through both entries, with the case's own
+    options, against the C ABI: a pair the shim left out although the library would touch it comes back unchanged and differs.
+    C flavour only: the flavour is an environment variable the shim reads per call."""
+    import rescue_cases
+    g, o, _ = rescue_cases.CASES[name]
+    opt = bpsw_hip.default_opt()
+    for k, v in o.items():
+        setattr(opt, k, v)
+    lib = bpsw_hip.load_library()
+    lib.bpsw_jni_last_mate_path.restype = C.c_int
+    want_cnt, want = ctx.matesw_group(opt, g)
+    rc, cnt, regs, frames, msg = jnishim.matesw(fake, g, partition=2, opt=opt)
+    assert rc == 0 and frames == 0, msg
+    assert lib.bpsw_jni_last_mate_path() == 1                     # the lazy path took the call
+    assert np.array_equal(cnt, want_cnt); region_fields_equal(regs, want); assert np.array_equal(regs["hash"], want["hash"])
+    rc, cnt, regs, msg = jnishim.matesw_flat(fake, g, partition=2, opt=opt)
+    assert rc == 0, msg
+    assert np.array_equal(cnt, want_cnt); region_fields_equal(regs, want); assert np.array_equal(regs["hash"], want["hash"])
+
+
 @pytest.mark.gpu
 def test_matesw_through_jni_with_reference_on_device(fake, ctx):
     """SURVEY.md 8f.2 through the JNI surface: loadPacJNI, then RefSWType objects that carry (rBeg, rEnd) only"""
