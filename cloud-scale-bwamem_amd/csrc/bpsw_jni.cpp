@@ -34,7 +34,7 @@
 #include <vector>
 
 #include "bpsw.h"
-#include "bpsw_rescue_skip.h"
+#include "bpsw_rescue_core.h"
 #include "jni_min.h"
 
 namespace {
@@ -406,7 +406,7 @@ void decode_pes(const double* v, bpsw_pestat_t pes[4]) {
 // paired, need no SW at all and come back exactly as they went in.  So: (1) one light pass over MateSWType[] reads what the skip test
 // needs of a region (its end, rBeg, score: 6 JNI calls instead of 18) and checks that the array is in (pair, end, rank) order with
 // regIdx = rank, as memSamPeGroupJNIPrepare builds it (MemSamPe.scala:1962-1990); (2) the skip test of the library itself
-// (bpsw_rescue_skip.h) selects the pairs that may need a job; (3) only THEIR regions (all fields), mates and windows are unmarshalled,
+// (bpsw_rescue_core.h) selects the pairs that may need a job; (3) only THEIR regions (all fields), mates and windows are unmarshalled,
 // into a group of their own, and bpsw_matesw_group runs on that; (4) the result array holds new objects for those pairs and, for every
 // other end, the caller's own MateSWType objects -- they already carry (readIdx, pairIdx, regIdx = rank) and the unchanged region.
 // The Scala caller rebuilds its lists from the returned array and drops the input arrays (MemSamPe.scala:2010-2044), so sharing the
@@ -475,29 +475,12 @@ int mate_sw_lazy(JNIEnv* env, const MateIds* ids, const bpsw_opt_t& opt, const b
   L.touched.clear();
   L.is_touched.assign((size_t)groupSize + 1, 0);
   if ((opt.flag & 0x20) == 0) {  // MEM_F_NO_RESCUE
-    int32_t low[4], high[4];
-    int failed_mask = 0;
-    for (int r = 0; r < 4; ++r) { low[r] = g0.pes[r].low; high[r] = g0.pes[r].high; failed_mask |= (g0.pes[r].failed ? 1 : 0) << r; }
-    const bool scala = scala_rescue();
+    const bpsw::RescueRules rules = bpsw::rescue_rules(opt, g0.pes, g0.l_pac, scala_rescue() ? BPSW_RESCUE_SCALA : BPSW_RESCUE_C);
     for (jint k = 0; k < groupSize; ++k) {
-      bool touched = false;
-      for (int i = 0; i < 2 && !touched; ++i) {
-        const size_t e = 2 * (size_t)k + (size_t)i, mate = e ^ 1;
-        if (L.reg_cnt[e] == 0 || L.ref_cnt[e] == 0) continue;
-        const LightReg* init = L.light.data() + L.reg_at[e];
-        const LightReg* minit = L.light.data() + L.reg_at[mate];
-        const int thr = init[0].score - opt.pen_unpaired;
-        int j = 0;
-        for (int ai = 0; ai < L.reg_cnt[e] && !touched; ++ai) {
-          if (!(init[ai].score >= thr)) continue;
-          if (j >= opt.max_matesw || j >= L.ref_cnt[e]) break;
-          int skip[4];
-          bpsw::rescue_skip_flags(g0.l_pac, low, high, failed_mask, scala, init[ai].rb, &minit->rb, sizeof(LightReg), (size_t)L.reg_cnt[mate], skip);
-          if (skip[0] + skip[1] + skip[2] + skip[3] != 4) touched = true;
-          ++j;
-        }
+      const size_t e = 2 * (size_t)k;
+      if (bpsw::rescue_pair_may_need_job(rules, L.light.data() + L.reg_at[e], L.light.data() + L.reg_at[e + 1], &L.reg_cnt[e], &L.ref_cnt[e])) {
+        L.touched.push_back(k); L.is_touched[(size_t)k] = 1;
       }
-      if (touched) { L.touched.push_back(k); L.is_touched[(size_t)k] = 1; }
     }
   }
   const size_t nt = L.touched.size();

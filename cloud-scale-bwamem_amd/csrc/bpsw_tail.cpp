@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "bpsw_rescue_core.h"    // mem_infer_dir, the anchors of an end and the orientation numbers, as the rescue itself reads them
 #include "bpsw_tail_internal.h"  // (with bpsw_internal.h) what bpsw_sam_se.hip and bpsw_sam_pe.hip share with this file
 
 using namespace bpsw;
@@ -240,13 +241,6 @@ int approx_mapq(const bpsw_opt_t& o, const bpsw_tail_opt_t& t, const bpsw_alnreg
 }
 
 inline int raw_mapq(int diff, int a) { return (int)(6.02 * diff / a + .499); }
-
-int infer_dir(long long l_pac, long long b1, long long b2, long long* dist) {  // native/bwamem_pair.c:27-34, PE:1575-1594
-  const bool r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-  const long long p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-  *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-  return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
 
 struct PairScore { int score, sub, n_sub, z[2]; };
 
@@ -874,8 +868,8 @@ int pe_lines(bpsw_ctx* c, const SwScoring& sc, const bpsw_opt_t* opt, const bpsw
       h[i] = make_aln(o, t, jb >= 0 ? &a[i][0] : nullptr, jb >= 0 ? &res[(size_t)jb] : nullptr, R);
     }
     if (!(o.flag & BPSW_MEM_F_NOPAIRING) && h[0].a.rid == h[1].a.rid && h[0].a.rid >= 0) {  // PE:1571-1594
-      long long dist;
-      const int d = infer_dir(bns.l_pac, a[0][0].rb, a[1][0].rb, &dist);
+      int64_t dist;
+      const int d = rescue_infer_dir(bns.l_pac, a[0][0].rb, a[1][0].rb, &dist);  // PE:1575-1594
       if (!g->pes[d].failed && dist >= g->pes[d].low && dist <= g->pes[d].high) extra_flag |= 2;
     }
     for (int i = 0; i < 2; ++i) {
@@ -1024,9 +1018,9 @@ int bpsw_pe_stat(const bpsw_opt_t* opt, const bpsw_tail_opt_t* topt, int64_t l_p
     at += (size_t)n0 + (size_t)n1;
     if (n0 == 0 || n1 == 0) continue;
     if (cal_sub(r0, n0) > 0.8 * r0[0].score || cal_sub(r1, n1) > 0.8 * r1[0].score) continue;  // MIN_RATIO
-    long long is;
-    const int dir = infer_dir((long long)l_pac, r0[0].rb, r1[0].rb, &is);
-    if (topt->flavour == BPSW_TAIL_SCALA) is = (long long)(int32_t)is;  // `var dist: Int`, PE:148
+    int64_t is;
+    const int dir = rescue_infer_dir(l_pac, r0[0].rb, r1[0].rb, &is);
+    if (topt->flavour == BPSW_TAIL_SCALA) is = (int64_t)(int32_t)is;  // `var dist: Int`, PE:148
     if (is > 0 && is <= opt->max_ins) isize[dir].push_back(is);
   }
   memset(pes, 0, 4 * sizeof(bpsw_pestat_t));
@@ -1070,6 +1064,7 @@ int bpsw::pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const
   const long long l_pac = (long long)bpsw_ref_length(c);
   if (l_pac <= 0) return fail(BPSW_ERR_ARG, w + ": no reference loaded on this device (bpsw_ref_load)");
   // ---- prepare: anchors and their windows ----------------------------------------------------------------------------------
+  const RescueRules rules = rescue_rules(*opt, g->pes, l_pac, rescue_mode);
   std::vector<int32_t> ref_cnt((size_t)(2 * G), 0);
   std::vector<int64_t> ref_rb, ref_re;
   size_t at = 0, n_in = 0;
@@ -1079,12 +1074,11 @@ int bpsw::pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const
     const bpsw_alnreg_t* a = g->regs + at;
     const int mate_len = g->read_len[e ^ 1];
     int cnt = 0;
-    for (int j = 0; j < n && cnt < opt->max_matesw; ++j) {
-      if (!(a[j].score >= a[0].score - opt->pen_unpaired)) continue;  // PE:1944-1947
+    rescue_walk_anchors(rules, a, n, kRescueNoCap, [&](int, int j) {  // PE:1944-1947; no cap by window rows: they are produced here
       for (int r = 0; r < 4; ++r) {                                    // PE:1834-1868
         long long rb = -1, re = -1;
         if (!g->pes[r].failed) {
-          const bool is_rev = (r >> 1) != (r & 1), is_larger = !(r >> 1);
+          const bool is_rev = rescue_is_rev(r), is_larger = rescue_is_larger(r);
           const long long lo = g->pes[r].low, hi = g->pes[r].high;
           if (!is_rev) {
             rb = is_larger ? a[j].rb + lo : a[j].rb - hi;
@@ -1099,7 +1093,8 @@ int bpsw::pe_rescue(bpsw_ctx_t* c, const char* who, const bpsw_opt_t* opt, const
         ref_rb.push_back(rb); ref_re.push_back(re);
       }
       ++cnt;
-    }
+      return true;
+    });
     ref_cnt[(size_t)e] = cnt;
     at += (size_t)n; n_in += (size_t)n;
   }

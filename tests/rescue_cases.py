@@ -1,5 +1,7 @@
-"""Hand-built mate-rescue groups for the host layer of boundary 1 (csrc/bpsw_rescue.cpp, csrc/bpsw_rescue_skip.h): the plan (fast
-path, lean speculation), the replay and the output assembly, at the pairs those shortcuts name.  numpy only: no GPU, no library.
+"""Hand-built mate-rescue groups for the host layer of boundary 1 (csrc/bpsw_rescue.cpp, and the rules it shares with the JNI shim and
+worker2's prepare step in csrc/bpsw_rescue_core.h): the plan (fast path, lean speculation), the replay and the output assembly, at the
+pairs those shortcuts name.  numpy only: no GPU, no library.  The models at the end of this file (infer_dir, first_round_jobs) are
+statements of their own and stay so: they are what the header is held to (tests/test_rescue_core_host.py).
 
 A pair is a dict
     reads: [end 0, end 1]           uint8 codes 0..4

@@ -126,7 +126,8 @@ def _shim_case_names():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", _shim_case_names())
 def test_matesw_lazy_path_selects_a_superset_at_the_limits(fake, ctx, name):
-    """mate_sw_lazy (csrc/bpsw_jni.cpp) unmarshals only the pairs it thinks may need a job: the fifth copy of the plan's decision.  The
+    """mate_sw_lazy (csrc/bpsw_jni.cpp) unmarshals only the pairs it thinks may need a job: the plan's own walk (rescue_pair_may_need_job,
+    csrc/bpsw_rescue_core.h), blind to windows and mate lengths, over the 16-byte records of its light pass.  The
     option, limit, edge-of-the-reference and odd-mate cases of tests/rescue_cases.py through both entries, with the case's own
     options, against the C ABI: a pair the shim left out although the library would touch it comes back unchanged and differs.
     C flavour only: the flavour is an environment variable the shim reads per call."""

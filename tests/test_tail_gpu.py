@@ -146,6 +146,52 @@ def test_worker2_in_one_call_vs_oracle_pipeline(ctx, orc, rescue_mode, flavour, 
     assert regs.tobytes() == want_regs.tobytes()
 
 
+@pytest.fixture(scope="module")
+def binding_group(orc):
+    """100 pairs of 2 x 150 bp (C flavours) on which the anchor rules bind, by the oracle alone and before anything goes to a device:
+    seven ends in ten carry too many errors for a seed, so many best hits are weak enough for a second locus or a decoy to lie within
+    pen_unpaired of them.  Returns (pac, bases, group, n_sw of the sequential walk per (max_matesw, pen_unpaired))."""
+    pac, bases, g = synthetic_group_with_bases(orc, 100, 9205, zdrop_mode=po.ZDROP_BWA, dedup_mode=po.RESCUE_C, p_hard=0.7, p_unmappable=0.03,
+                                               sub_rate=0.02, indel_rate=0.004)
+    n_sw = {}
+    for m, p in [(1, 17), (2, 17), (100, 17), (100, 0)]:
+        oopt = orc.default_opt()
+        oopt.max_matesw, oopt.pen_unpaired = m, p
+        n_sw[m, p] = orc.matesw_group(oopt, rescue_group_of(g, bases, oopt), po.RESCUE_C)[2]
+    assert orc.default_opt().max_matesw == 100 and orc.default_opt().pen_unpaired == 17
+    assert len({n_sw[1, 17], n_sw[2, 17], n_sw[100, 17]}) == 3, n_sw      # the cap binds at 1 and at 2
+    assert n_sw[100, 0] != n_sw[100, 17], n_sw                             # the threshold binds
+    return pac, bases, g, n_sw
+
+
+@pytest.mark.parametrize("pen_unpaired", [0, 3, -1])
+@pytest.mark.parametrize("max_matesw", [0, 1, 2])
+def test_worker2_anchor_selection_under_other_options_vs_oracle_pipeline(ctx, orc, binding_group, max_matesw, pen_unpaired):
+    """pe_rescue's anchor selection (the anchor walk of csrc/bpsw_rescue_core.h, without a cap by window rows: it produces them) where
+    max_matesw and pen_unpaired are not the defaults, against the oracle's pipeline with the windows cut by tests/tail_util.py.  The
+    assertions of test_worker2_in_one_call_vs_oracle_pipeline, except that the walk runs no SW at all where the options leave no
+    anchor (max_matesw 0; pen_unpaired -1, under which no hit passes its own threshold)."""
+    pac, bases, g, _ = binding_group
+    _load_ref(ctx, pac, g)
+    opt, oopt = bpsw_hip.default_opt(), orc.default_opt()
+    for o in (opt, oopt):
+        o.max_matesw, o.pen_unpaired = max_matesw, pen_unpaired
+    rg = rescue_group_of(g, bases, oopt)
+    cnt_o, regs_o, n_sw, _ = orc.matesw_group(oopt, rg, po.RESCUE_C)
+    if max_matesw == 0 or pen_unpaired < 0:
+        assert n_sw == 0 and int(rg.ref_cnt.sum()) == 0
+    else:
+        assert n_sw > 10 and regs_o.shape[0] > g.regs.shape[0]          # the rescue really added regions
+    g2 = copy.copy(g)
+    g2.reg_cnt, g2.regs = cnt_o, regs_o
+    want, want_regs, _ = orc.sam_pe_batch(oopt, orc.default_tail_opt(), pac, g2, flavour=bpsw_hip.TAIL_C)
+    got, cnt, regs = ctx.worker2_batch(opt, bpsw_hip.default_tail_opt(bpsw_hip.TAIL_C), g, bpsw_hip.RESCUE_C)
+    assert np.array_equal(cnt, cnt_o)
+    bad = [i for i in range(len(want)) if want[i] != got[i]]
+    assert not bad, (len(bad), want[bad[0]], got[bad[0]])
+    assert regs.tobytes() == want_regs.tobytes()
+
+
 def test_worker2_in_one_call_vs_reference_mem_sam_pe(ctx, orc, ref):
     """The same call against the reference's own mem_sam_pe INCLUDING its rescue (mem_matesw over the packed reference).
     Everything must agree except what derives from ksw_align2's second-best score (the SSE2 kernel inflates
