@@ -547,13 +547,27 @@ def _seeded_read(rng, ref_bases, l_pac, rb0, L, es, ei, min_seed):
     return read, seeds
 
 
+def _pinned(seq, anchor_rev, k, drawn, rev_shift):
+    """entry k (cycled) of a caller's position list, or the drawn position where there is no list or the entry is None"""
+    if not seq or seq[k % len(seq)] is None:
+        return drawn
+    rev = bool(anchor_rev) and bool(anchor_rev[k % len(anchor_rev)])
+    return int(seq[k % len(seq)]) + (rev_shift if rev else 0)
+
+
 def tail_pairs(n_pairs: int, ref_bases: np.ndarray, ann_off, ann_len, dups=(), read_len: int = 150, sub_rate: float = 0.01,
                indel_rate: float = 0.002, p_unmappable: float = 0.04, p_far: float = 0.05, p_span: float = 0.03,
                p_dup: float = 0.15, p_decoy: float = 0.15, p_clip: float = 0.1, p_hard: float = 0.0, min_seed: int = 19,
-               seed: int = CONFIG_SEED_BASE + 11):
+               seed: int = CONFIG_SEED_BASE + 11, positions=None, mate_positions=None, anchor_rev=None, chimeric=None):
     """FR pairs (insert ~ N(400, 50^2)) with the seed chains of both ends, plus names and qualities: what worker2's tail
     needs once chains have been turned into regions (memChainToAln + memSortAndDedup) and the rescue has run.
-    Returns (ChainBatchSoA over the 2n reads in (pair, end) order, names list, qual_pool aligned with read_pool, pes)."""
+    Returns (ChainBatchSoA over the 2n reads in (pair, end) order, names list, qual_pool aligned with read_pool, pes).
+
+    positions / mate_positions pin pair k's fragment start P and its improper mate's P2 (forward coordinates) to entry
+    k % len of the sequence; an entry of None leaves the random draw.  Where anchor_rev's entry is true the given position is
+    the forward start of the REVERSE-strand end instead (P, and P2 alike, = position + read_len - insert), so that the same locus
+    is read on both strands.  chimeric's entry, (a, b) in doubled coordinates, makes end 0 of the pair a read whose halves are copied
+    from a and from b, one chain each (supplementary lines with SA:Z).  All four absent: the random stream is unchanged."""
     from . import ChainBatchSoA
     rng = np.random.default_rng(seed)
     L = read_len
@@ -593,14 +607,24 @@ def tail_pairs(n_pairs: int, ref_bases: np.ndarray, ann_off, ann_len, dups=(), r
         else:
             c = int(rng.integers(0, len(ann_off)))
             P = int(ann_off[c]) + int(rng.integers(0, max(1, int(ann_len[c]) - ins)))
+        P = _pinned(positions, anchor_rev, k, P, L - ins)
         P = max(0, min(P, l_pac - ins - 70))
         P2 = P
         if rng.random() < p_far:                 # improper pair: the mate comes from somewhere else
             P2 = int(rng.integers(0, l_pac - ins - 70))
+        P2 = max(0, min(_pinned(mate_positions, anchor_rev, k, P2, L - ins), l_pac - ins - 70))
         fwd_rb = P                               # forward-strand end starts at P
         rev_rb = 2 * l_pac - (P2 + ins)          # reverse-strand end, doubled coordinates
         ends = [fwd_rb, rev_rb] if rng.random() < 0.5 else [rev_rb, fwd_rb]
+        chim = chimeric[k % len(chimeric)] if chimeric else None
         for i in range(2):
+            if chim is not None and i == 0:      # two exact halves from two loci, a chain each
+                h = L // 2
+                read = np.concatenate([window_bases(ref_bases, l_pac, chim[0], chim[0] + h),
+                                       window_bases(ref_bases, l_pac, chim[1], chim[1] + L - h)])
+                assert len(read) == L, chim
+                add_read(read, [[(int(chim[0]), 0, h)], [(int(chim[1]), h, L - h)]])
+                continue
             if rng.random() < p_unmappable:
                 add_read(rng.integers(0, 4, L).astype(np.uint8), [])
                 continue

@@ -16,6 +16,22 @@ def test_reg2bin_literals():
     assert bp.reg2bin(0, 1 << 29) == 0
 
 
+@pytest.mark.parametrize("beg,end,want", [
+    # two bases either side of the 9th edge of a level lie in bin 1 of the level above: offsets 4681 585 73 9 1 0 (specification 5.3)
+    ((9 << 14) - 1, (9 << 14) + 1, 585 + 1),       # 16 kb edge 9 is inside 128 kb bin 1
+    ((9 << 17) - 1, (9 << 17) + 1, 73 + 1),        # 128 kb edge 9 is inside 1 Mb bin 1
+    ((9 << 20) - 1, (9 << 20) + 1, 9 + 1),         # 1 Mb edge 9 is inside 8 Mb bin 1
+    ((9 << 23) - 1, (9 << 23) + 1, 1 + 1),         # 8 Mb edge 9 is inside 64 Mb bin 1
+    ((1 << 26) - 1, (1 << 26) + 1, 0),             # across a 64 Mb edge: bin 0
+    (1 << 29, (1 << 29) + 1, 4681 + 32768),        # 37 449: beyond the 512 Mb the scheme was made for, the formula goes on
+    (1 << 30, (1 << 30) + 1, 4681 + 65536),        # 70 217: more than the record's 16-bit field holds
+])
+def test_reg2bin_one_literal_per_level_and_beyond_512_mb(beg, end, want):
+    assert want in (586, 74, 10, 2, 0, 37449, 70217)
+    assert bp.reg2bin(beg, end) == want
+    assert want != 70217 or want & 0xffff == 4681    # what the field keeps of it
+
+
 @pytest.mark.parametrize("v,want", [(0, b"NMC\x00"), (255, b"NMC\xff"), (256, b"NMS\x00\x01"), (65535, b"NMS\xff\xff"),
                                     (65536, b"NMI\x00\x00\x01\x00"), (-1, b"NMc\xff"), (-128, b"NMc\x80"), (-129, b"NMs\x7f\xff"),
                                     (-32769, b"NMi\xff\x7f\xff\xff")])
