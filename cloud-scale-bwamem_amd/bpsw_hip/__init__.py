@@ -43,7 +43,7 @@ ABI_SYMBOLS = [
     "bpsw_sam_pe_batch_ex", "bpsw_align_pe_batch", "bpsw_last_sam_pe_times",
     "bpsw_fastq_parse", "bpsw_align_fastq_se", "bpsw_align_fastq_pe", "bpsw_last_fastq_times",
     "bpsw_bam_se_batch", "bpsw_bam_pe_batch", "bpsw_align_bam_se_batch", "bpsw_align_bam_pe_batch", "bpsw_align_fastq_bam_se", "bpsw_align_fastq_bam_pe",
-    "bpsw_sam_header", "bpsw_bam_header", "bpsw_bam_eof", "bpsw_bam_set_block_payload", "bpsw_last_bam_times",
+    "bpsw_sam_header", "bpsw_bam_header", "bpsw_bam_eof", "bpsw_bam_set_block_payload", "bpsw_last_bam_times", "bpsw_last_bam_deflate_times",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -307,6 +307,7 @@ def _bind_seeding(lib):
         "bpsw_bam_eof": ([C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
         "bpsw_bam_set_block_payload": ([C.c_int], C.c_int),
         "bpsw_last_bam_times": ([C.c_void_p], None),
+        "bpsw_last_bam_deflate_times": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -1276,6 +1277,7 @@ def last_fastq_times():
 
 # ---- alignments out as BAM (bpsw_bam.hip) -------------------------------------------------------------------------------------------
 BGZF_PAYLOAD = 65280   # the payload bytes of a BGZF block unless bam_set_block_payload says otherwise
+BAM_DEFLATE = 16       # flags of the six BAM entries: every block a dynamic-Huffman deflate block made on the device (BPSW_BAM_DEFLATE)
 
 
 def _bytes_call(lib, what, call, cap=None, start=1 << 16):
@@ -1395,6 +1397,14 @@ def last_bam_times():
     """(bam_len_kernel, bam_write_kernel, bgzf_frame_kernel, line table, round trip) in ms of this thread's last BAM entry"""
     ms = (C.c_double * 5)()
     load_library().bpsw_last_bam_times(ms)
+    return tuple(ms)
+
+
+def last_bam_deflate_times():
+    """(bgzf_deflate_kernel, bgzf_pack_kernel, the size table's round trip, the copy of the packed blocks) in ms of this thread's last
+    BAM entry; zeros when it ran without BAM_DEFLATE"""
+    ms = (C.c_double * 4)()
+    load_library().bpsw_last_bam_deflate_times(ms)
     return tuple(ms)
 
 

@@ -235,5 +235,14 @@ BPSW_SAM_HD uint8_t bgzf_head_byte(int k, uint32_t n) {
 // byte k (0 .. kBgzfTail - 1) behind it
 BPSW_SAM_HD uint8_t bgzf_tail_byte(int k, uint32_t crc, uint32_t n) { return (uint8_t)((k < 4 ? crc : n) >> (8 * (k & 3))); }
 
+// ---- the same around a compressed block (bpsw_deflate_core.h): the 18 bytes of the BGZF header in front of `dbytes` deflate bytes ----------
+// (what follows them is bgzf_tail_byte's: the CRC and the size are the payload's, however it is coded)
+constexpr int kBgzfDeflateHead = 18;
+BPSW_SAM_HD uint8_t bgzf_deflate_head_byte(int k, uint32_t dbytes) {
+  if (k < 8) return (uint8_t)(0x0000000004088b1fULL >> (8 * k));
+  if (k < 16) return (uint8_t)(0x000243420006ff00ULL >> (8 * (k - 8)));
+  return (uint8_t)((kBgzfDeflateHead + dbytes + kBgzfTail - 1) >> (8 * (k - 16)));
+}
+
 }  // namespace bamcore
 }  // namespace bpsw

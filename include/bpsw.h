@@ -734,7 +734,16 @@ void bpsw_last_fastq_times(double ms[5]);
  * small (nothing is written then: the size is known before the records are); an empty batch is *out_needed == 0.  flags must be 0
  * (BPSW_ERR_ARG otherwise); the FASTQ twins keep fastq_flags, and w1_flags pass through.  A read name of more than 254 bytes cannot be
  * a BAM record: BPSW_ERR_LIMIT, nothing written.  Everything else -- arguments, refusals, out_regs, out_pes, n_reads, consumed,
- * bpsw_last_tail_times -- is the twin's.  Not here: deflate compression, sorting, an index. */
+ * bpsw_last_tail_times -- is the twin's.  Not here: sorting, an index.
+ *
+ * flags = BPSW_BAM_DEFLATE (all six entries; any other bit is still BPSW_ERR_ARG): every member holds one dynamic-Huffman deflate block
+ * with LZ77 matches (RFC 1951, BTYPE 10), made on the device by one wavefront a block (csrc/bpsw_deflate_core.h), unless that would not
+ * be smaller than the stored form, which the member then keeps: no member grows.  The records, the cuts, the CRC-32 and ISIZE are the
+ * same, and the bytes are a function of the stream and P alone.  The size is known only after compression: with cap too small (or out
+ * NULL) the call still compresses, writes nothing and returns BPSW_ERR_CAPACITY with *out_needed the exact size, at which a repeat
+ * succeeds.  A caller who wants one call sizes by the stored form, S + 31 ceil(S / P) -- what the same call with flags == 0 reports --
+ * which the compressed output never exceeds.  Outputs with and without the flag concatenate; the header and the EOF block are as before. */
+#define BPSW_BAM_DEFLATE 16 /* flags: compress every BGZF block on the device; default: stored blocks */
 int bpsw_bam_se_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_tail_opt_t *topt, const bpsw_se_reads_t *reads, int flags, char *out,
                       size_t cap, size_t *out_needed, bpsw_alnreg_t *out_regs);
 int bpsw_bam_pe_batch(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_tail_opt_t *topt, const bpsw_pairs_t *g, int flags, char *out,
@@ -770,6 +779,10 @@ int bpsw_bam_set_block_payload(int bytes);
 /* Diagnostics, of the calling thread's most recent call of a BAM entry (ms): bam_len_kernel, bam_write_kernel, bgzf_frame_kernel,
  * building and staging the line table, the round trip of the three kernels with the copies. */
 void bpsw_last_bam_times(double ms[5]);
+/* ... and of what BPSW_BAM_DEFLATE adds (ms; zeros after a call without it): bgzf_deflate_kernel, bgzf_pack_kernel (0 when the capacity
+ * was refused), the blocks' size table back to the host with its sum and the offsets' way out, the copy of the packed blocks.  With the
+ * flag, slot 2 of bpsw_last_bam_times (bgzf_frame_kernel) is 0. */
+void bpsw_last_bam_deflate_times(double ms[4]);
 
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {
