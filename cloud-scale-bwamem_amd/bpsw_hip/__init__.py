@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "bpsw_fastq_parse", "bpsw_align_fastq_se", "bpsw_align_fastq_pe", "bpsw_last_fastq_times",
     "bpsw_bam_se_batch", "bpsw_bam_pe_batch", "bpsw_align_bam_se_batch", "bpsw_align_bam_pe_batch", "bpsw_align_fastq_bam_se", "bpsw_align_fastq_bam_pe",
     "bpsw_sam_header", "bpsw_bam_header", "bpsw_bam_eof", "bpsw_bam_set_block_payload", "bpsw_last_bam_times", "bpsw_last_bam_deflate_times",
+    "bpsw_bgzf_inflate", "bpsw_last_bgzf_times", "bpsw_fastq_bgzf_parse", "bpsw_align_fastq_bgzf_se", "bpsw_align_fastq_bgzf_pe",
+    "bpsw_align_fastq_bgzf_bam_se", "bpsw_align_fastq_bgzf_bam_pe",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -308,6 +310,25 @@ def _bind_seeding(lib):
         "bpsw_bam_set_block_payload": ([C.c_int], C.c_int),
         "bpsw_last_bam_times": ([C.c_void_p], None),
         "bpsw_last_bam_deflate_times": ([C.c_void_p], None),
+        # FASTQ in as BGZF (bpsw_bgzf_in.hip, bpsw_fastq.hip): the FASTQ entries' lists with an int32 skip behind each bytes
+        "bpsw_bgzf_inflate": ([C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_last_bgzf_times": ([C.c_void_p], None),
+        "bpsw_fastq_bgzf_parse": ([C.c_void_p, C.c_char_p, C.c_size_t, C.c_int32, C.c_char_p, C.c_size_t, C.c_int32, C.c_int, C.c_int64, C.c_size_t,
+                                   C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                   C.c_void_p], C.c_int),
+        "bpsw_align_fastq_bgzf_se": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int32, C.c_int, C.c_int64,
+                                      C.c_int32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_int64), C.c_void_p], C.c_int),
+        "bpsw_align_fastq_bgzf_pe": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int32, C.c_char_p, C.c_size_t,
+                                      C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_int64, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p], C.c_int),
+        "bpsw_align_fastq_bgzf_bam_se": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int32, C.c_int, C.c_int64,
+                                          C.c_int32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64),
+                                          C.c_void_p], C.c_int),
+        "bpsw_align_fastq_bgzf_bam_pe": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int32, C.c_char_p,
+                                          C.c_size_t, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -1363,6 +1384,146 @@ def _ctx_align_fastq_bam_pe(self, opt: Opt, sopt, topt: "TailOpt", text1: bytes,
             int(n.value), (int(consumed[0]), int(consumed[1])))
 
 
+# ---- FASTQ in as BGZF (bpsw_bgzf_in.hip, bpsw_fastq.hip) ------------------------------------------------------------------------------
+BGZF_FINAL, BGZF_HOST = 1, 2   # BPSW_BGZF_*
+
+
+class BgzfError(BpswError):
+    """a failed bpsw_bgzf_inflate: rc is the library's code, needed / n_blocks / consumed what it set"""
+
+    def __init__(self, msg, rc, needed=0, n_blocks=0, consumed=0):
+        super().__init__(msg)
+        self.rc, self.needed, self.n_blocks, self.consumed = rc, needed, n_blocks, consumed
+
+
+def bgzf_inflate(data: bytes, flags: int = 0, cap: int | None = None, ctx: "Context | None" = None):
+    """bpsw_bgzf_inflate: the whole blocks of `data` -> (their bytes, the number of blocks, the offset behind the last of them).  Without a
+    cap the buffer is sized by a first call; without a context the call needs BGZF_HOST."""
+    lib = load_library() if ctx is None else ctx.lib
+    need, nb, consumed = C.c_size_t(0), C.c_int64(0), C.c_int64(0)
+    size = 0 if cap is None else int(cap)
+    while True:
+        buf = np.full(size + 1, 0xee, np.uint8)
+        rc = lib.bpsw_bgzf_inflate(None if ctx is None else ctx.h, data, len(data), int(flags), _ptr(buf), size, C.byref(need), C.byref(nb),
+                                   C.byref(consumed))
+        if rc == -3 and cap is None and need.value > size:
+            size = int(need.value)
+            continue
+        if rc != BPSW_OK:
+            raise BgzfError(f"bpsw_bgzf_inflate failed ({rc}): {lib.bpsw_last_error().decode()}", rc, int(need.value), int(nb.value),
+                            int(consumed.value))
+        assert buf[size] == 0xee   # (nothing is written past the capacity)
+        return buf[: int(need.value)].tobytes(), int(nb.value), int(consumed.value)
+
+
+def last_bgzf_times():
+    """(the header walk, bgzf_inflate_kernel, the round trip with the copies) in ms of this thread's last bgzf_inflate"""
+    ms = (C.c_double * 3)()
+    load_library().bpsw_last_bgzf_times(ms)
+    return tuple(ms)
+
+
+def voffset(v: int):
+    """a BGZF virtual offset -> (coffset, uoffset)"""
+    return int(v) >> 16, int(v) & 0xffff
+
+
+def _grown(call, max_reads, start=4096):
+    """call(max_reads) with room for `start` reads, and once more with what the refusal names when that was too few"""
+    if max_reads is not None:
+        return call(int(max_reads))
+    try:
+        return call(start)
+    except FastqError as e:
+        if e.rc != -3 or e.n_reads <= start:
+            raise
+        return call(e.n_reads)
+
+
+def fastq_bgzf_parse(text1: bytes, text2: bytes | None = None, flags: int = 0, skip=(0, 0), max_reads: int | None = None,
+                     pool_cap: int | None = None, name_cap: int | None = None, ctx: "Context | None" = None) -> FastqReads:
+    """bpsw_fastq_bgzf_parse: fastq_parse over BGZF chunks; consumed comes back as virtual offsets.  Without capacities a first call
+    asks for the sizes."""
+    lib = load_library() if ctx is None else ctx.lib
+    mr, pc, nc = (0 if v is None else int(v) for v in (max_reads, pool_cap, name_cap))
+    while True:
+        read_len, read_off, name_off = np.zeros(mr + 1, np.int32), np.zeros(mr + 1, np.int64), np.zeros(mr + 2, np.int64)
+        read_pool, qual_pool, name_pool = np.full(pc + 1, 0xee, np.uint8), np.full(pc + 1, 0xee, np.uint8), np.full(nc + 1, 0xee, np.uint8)
+        n, consumed, needed = C.c_int64(0), np.zeros(2, np.int64), np.zeros(3, np.int64)
+        rc = lib.bpsw_fastq_bgzf_parse(None if ctx is None else ctx.h, text1, len(text1 or b""), int(skip[0]), text2, len(text2 or b""),
+                                       int(skip[1]), int(flags), mr, pc, nc, _ptr(read_len), _ptr(read_off), _ptr(read_pool), _ptr(qual_pool),
+                                       _ptr(name_off), _ptr(name_pool), C.byref(n), _ptr(consumed), _ptr(needed))
+        if rc == -3 and max_reads is None and pool_cap is None and name_cap is None and (needed[0] > mr or needed[1] > pc or needed[2] > nc):
+            mr, pc, nc = int(needed[0]), int(needed[1]), int(needed[2])
+            continue
+        break
+    if rc != BPSW_OK:
+        raise FastqError(f"bpsw_fastq_bgzf_parse failed ({rc}): {lib.bpsw_last_error().decode()}", rc, [int(x) for x in needed])
+    assert read_pool[pc] == 0xee and qual_pool[pc] == 0xee and name_pool[nc] == 0xee
+    k = int(n.value)
+    pairs = text2 is not None or bool(flags & FASTQ_PAIR_NAMES)
+    names = k // 2 if pairs else k
+    return FastqReads(k, (int(consumed[0]), int(consumed[1])), tuple(int(x) for x in needed), read_len[:k], read_off[:k],
+                      read_pool[: int(needed[1])], qual_pool[: int(needed[1])], name_off[: names + 1], name_pool[: int(needed[2])])
+
+
+def _ctx_align_fastq_bgzf_se(self, opt: Opt, sopt, topt: "TailOpt", text: bytes, skip: int = 0, fastq_flags: int = FASTQ_FINAL, id0: int = 0,
+                             id_step: int = 1, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0, flags: int = 0, text_cap: int | None = None,
+                             max_reads: int | None = None):
+    """a BGZF chunk of FASTQ text -> (SAM texts per read, the virtual offset consumed): align_fastq_se over compressed text"""
+    consumed = np.zeros(2, np.int64)
+    texts = _grown(lambda room: _fastq_text_call(
+        self.lib, "bpsw_align_fastq_bgzf_se", [],
+        lambda buf, cap, off, mr, need, n: self.lib.bpsw_align_fastq_bgzf_se(
+            self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text, len(text), int(skip), int(fastq_flags), int(id0), int(id_step), zdrop_mode,
+            w1_flags, flags, buf, cap, off, mr, need, n, _ptr(consumed)), text_cap, room), max_reads)
+    return texts, int(consumed[0])
+
+
+def _ctx_align_fastq_bgzf_pe(self, opt: Opt, sopt, topt: "TailOpt", text1: bytes, text2: bytes | None = None, skip=(0, 0),
+                             fastq_flags: int = FASTQ_FINAL, id0: int = 0, pes0=None, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0,
+                             rescue_mode: int = RESCUE_C, flags: int = 0, text_cap: int | None = None, max_reads: int | None = None):
+    """BGZF chunks of paired FASTQ text -> (SAM texts per read, the statistics used, the virtual offsets consumed)"""
+    consumed = np.zeros(2, np.int64)
+    pes_in = None if pes0 is None else _pes_struct(pes0)
+    pes = (PeStat * 4)()
+    texts = _grown(lambda room: _fastq_text_call(
+        self.lib, "bpsw_align_fastq_bgzf_pe", [],
+        lambda buf, cap, off, mr, need, n: self.lib.bpsw_align_fastq_bgzf_pe(
+            self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text1, len(text1), int(skip[0]), text2, len(text2 or b""), int(skip[1]),
+            int(fastq_flags), int(id0), pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, cap, off, mr, need, pes, n, _ptr(consumed)),
+        text_cap, room), max_reads)
+    return (texts, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)],
+            (int(consumed[0]), int(consumed[1])))
+
+
+def _ctx_align_fastq_bgzf_bam_se(self, opt: Opt, sopt, topt: "TailOpt", text: bytes, skip: int = 0, fastq_flags: int = FASTQ_FINAL, id0: int = 0,
+                                 id_step: int = 1, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0, flags: int = 0, cap: int | None = None):
+    """a BGZF chunk of FASTQ text -> (BAM records in BGZF blocks, reads parsed, the virtual offset consumed)"""
+    consumed, n = np.zeros(2, np.int64), C.c_int64(0)
+    out = _bytes_call(self.lib, "bpsw_align_fastq_bgzf_bam_se",
+                      lambda buf, size, need: self.lib.bpsw_align_fastq_bgzf_bam_se(
+                          self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text, len(text), int(skip), int(fastq_flags), int(id0), int(id_step),
+                          zdrop_mode, w1_flags, flags, buf, size, need, C.byref(n), _ptr(consumed)), cap)
+    return out, int(n.value), int(consumed[0])
+
+
+def _ctx_align_fastq_bgzf_bam_pe(self, opt: Opt, sopt, topt: "TailOpt", text1: bytes, text2: bytes | None = None, skip=(0, 0),
+                                 fastq_flags: int = FASTQ_FINAL, id0: int = 0, pes0=None, zdrop_mode: int = ZDROP_SCALA, w1_flags: int = 0,
+                                 rescue_mode: int = RESCUE_C, flags: int = 0, cap: int | None = None):
+    """BGZF chunks of paired FASTQ text -> (BAM records in BGZF blocks, the statistics used, reads parsed, the virtual offsets consumed)"""
+    consumed, n = np.zeros(2, np.int64), C.c_int64(0)
+    pes_in = None if pes0 is None else _pes_struct(pes0)
+    pes = (PeStat * 4)()
+    out = _bytes_call(self.lib, "bpsw_align_fastq_bgzf_bam_pe",
+                      lambda buf, size, need: self.lib.bpsw_align_fastq_bgzf_bam_pe(
+                          self.h, C.byref(opt), C.byref(sopt), C.byref(topt), text1, len(text1), int(skip[0]), text2, len(text2 or b""),
+                          int(skip[1]), int(fastq_flags), int(id0), pes_in, zdrop_mode, w1_flags, rescue_mode, flags, buf, size, need, pes,
+                          C.byref(n), _ptr(consumed)), cap)
+    return (out, [(int(pes[r].low), int(pes[r].high), int(pes[r].failed), float(pes[r].avg), float(pes[r].std)) for r in range(4)],
+            int(n.value), (int(consumed[0]), int(consumed[1])))
+
+
 def _header_call(entry: str, ctx, lens, names, extra: bytes, cap):
     lib = load_library() if ctx is None else ctx.lib
     ln = None if lens is None else np.ascontiguousarray(lens, np.int32)
@@ -1500,6 +1661,12 @@ Context.align_bam_se_batch = _ctx_align_bam_se_batch
 Context.align_bam_pe_batch = _ctx_align_bam_pe_batch
 Context.align_fastq_bam_se = _ctx_align_fastq_bam_se
 Context.align_fastq_bam_pe = _ctx_align_fastq_bam_pe
+Context.bgzf_inflate = lambda self, data, flags=0, cap=None: bgzf_inflate(data, flags, cap, ctx=self)
+Context.fastq_bgzf_parse = lambda self, text1, text2=None, flags=0, **kw: fastq_bgzf_parse(text1, text2, flags, ctx=self, **kw)
+Context.align_fastq_bgzf_se = _ctx_align_fastq_bgzf_se
+Context.align_fastq_bgzf_pe = _ctx_align_fastq_bgzf_pe
+Context.align_fastq_bgzf_bam_se = _ctx_align_fastq_bgzf_bam_se
+Context.align_fastq_bgzf_bam_pe = _ctx_align_fastq_bgzf_bam_pe
 Context.sam_header = lambda self, extra=b"", cap=None: sam_header(extra=extra, ctx=self, cap=cap)
 Context.bam_header = lambda self, extra=b"", cap=None: bam_header(extra=extra, ctx=self, cap=cap)
 Context.bam_eof = lambda self: bam_eof()

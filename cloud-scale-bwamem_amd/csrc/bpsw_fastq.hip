@@ -19,6 +19,12 @@
 // The host waits three times: for the line counts (they size the line table and say how many reads there are), for the totals and
 // the bad-read word (they decide between a refusal, BPSW_ERR_CAPACITY and the emit), and for the pools.
 //
+// The bpsw_*_bgzf_* entries are the same bodies over BGZF chunks.  The calling thread walks the block headers (bpsw_inflate_core.h), the
+// whole blocks and their tables are what is staged, bgzf_inflate_kernel (bpsw_bgzf_in.hip) writes the text into a buffer of the
+// context's own, d_bgzf, and the four kernels read it there: the text never crosses PCIe.  The count kernels are launched right behind
+// the inflate and its status word comes back in the first wait, together with the text's last byte (open_line needs it); an inflate
+// refusal wins over every refusal of the parse.  Offsets into such a text go back to the caller as BGZF virtual offsets.
+//
 // The line table has room for 4 * fq_records_to_parse(lines, bytes) + 1 starts, not for 4 * max_reads + 1: `needed` is to be complete
 // after one call, also when max_reads is the capacity that is short, and fq_records_to_parse bounds the room by the text's size.
 #include <string.h>
@@ -29,9 +35,11 @@
 #include "bpsw_internal.h"
 #include "bpsw_wave.h"
 #include "bpsw_fastq_core.h"
+#include "bpsw_inflate_core.h"
 
 using namespace bpsw;
 namespace fq = bpsw::fqcore;
+namespace ic = bpsw::inflcore;
 
 static_assert(fq::FINAL == BPSW_FASTQ_FINAL && fq::INTERLEAVED == BPSW_FASTQ_INTERLEAVED && fq::PAIR_NAMES == BPSW_FASTQ_PAIR_NAMES &&
               fq::HOST == BPSW_FASTQ_HOST, "the core's flags are the header's");
@@ -172,6 +180,29 @@ struct Caller {  // what a parse is asked for, whoever applies the rules
   int n_texts, flags;
 };
 
+// The compressed side of a parse whose texts are BGZF chunks (the bpsw_*_bgzf_* entries): per text the chunk, the walk of its headers
+// and how many bytes of the first block's output earlier calls consumed.  The Caller of such a parse has no host text (text[t] null);
+// its bytes[t] are the inflated bytes behind skip[t].
+struct Bgzf {
+  const char* in[2];
+  int32_t skip[2];
+  ic::Walk walk[2];
+};
+int refuse_block(const char* who, int t, long long block, int reason) {
+  return fail(BPSW_ERR_ARG, std::string(who) + ": text " + std::to_string(t + 1) + ": block " + std::to_string(block) + ": " + ic::inflate_reason_text(reason));
+}
+// where text t's 16-byte status line and its bytes lie in d_bgzf: the inflated stream begins (-skip) & 15 bytes behind a 16-byte line, so
+// that the text, which begins `skip` bytes into it, begins on one (the count / lines / emit kernels load it 16 bytes at a time)
+struct BgzfPlace { size_t status, stream, text, end; };
+BgzfPlace bgzf_place(const Bgzf& Z, int t, size_t from) {
+  BgzfPlace P;
+  P.status = from;
+  P.stream = from + 16 + (size_t)((16 - (Z.skip[t] & 15)) & 15);
+  P.text = P.stream + (size_t)Z.skip[t];
+  P.end = align16(P.stream + (size_t)Z.walk[t].total) + 16;
+  return P;
+}
+
 // the refusal of read `bad` for `reason`: the entry, the record, the text and the reason in fixed words
 int refuse(const Caller& A, const fq::Shape& S, long long bad, int reason) {
   if (reason == fq::R_TABLE) return fail(BPSW_ERR_DEVICE, std::string(A.who) + ": the line table is inconsistent");
@@ -183,16 +214,25 @@ int refuse(const Caller& A, const fq::Shape& S, long long bad, int reason) {
 unsigned grid_of(long long items) { return (unsigned)((items + kFqThreads - 1) / kFqThreads); }
 
 // The parse on the device.  Caller holds c->mu through a ContextEntry.  room: as parse_serial's.
+// Z: the texts are BGZF chunks -- what is staged is the chunks' whole blocks and their tables, bgzf_inflate_kernel writes the text into
+// d_bgzf, and the kernels below read it there; its status words come back with the line counts.
 template <class Room>
-int parse_device(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res) {
+int parse_device(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res, const Bgzf* Z = nullptr) {
   const double t0 = wall_ms();
   hipStream_t s = c->stream;
   // ---- the text, and its newlines per tile --------------------------------------------------------------------------------------
   StageIn in;
-  int i_text[2] = {-1, -1};
+  int i_text[2] = {-1, -1}, i_tab[2] = {-1, -1};
   long long tiles[2] = {0, 0};
+  BgzfPlace place[2] = {};
   for (int t = 0; t < A.n_texts; ++t) {
-    i_text[t] = in.add(A.text[t], (size_t)A.bytes[t]);
+    if (Z) {
+      i_text[t] = in.add(Z->in[t], (size_t)Z->walk[t].consumed);
+      i_tab[t] = in.add(Z->walk[t].blocks.data(), sizeof(ic::Block) * Z->walk[t].blocks.size());
+      place[t] = bgzf_place(*Z, t, t ? place[0].end : 0);
+    } else {
+      i_text[t] = in.add(A.text[t], (size_t)A.bytes[t]);
+    }
     tiles[t] = (A.bytes[t] + kFqTileBytes - 1) / kFqTileBytes;
   }
   const int tile_items = scan_tile_items();
@@ -211,6 +251,19 @@ int parse_device(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res) {
     T.lt[t] = nullptr;
     T.bytes[t] = t < A.n_texts ? A.bytes[t] : 0;
   }
+  if (Z) {
+    HIP_TRY(c->d_bgzf.reserve(place[A.n_texts - 1].end));
+    uint8_t* D = (uint8_t*)c->d_bgzf.ptr;
+    for (int t = 0; t < A.n_texts; ++t) {
+      const std::vector<ic::Block>& blocks = Z->walk[t].blocks;
+      int last = (int)blocks.size() - 1;  // the block that holds the text's last byte
+      while (last >= 0 && !blocks[(size_t)last].isize) --last;
+      HIP_TRY(hipMemsetAsync(D + place[t].status, 0xff, 16, s));
+      HIP_TRY(launch_bgzf_inflate(s, in.dev<uint8_t>(i_text[t]), in.dev<ic::Block>(i_tab[t]), (int)blocks.size(), D + place[t].stream, last,
+                                  (unsigned long long*)(D + place[t].status)));
+      T.text[t] = (const char*)(D + place[t].text);
+    }
+  }
   HIP_TRY(hipEventRecord(c->ev[0], s));
   for (int t = 0; t < A.n_texts; ++t) {
     if (!tiles[t]) continue;
@@ -223,6 +276,8 @@ int parse_device(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res) {
   for (int t = 0; t < A.n_texts; ++t) {
     HIP_TRY(scan_exclusive_i64(s, (long long*)(W1 + o_cnt[t]), 1, tiles[t], tile_items, (long long*)(W1 + o_sums[t])));
     HIP_TRY(hipMemcpyAsync((long long*)c->h_stage_out.ptr + t, (long long*)(W1 + o_cnt[t]) + tiles[t], 8, hipMemcpyDeviceToHost, s));
+    if (Z)  // (the inflate's status comes back in the wait for the line counts: a bad block costs no wait of its own)
+      HIP_TRY(hipMemcpyAsync((long long*)c->h_stage_out.ptr + 2 + 2 * t, (uint8_t*)c->d_bgzf.ptr + place[t].status, 16, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
   float ms = 0.f;
@@ -230,8 +285,18 @@ int parse_device(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res) {
   t_fq[0] = ms;
   long long lines[2] = {0, 0};
   int open_line[2] = {0, 0};
+  char last_byte[2] = {'\n', '\n'};
   for (int t = 0; t < A.n_texts; ++t) {
-    open_line[t] = (A.flags & BPSW_FASTQ_FINAL) && A.bytes[t] > 0 && A.text[t][A.bytes[t] - 1] != '\n';
+    if (Z) {
+      const unsigned long long* st = (const unsigned long long*)c->h_stage_out.ptr + 2 + 2 * t;
+      if (st[0] != ~0ull) return refuse_block(A.who, t, (long long)(st[0] >> 8), (int)(st[0] & 0xff));
+      last_byte[t] = (char)(uint8_t)st[1];
+    } else if (A.bytes[t] > 0) {
+      last_byte[t] = A.text[t][A.bytes[t] - 1];
+    }
+  }
+  for (int t = 0; t < A.n_texts; ++t) {
+    open_line[t] = (A.flags & BPSW_FASTQ_FINAL) && A.bytes[t] > 0 && last_byte[t] != '\n';
     lines[t] = ((const long long*)c->h_stage_out.ptr)[t] + open_line[t];
   }
   const fq::Shape S = fq::fq_shape(A.n_texts, A.flags, lines, A.bytes);
@@ -354,21 +419,56 @@ int check_texts(const char* who, const char* text1, size_t bytes1, const char* t
   return BPSW_OK;
 }
 
+// ... and what the BGZF entries check on top: the headers of every chunk, that a final chunk ends on a block, the skips, the limit.
+// A's texts become the inflated ones (no host pointer, the bytes behind the skip).
+int open_bgzf(const int32_t skip[2], Caller* A, Bgzf* Z) {
+  const std::string w(A->who);
+  for (int t = 0; t < A->n_texts; ++t) {
+    const std::string wt = w + ": text " + std::to_string(t + 1);
+    Z->in[t] = A->text[t];
+    Z->skip[t] = skip[t];
+    ic::Walk& W = Z->walk[t];
+    ic::bgzf_walk((const uint8_t*)A->text[t], A->bytes[t], &W);
+    if (W.bad_reason) return refuse_block(A->who, t, W.bad_block, W.bad_reason);
+    if ((A->flags & BPSW_FASTQ_FINAL) && W.consumed != A->bytes[t]) return fail(BPSW_ERR_ARG, wt + ": the text ends inside a BGZF block");
+    if (skip[t] < 0 || (W.blocks.empty() ? skip[t] != 0 : (uint32_t)skip[t] > W.blocks[0].isize))
+      return fail(BPSW_ERR_ARG, wt + ": skip is not within the first block's bytes");
+    if (W.total >= (1ll << 31)) return fail(BPSW_ERR_LIMIT, wt + ": 2^31 inflated bytes or more");
+    A->text[t] = nullptr;
+    A->bytes[t] = W.total - skip[t];
+  }
+  return BPSW_OK;
+}
+
 // one parse by either path; PARSE_BAD has become the refusal, PARSE_CAPACITY is the caller's to report
 template <class Room>
-int parse_any(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res, int* how) {
+int parse_any(bpsw_ctx* c, const Caller& A, Room&& room, fq::Result* res, int* how, const Bgzf* Z = nullptr) {
   if (A.flags & BPSW_FASTQ_HOST) {
     const double t0 = wall_ms();
-    *how = fq::parse_serial(A.text, A.bytes, A.n_texts, A.flags, room, res);
+    Caller H = A;
+    if (Z) {  // inflate_serial into a buffer of the calling thread; the text begins `skip` bytes into it
+      thread_local std::vector<uint8_t> text[2];
+      thread_local std::vector<ic::Work> work(1);
+      for (int t = 0; t < A.n_texts; ++t) {
+        if (text[t].size() < (size_t)Z->walk[t].total + 1) text[t].resize((size_t)Z->walk[t].total + 1);
+        long long bad_block = -1;
+        const int reason = ic::inflate_serial(work[0], (const uint8_t*)Z->in[t], Z->walk[t], text[t].data(), &bad_block);
+        if (reason) return refuse_block(A.who, t, bad_block, reason);
+        H.text[t] = (const char*)text[t].data() + Z->skip[t];
+      }
+    }
+    *how = fq::parse_serial(H.text, H.bytes, H.n_texts, H.flags, room, res);
     t_fq[0] = t_fq[1] = t_fq[2] = t_fq[3] = 0.;
     t_fq[4] = wall_ms() - t0;
   } else {
     ContextEntry entry(c);
     if (entry.rc != BPSW_OK) return entry.rc;
-    const int rc = parse_device(c, A, room, res);
+    const int rc = parse_device(c, A, room, res, Z);
     if (rc < 0) return rc;
     *how = rc;
   }
+  if (Z)  // how far each text was consumed, as a virtual offset
+    for (int t = 0; t < A.n_texts; ++t) res->consumed[t] = ic::virtual_offset(Z->walk[t], (long long)Z->skip[t] + res->consumed[t]);
   if (*how == fq::PARSE_BAD) {
     long long lines[2] = {0, 0};  // (the shape's mapping of reads to records does not depend on the line counts)
     return refuse(A, fq::fq_shape(A.n_texts, A.flags, lines, A.bytes), res->bad_read, res->bad_reason);
@@ -394,8 +494,9 @@ struct Parsed {
 };
 
 // the bodies of the align entries: the parse, then the align entry of the form asked for (bam: the BAM twin, which has no out_off)
+// skip: null for plain text, else the texts are BGZF chunks and skip[t] text t's
 int fastq_se(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
-             size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out_text, size_t text_cap,
+             size_t bytes, const int32_t* skip, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out_text, size_t text_cap,
              int64_t* out_off, int64_t max_reads, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
   const std::string w(who);
   if (!c || !opt || !sopt || !topt || (!bam && !out_off) || !n_reads || !consumed || max_reads < 0) return fail(BPSW_ERR_ARG, w + ": null argument");
@@ -404,10 +505,12 @@ int fastq_se(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, co
   int rc = check_texts(who, text, bytes, nullptr, 0, fastq_flags, &A);
   if (rc != BPSW_OK) return rc;
   thread_local Parsed P;  // (grown, never shrunk: fresh pools of a 30 MB chunk cost the call more than its parse)
+  thread_local Bgzf Z;
   fq::Result res;
   int how = fq::PARSE_OK;
   *n_reads = 0; *consumed = 0;
-  rc = parse_any(c, A, P, &res, &how);
+  if (skip && (rc = open_bgzf(skip, &A, &Z)) != BPSW_OK) return rc;
+  rc = parse_any(c, A, P, &res, &how, skip ? &Z : nullptr);
   if (rc != BPSW_OK) return rc;
   *n_reads = res.n_reads;
   if (!bam && res.n_reads > max_reads) return fail(BPSW_ERR_CAPACITY, w + ": out_off has room for fewer reads than the text holds (*n_reads)");
@@ -425,7 +528,7 @@ int fastq_se(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, co
 }
 
 int fastq_pe(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text1,
-             size_t bytes1, const char* text2, size_t bytes2, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags,
+             size_t bytes1, const char* text2, size_t bytes2, const int32_t* skip, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags,
              int rescue_mode, int flags, char* out_text, size_t text_cap, int64_t* out_off, int64_t max_reads, size_t* out_needed,
              bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
   const std::string w(who);
@@ -436,10 +539,12 @@ int fastq_pe(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, co
   int rc = check_texts(who, text1, bytes1, text2, bytes2, fastq_flags, &A);
   if (rc != BPSW_OK) return rc;
   thread_local Parsed P;
+  thread_local Bgzf Z;
   fq::Result res;
   int how = fq::PARSE_OK;
   *n_reads = 0; consumed[0] = consumed[1] = 0;
-  rc = parse_any(c, A, P, &res, &how);
+  if (skip && (rc = open_bgzf(skip, &A, &Z)) != BPSW_OK) return rc;
+  rc = parse_any(c, A, P, &res, &how, skip ? &Z : nullptr);
   if (rc != BPSW_OK) return rc;
   *n_reads = res.n_reads;
   if (!bam && res.n_reads > max_reads) return fail(BPSW_ERR_CAPACITY, w + ": out_off has room for fewer reads than the texts hold (*n_reads)");
@@ -460,15 +565,17 @@ int fastq_pe(const char* who, bool bam, bpsw_ctx_t* c, const bpsw_opt_t* opt, co
 
 extern "C" {
 
-int bpsw_fastq_parse(bpsw_ctx_t* c, const char* text1, size_t bytes1, const char* text2, size_t bytes2, int flags, int64_t max_reads,
-                     size_t pool_cap, size_t name_cap, int32_t* read_len, int64_t* read_off, uint8_t* read_pool, uint8_t* qual_pool,
-                     int64_t* name_off, char* name_pool, int64_t* n_reads, int64_t consumed[2], int64_t needed[3]) {
+static int fastq_parse_body(const char* who, bpsw_ctx_t* c, const char* text1, size_t bytes1, const char* text2, size_t bytes2, const int32_t* skip,
+                            int flags, int64_t max_reads, size_t pool_cap, size_t name_cap, int32_t* read_len, int64_t* read_off, uint8_t* read_pool,
+                            uint8_t* qual_pool, int64_t* name_off, char* name_pool, int64_t* n_reads, int64_t consumed[2], int64_t needed[3]) {
+  const std::string w(who);
   if ((!c && !(flags & BPSW_FASTQ_HOST)) || !read_len || !read_off || !read_pool || !qual_pool || !name_off || !name_pool || !n_reads || !consumed ||
       !needed || max_reads < 0)
-    return fail(BPSW_ERR_ARG, "fastq_parse: null argument");
+    return fail(BPSW_ERR_ARG, w + ": null argument");
   Caller A;
-  int rc = check_texts("fastq_parse", text1, bytes1, text2, bytes2, flags, &A);
+  int rc = check_texts(who, text1, bytes1, text2, bytes2, flags, &A);
   if (rc != BPSW_OK) return rc;
+  thread_local Bgzf Z;
   auto room = [&](const fq::Result& r, fq::Outputs* o) {
     if (r.needed[0] > max_reads || (unsigned long long)r.needed[1] > pool_cap || (unsigned long long)r.needed[2] > name_cap) return false;
     o->read_len = read_len; o->read_off = read_off; o->read_pool = read_pool; o->qual_pool = qual_pool;
@@ -480,21 +587,29 @@ int bpsw_fastq_parse(bpsw_ctx_t* c, const char* text1, size_t bytes1, const char
   *n_reads = 0;
   consumed[0] = consumed[1] = 0;
   needed[0] = needed[1] = needed[2] = 0;
-  rc = parse_any(c, A, room, &res, &how);
+  if (skip && (rc = open_bgzf(skip, &A, &Z)) != BPSW_OK) return rc;
+  rc = parse_any(c, A, room, &res, &how, skip ? &Z : nullptr);
   if (rc != BPSW_OK) return rc;
   for (int k = 0; k < 3; ++k) needed[k] = res.needed[k];
   if (how == fq::PARSE_CAPACITY)
-    return fail(BPSW_ERR_CAPACITY, "fastq_parse: the outputs are too small (needed: " + std::to_string(res.needed[0]) + " reads, " +
+    return fail(BPSW_ERR_CAPACITY, w + ": the outputs are too small (needed: " + std::to_string(res.needed[0]) + " reads, " +
                                        std::to_string(res.needed[1]) + " pool bytes, " + std::to_string(res.needed[2]) + " name bytes)");
   *n_reads = res.n_reads;
   consumed[0] = res.consumed[0]; consumed[1] = res.consumed[1];
   return BPSW_OK;
 }
 
+int bpsw_fastq_parse(bpsw_ctx_t* c, const char* text1, size_t bytes1, const char* text2, size_t bytes2, int flags, int64_t max_reads,
+                     size_t pool_cap, size_t name_cap, int32_t* read_len, int64_t* read_off, uint8_t* read_pool, uint8_t* qual_pool,
+                     int64_t* name_off, char* name_pool, int64_t* n_reads, int64_t consumed[2], int64_t needed[3]) {
+  return fastq_parse_body("fastq_parse", c, text1, bytes1, text2, bytes2, nullptr, flags, max_reads, pool_cap, name_cap, read_len, read_off, read_pool,
+                          qual_pool, name_off, name_pool, n_reads, consumed, needed);
+}
+
 int bpsw_align_fastq_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
                         size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out_text,
                         size_t text_cap, int64_t* out_off, int64_t max_reads, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
-  return fastq_se("align_fastq_se", false, c, opt, sopt, topt, text, bytes, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out_text, text_cap,
+  return fastq_se("align_fastq_se", false, c, opt, sopt, topt, text, bytes, nullptr, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out_text, text_cap,
                   out_off, max_reads, out_needed, n_reads, consumed);
 }
 
@@ -502,7 +617,7 @@ int bpsw_align_fastq_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_op
                         size_t bytes1, const char* text2, size_t bytes2, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0, int zdrop_mode,
                         int w1_flags, int rescue_mode, int flags, char* out_text, size_t text_cap, int64_t* out_off, int64_t max_reads,
                         size_t* out_needed, bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
-  return fastq_pe("align_fastq_pe", false, c, opt, sopt, topt, text1, bytes1, text2, bytes2, fastq_flags, id0, pes0, zdrop_mode, w1_flags, rescue_mode,
+  return fastq_pe("align_fastq_pe", false, c, opt, sopt, topt, text1, bytes1, text2, bytes2, nullptr, fastq_flags, id0, pes0, zdrop_mode, w1_flags, rescue_mode,
                   flags, out_text, text_cap, out_off, max_reads, out_needed, out_pes, n_reads, consumed);
 }
 
@@ -510,7 +625,7 @@ int bpsw_align_fastq_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_op
 int bpsw_align_fastq_bam_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
                             size_t bytes, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags, char* out,
                             size_t cap, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
-  return fastq_se("align_fastq_bam_se", true, c, opt, sopt, topt, text, bytes, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out, cap, nullptr,
+  return fastq_se("align_fastq_bam_se", true, c, opt, sopt, topt, text, bytes, nullptr, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out, cap, nullptr,
                   0, out_needed, n_reads, consumed);
 }
 
@@ -518,7 +633,51 @@ int bpsw_align_fastq_bam_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_see
                             size_t bytes1, const char* text2, size_t bytes2, int fastq_flags, int64_t id0, const bpsw_pestat_t* pes0,
                             int zdrop_mode, int w1_flags, int rescue_mode, int flags, char* out, size_t cap, size_t* out_needed,
                             bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
-  return fastq_pe("align_fastq_bam_pe", true, c, opt, sopt, topt, text1, bytes1, text2, bytes2, fastq_flags, id0, pes0, zdrop_mode, w1_flags,
+  return fastq_pe("align_fastq_bam_pe", true, c, opt, sopt, topt, text1, bytes1, text2, bytes2, nullptr, fastq_flags, id0, pes0, zdrop_mode, w1_flags,
+                  rescue_mode, flags, out, cap, nullptr, 0, out_needed, out_pes, n_reads, consumed);
+}
+
+// the same entries over BGZF chunks (bpsw_bgzf_in.hip inflates them; the text stays on the device)
+int bpsw_fastq_bgzf_parse(bpsw_ctx_t* c, const char* text1, size_t bytes1, int32_t skip1, const char* text2, size_t bytes2, int32_t skip2, int flags,
+                          int64_t max_reads, size_t pool_cap, size_t name_cap, int32_t* read_len, int64_t* read_off, uint8_t* read_pool,
+                          uint8_t* qual_pool, int64_t* name_off, char* name_pool, int64_t* n_reads, int64_t consumed[2], int64_t needed[3]) {
+  const int32_t skip[2] = {skip1, skip2};
+  return fastq_parse_body("fastq_bgzf_parse", c, text1, bytes1, text2, bytes2, skip, flags, max_reads, pool_cap, name_cap, read_len, read_off,
+                          read_pool, qual_pool, name_off, name_pool, n_reads, consumed, needed);
+}
+
+int bpsw_align_fastq_bgzf_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
+                             size_t bytes, int32_t skip, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags,
+                             char* out_text, size_t text_cap, int64_t* out_off, int64_t max_reads, size_t* out_needed, int64_t* n_reads,
+                             int64_t* consumed) {
+  const int32_t sk[2] = {skip, 0};
+  return fastq_se("align_fastq_bgzf_se", false, c, opt, sopt, topt, text, bytes, sk, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out_text,
+                  text_cap, out_off, max_reads, out_needed, n_reads, consumed);
+}
+
+int bpsw_align_fastq_bgzf_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text1,
+                             size_t bytes1, int32_t skip1, const char* text2, size_t bytes2, int32_t skip2, int fastq_flags, int64_t id0,
+                             const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char* out_text, size_t text_cap,
+                             int64_t* out_off, int64_t max_reads, size_t* out_needed, bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
+  const int32_t sk[2] = {skip1, skip2};
+  return fastq_pe("align_fastq_bgzf_pe", false, c, opt, sopt, topt, text1, bytes1, text2, bytes2, sk, fastq_flags, id0, pes0, zdrop_mode, w1_flags,
+                  rescue_mode, flags, out_text, text_cap, out_off, max_reads, out_needed, out_pes, n_reads, consumed);
+}
+
+int bpsw_align_fastq_bgzf_bam_se(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text,
+                                 size_t bytes, int32_t skip, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags,
+                                 char* out, size_t cap, size_t* out_needed, int64_t* n_reads, int64_t* consumed) {
+  const int32_t sk[2] = {skip, 0};
+  return fastq_se("align_fastq_bgzf_bam_se", true, c, opt, sopt, topt, text, bytes, sk, fastq_flags, id0, id_step, zdrop_mode, w1_flags, flags, out, cap,
+                  nullptr, 0, out_needed, n_reads, consumed);
+}
+
+int bpsw_align_fastq_bgzf_bam_pe(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_seed_opt_t* sopt, const bpsw_tail_opt_t* topt, const char* text1,
+                                 size_t bytes1, int32_t skip1, const char* text2, size_t bytes2, int32_t skip2, int fastq_flags, int64_t id0,
+                                 const bpsw_pestat_t* pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char* out, size_t cap,
+                                 size_t* out_needed, bpsw_pestat_t* out_pes, int64_t* n_reads, int64_t consumed[2]) {
+  const int32_t sk[2] = {skip1, skip2};
+  return fastq_pe("align_fastq_bgzf_bam_pe", true, c, opt, sopt, topt, text1, bytes1, text2, bytes2, sk, fastq_flags, id0, pes0, zdrop_mode, w1_flags,
                   rescue_mode, flags, out, cap, nullptr, 0, out_needed, out_pes, n_reads, consumed);
 }
 

@@ -325,6 +325,13 @@ hipError_t launch_chain2aln_kernel(const ChainBatchDev& B, const ChainParams& P,
 int sort_dedup_regs(std::vector<bpsw_alnreg_t>& v, float mask_level_redun, int mode);
 void rescue_scratch_free(void* p);
 
+// ---- BGZF input (bpsw_bgzf_in.hip) -------------------------------------------------------------
+// bgzf_inflate_kernel over n_blocks entries of an inflcore::Block table: d_in is the chunk the table's offsets count in, d_out where
+// offset 0 of the inflated bytes goes (any alignment), d_status two 64-bit words, all ones before the launch ([0] the lowest
+// block << 8 | reason, [1] the last byte of block last_block's bytes; last_block -1: nobody's).
+hipError_t launch_bgzf_inflate(hipStream_t s, const uint8_t* d_in, const void* d_tab, int n_blocks, uint8_t* d_out, int last_block,
+                               unsigned long long* d_status);
+
 // ---- error text -----------------------------------------------------------------------------------
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
@@ -608,6 +615,7 @@ struct bpsw_ctx {
   bpsw_stats_t stats;
   float last_ext_ms = 0.f, last_sw_ms = 0.f;
   bool have_ext_ev = false, have_sw_ev = false;
+  bpsw::DeviceBuffer d_bgzf;  // the inflated text of BGZF input (bpsw_bgzf_in.hip): per text a 16-byte status line, then the bytes; grown, never shrunk
   bpsw::DeviceBuffer d_chain_tab;  // the resident chains (bpsw_chain_dev.hip, ChainTablesDev): pools, per-read columns, the tables the round loop indexes
 };
 

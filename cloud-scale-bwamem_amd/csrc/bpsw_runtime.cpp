@@ -396,7 +396,7 @@ double bpsw_diag_wait_est_update(double est, double took_ms, int polls, int napp
 int bpsw_diag_wait_naps(double est_ms) { return bpsw::wait_naps(est_ms) ? 1 : 0; }
 
 const char* bpsw_version(void) {
-  return "bPSW-hip 0.6 (gfx950)";  // 0.5: bpsw_stats_t grew (sw_ring_calls, ext_ring_calls): rebuild callers against include/bpsw.h; 0.6: new entries only
+  return "bPSW-hip 0.7 (gfx950)";  // 0.5: bpsw_stats_t grew (sw_ring_calls, ext_ring_calls): rebuild callers against include/bpsw.h; 0.6, 0.7: new entries only
 }
 
 int bpsw_device_count(void) {
@@ -508,6 +508,7 @@ void bpsw_destroy(bpsw_ctx_t* c) {
   for (bpsw::DeviceBuffer& b : c->d_seed) b.release();
   c->d_chain.release();
   c->d_chain_tab.release();
+  c->d_bgzf.release();
   c->h_stage_in.release(); c->h_stage_out.release(); c->h_pre.release();
   rescue_scratch_free(c->rescue_scratch);
   for (int i = 0; i < 8; ++i)

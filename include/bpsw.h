@@ -675,8 +675,9 @@ void bpsw_last_sam_pe_times(double ms[8]);
  * trim_readno): a line ends at '\n' and loses one '\r' in front of it when it has more than one byte; line 4r begins with '@', line
  * 4r + 2 with '+' (its rest is ignored), line 4r + 3 is as long as line 4r + 1, which is not empty; the name is what follows '@' up
  * to the first isspace byte, without a trailing "/" + digit when it is longer than 2 bytes, and not empty; Aa Cc Gg Tt are 0..3 and
- * every other base is 4, except '-' and bytes below 4, which are refused; qualities are copied.  gzip, multi-line records, blank
- * lines between records and the comment field are not handled (the first three are refused as "not four-line FASTQ").
+ * every other base is 4, except '-' and bytes below 4, which are refused; qualities are copied.  Multi-line records, blank lines
+ * between records and the comment field are not handled (the first two are refused as "not four-line FASTQ"); compressed text is the
+ * bpsw_fastq_bgzf_* entries' (BGZF blocks; plain gzip is not handled).
  *
  * text1 / bytes1, text2 / bytes2: one text (text2 NULL, bytes2 0), or the two texts of paired reads -- record k of text1 is read 2k,
  * record k of text2 read 2k + 1, as bseq_read interleaves them.  Only whole records are parsed: consumed[i] is the offset just
@@ -783,6 +784,59 @@ void bpsw_last_bam_times(double ms[5]);
  * was refused), the blocks' size table back to the host with its sum and the offsets' way out, the copy of the packed blocks.  With the
  * flag, slot 2 of bpsw_last_bam_times (bgzf_frame_kernel) is 0. */
 void bpsw_last_bam_deflate_times(double ms[4]);
+
+/* ---- FASTQ in as BGZF: the blocks inflated on the device, parsed from there (bpsw_bgzf_in.hip, bpsw_fastq.hip) ------------------------
+ * Accepted: a sequence of BGZF blocks -- gzip members that begin 1f 8b 08 04 and whose extra field has the subfield BC (SLEN 2) with
+ * BSIZE; other subfields are skipped.  The deflate data of a block may be anything RFC 1951 allows (any number of stored, fixed and
+ * dynamic deflate blocks); the bound is ISIZE <= 65536, and a distance may not reach in front of the block's own output.  A gzip
+ * member without BC is refused with BPSW_ERR_ARG ("plain gzip, not BGZF").
+ *
+ * bpsw_bgzf_inflate: the whole blocks of in[0, in_bytes) to out.  Only whole blocks are inflated: *consumed is the offset behind the
+ * last of them, *n_blocks their number, *out_needed the sum of their ISIZE -- all three known from the headers before anything is
+ * launched.  cap < *out_needed is BPSW_ERR_CAPACITY with nothing launched.  A malformed header is BPSW_ERR_ARG and wins over a
+ * capacity; malformed deflate data, a wrong length or a wrong CRC-32 is BPSW_ERR_ARG too: the lowest such block is reported, and the
+ * text names the entry, the block and the reason.  in_bytes or the inflated total at 2^31 or above is BPSW_ERR_LIMIT.  An empty chunk
+ * and a lone end-of-file block give *out_needed == 0.
+ *   BPSW_BGZF_FINAL   the chunk ends here: bytes behind the last whole block are refused, not left
+ *   BPSW_BGZF_HOST    the same rules serially on the calling thread: nothing is launched, ctx may be NULL
+ *
+ * The five FASTQ entries below are their twins' argument lists with two differences: each text argument is BGZF bytes, and behind
+ * each `bytes` comes a `skip`.  The caller's state is a BGZF virtual offset as htslib defines it: skip is the number of inflated bytes
+ * of the chunk's first block that earlier calls consumed (0 .. its ISIZE; non-zero without a block, or above it, is BPSW_ERR_ARG), and
+ * consumed[i] comes back as coffset << 16 | uoffset: coffset is the chunk offset of the first block whose inflated end lies above the
+ * end of the last parsed record, uoffset that end within it; when no such block exists, (the offset behind the last whole block, 0).
+ * The next call passes in + coffset and skip = uoffset (it inflates that one block again).  Only whole blocks are read; with
+ * BPSW_FASTQ_FINAL a chunk must end on a block boundary ("the text ends inside a BGZF block").  An inflate refusal wins over every
+ * refusal of the parse.  On the device the inflated text stays there; with BPSW_FASTQ_HOST it is inflate_serial, then the serial
+ * parse, without a context, with identical results and refusals. */
+#define BPSW_BGZF_FINAL 1
+#define BPSW_BGZF_HOST 2
+int bpsw_bgzf_inflate(bpsw_ctx_t *ctx, const char *in, size_t in_bytes, int flags, char *out, size_t cap, size_t *out_needed,
+                      int64_t *n_blocks, int64_t *consumed);
+/* ms of the calling thread's last bpsw_bgzf_inflate: the header walk, bgzf_inflate_kernel, the round trip with the copies (zeros
+ * under BPSW_BGZF_HOST) */
+void bpsw_last_bgzf_times(double ms[3]);
+int bpsw_fastq_bgzf_parse(bpsw_ctx_t *ctx, const char *text1, size_t bytes1, int32_t skip1, const char *text2, size_t bytes2, int32_t skip2,
+                          int flags, int64_t max_reads, size_t pool_cap, size_t name_cap, int32_t *read_len, int64_t *read_off,
+                          uint8_t *read_pool, uint8_t *qual_pool, int64_t *name_off, char *name_pool, int64_t *n_reads, int64_t consumed[2],
+                          int64_t needed[3]);
+int bpsw_align_fastq_bgzf_se(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt, const char *text,
+                             size_t bytes, int32_t skip, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode, int w1_flags, int flags,
+                             char *out_text, size_t text_cap, int64_t *out_off, int64_t max_reads, size_t *out_needed, int64_t *n_reads,
+                             int64_t *consumed);
+int bpsw_align_fastq_bgzf_pe(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                             const char *text1, size_t bytes1, int32_t skip1, const char *text2, size_t bytes2, int32_t skip2, int fastq_flags,
+                             int64_t id0, const bpsw_pestat_t *pes0, int zdrop_mode, int w1_flags, int rescue_mode, int flags, char *out_text,
+                             size_t text_cap, int64_t *out_off, int64_t max_reads, size_t *out_needed, bpsw_pestat_t *out_pes, int64_t *n_reads,
+                             int64_t consumed[2]);
+int bpsw_align_fastq_bgzf_bam_se(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                                 const char *text, size_t bytes, int32_t skip, int fastq_flags, int64_t id0, int32_t id_step, int zdrop_mode,
+                                 int w1_flags, int flags, char *out, size_t cap, size_t *out_needed, int64_t *n_reads, int64_t *consumed);
+int bpsw_align_fastq_bgzf_bam_pe(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_seed_opt_t *sopt, const bpsw_tail_opt_t *topt,
+                                 const char *text1, size_t bytes1, int32_t skip1, const char *text2, size_t bytes2, int32_t skip2,
+                                 int fastq_flags, int64_t id0, const bpsw_pestat_t *pes0, int zdrop_mode, int w1_flags, int rescue_mode,
+                                 int flags, char *out, size_t cap, size_t *out_needed, bpsw_pestat_t *out_pes, int64_t *n_reads,
+                                 int64_t consumed[2]);
 
 /* ---- statistics (the buckets of profiling/SWBatchTimeBreakdown.scala:25-39, device flavoured) -- */
 typedef struct {
