@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "bpsw_sam_header", "bpsw_bam_header", "bpsw_bam_eof", "bpsw_bam_set_block_payload", "bpsw_last_bam_times", "bpsw_last_bam_deflate_times",
     "bpsw_bgzf_inflate", "bpsw_last_bgzf_times", "bpsw_fastq_bgzf_parse", "bpsw_align_fastq_bgzf_se", "bpsw_align_fastq_bgzf_pe",
     "bpsw_align_fastq_bgzf_bam_se", "bpsw_align_fastq_bgzf_bam_pe",
+    "bpsw_fmi_build_shape", "bpsw_fmi_build", "bpsw_last_fmi_build_times", "bpsw_last_fmi_build_stats", "bpsw_fmi_build_set_first_key",
+    "bpsw_fmi_build_set_budget",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -329,6 +331,13 @@ def _bind_seeding(lib):
         "bpsw_align_fastq_bgzf_bam_pe": ([C.c_void_p, C.POINTER(Opt), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int32, C.c_char_p,
                                           C.c_size_t, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p], C.c_int),
+        # the FM-index built on the device (bpsw_index.hip)
+        "bpsw_fmi_build_shape": ([C.c_int64, C.c_int32, C.c_void_p], C.c_int),
+        "bpsw_fmi_build": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+        "bpsw_last_fmi_build_times": ([C.c_void_p], None),
+        "bpsw_last_fmi_build_stats": ([C.c_void_p], None),
+        "bpsw_fmi_build_set_first_key": ([C.c_int], None),
+        "bpsw_fmi_build_set_budget": ([C.c_int64], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -338,6 +347,41 @@ def _bind_seeding(lib):
 
 def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+FMI_BUILD_LOAD, FMI_BUILD_REF = 1, 2   # fmi_build(flags=): BPSW_FMI_BUILD_LOAD, BPSW_FMI_BUILD_REF
+
+
+def fmi_build_shape(l_pac: int, sa_intv: int):
+    """bpsw_fmi_build_shape (host only) -> fmi.BuildShape with seq_len, bwt_size, n_sa and sa_intv filled"""
+    from . import fmi
+    lib = load_library()
+    sh = fmi.BuildShape()
+    _chk(lib, lib.bpsw_fmi_build_shape(int(l_pac), int(sa_intv), C.byref(sh)), "bpsw_fmi_build_shape")
+    return sh
+
+
+def last_fmi_build_times():
+    """ms of this thread's last fmi_build: (first keys + first sort, doubling rounds, BWT + counts + packing, sampling + copy-out, whole)"""
+    t = (C.c_double * 5)()
+    load_library().bpsw_last_fmi_build_times(t)
+    return tuple(float(v) for v in t)
+
+
+def last_fmi_build_stats():
+    """this thread's last fmi_build: dict(rounds, unresolved_first, unresolved_max, radix_passes, sort_tile, peak_bytes, first_key)"""
+    s = (C.c_int64 * 8)()
+    load_library().bpsw_last_fmi_build_stats(s)
+    names = ("rounds", "unresolved_first", "unresolved_max", "radix_passes", "sort_tile", "peak_bytes", "first_key")
+    return {k: int(s[i]) for i, k in enumerate(names)}
+
+
+def fmi_build_set_first_key(bases: int = 0):
+    load_library().bpsw_fmi_build_set_first_key(int(bases))
+
+
+def fmi_build_set_budget(nbytes: int = 0):
+    load_library().bpsw_fmi_build_set_budget(int(nbytes))
 
 
 def _chk(lib, rc, what):
@@ -636,6 +680,23 @@ class Context:
         sa = np.ascontiguousarray(idx.sa, np.int64)
         _chk(self.lib, self.lib.bpsw_fmi_load(self.h, int(idx.primary), _ptr(L2), int(idx.seq_len), _ptr(bwt), bwt.size, int(idx.sa_intv),
                                              sa.size, _ptr(sa)), "bpsw_fmi_load")
+
+    def fmi_build(self, pac: np.ndarray, l_pac: int, sa_intv: int, flags: int = 0, fetch: bool = True):
+        """bpsw_fmi_build: the index of the doubled text of a packed forward strand -> fmi.FmIndex.  flags: FMI_BUILD_LOAD,
+        FMI_BUILD_REF.  fetch=False (with FMI_BUILD_LOAD) passes no host arrays: the index stays on the device, and the FmIndex
+        that comes back has empty `bwt` and `sa`."""
+        from . import fmi
+        pac = np.ascontiguousarray(pac, np.uint8)
+        if pac.size < (int(l_pac) + 3) // 4:
+            raise BpswError("pac shorter than (l_pac+3)/4 bytes")
+        sh = fmi_build_shape(l_pac, sa_intv)
+        bwt = np.zeros(sh.bwt_size, np.uint32) if fetch else None
+        sa = np.zeros(sh.n_sa, np.int64) if fetch else None
+        out = fmi.BuildShape()
+        _chk(self.lib, self.lib.bpsw_fmi_build(self.h, _ptr(pac), int(l_pac), int(sa_intv), int(flags), _ptr(bwt), sh.bwt_size if fetch else 0,
+                                              _ptr(sa), sh.n_sa if fetch else 0, C.byref(out)), "bpsw_fmi_build")
+        return fmi.FmIndex(primary=int(out.primary), L2=np.array(list(out.L2), np.int64), seq_len=int(out.seq_len),
+                           bwt=bwt if fetch else np.zeros(0, np.uint32), sa_intv=int(out.sa_intv), sa=sa if fetch else np.zeros(0, np.int64))
 
     def fmi_unload(self):
         _chk(self.lib, self.lib.bpsw_fmi_unload(self.h), "bpsw_fmi_unload")

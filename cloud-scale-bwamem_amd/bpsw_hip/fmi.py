@@ -54,6 +54,26 @@ def read_index_files(bwt_path: str, sa_path: str) -> FmIndex:
     return FmIndex(primary=int(head[0]), L2=L2, seq_len=int(L2[4]), bwt=bwt, sa_intv=sa_intv, sa=sa)
 
 
+def write_index_files(idx: FmIndex, bwt_path: str, sa_path: str) -> None:
+    """The inverse of read_index_files: the .bwt and .sa files as bwt_dump_bwt / bwt_dump_sa write them (native/bwt.c).  .bwt: primary,
+    L2[1..4] (five 64-bit words), then the uint32 array.  .sa: primary, L2[1..4], sa_intv, seq_len (seven 64-bit words), then the
+    samples from the second on (the first, -1, is not stored)."""
+    L2 = np.asarray(idx.L2, np.int64)
+    head = np.concatenate([[int(idx.primary)], L2[1:5]]).astype("<i8")
+    with open(bwt_path, "wb") as f:
+        f.write(head.tobytes())
+        f.write(np.ascontiguousarray(idx.bwt, "<u4").tobytes())
+    with open(sa_path, "wb") as f:
+        f.write(head.tobytes())
+        f.write(np.array([int(idx.sa_intv), int(idx.seq_len)], "<i8").tobytes())
+        f.write(np.ascontiguousarray(idx.sa[1:], "<i8").tobytes())
+
+
+class BuildShape(C.Structure):  # bpsw_fmi_shape_t
+    _fields_ = [("primary", C.c_int64), ("L2", C.c_int64 * 5), ("seq_len", C.c_int64), ("bwt_size", C.c_int64), ("n_sa", C.c_int64),
+                ("sa_intv", C.c_int32), ("pad_", C.c_int32)]
+
+
 @dataclass
 class ReadBatch:
     read_len: np.ndarray   # int32 [n]

@@ -575,6 +575,11 @@ int scan_tile_items();
 long long scan_tiles(long long n, int tile);
 hipError_t scan_exclusive_i64(hipStream_t s, long long* data, int cols, long long n, int tile, long long* tile_sums);
 
+// ---- an index that is on the device already (bpsw_seed.hip; bpsw_index.hip builds one) -------------------------------------------------
+// bwt (bwt_size words and 64 zero bytes behind them) and sa become the loaded index of c's device exactly as after bpsw_fmi_load, with
+// no copy: the buffers change hands, and the caller is left with the previous index's, to free.  Caller holds c->mu (ContextEntry).
+int fmi_adopt(bpsw_ctx* c, DeviceBuffer* bwt, DeviceBuffer* sa, long long primary, const long long L2[5], long long seq_len, int sa_intv);
+
 }  // namespace bpsw
 
 struct bpsw_ctx {

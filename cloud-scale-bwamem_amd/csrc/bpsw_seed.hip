@@ -17,6 +17,7 @@
 
 #include <atomic>
 #include <optional>
+#include <utility>
 
 #include "bpsw_internal.h"
 #include "bpsw_seed_plan_core.h"
@@ -603,6 +604,29 @@ int check_reads(const char* who, const bpsw_reads_t* R) {
 }
 
 }  // namespace
+
+namespace bpsw {
+
+int fmi_adopt(bpsw_ctx* c, DeviceBuffer* bwt, DeviceBuffer* sa, long long primary, const long long L2[5], long long seq_len, int sa_intv) {
+  DeviceFmi& fm = device_fmi(c->device);
+  RefWriteHold wr(&fm.gate);
+  std::lock_guard<std::mutex> g(fm.mu);
+  RingPause ring_paused(c->device);
+  HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still read the previous index
+  std::swap(fm.bwt, *bwt);
+  std::swap(fm.sa, *sa);
+  FmiDev F;
+  F.bwt = (const uint32_t*)fm.bwt.ptr; F.sa = (const long long*)fm.sa.ptr;
+  F.primary = (u64)primary; F.seq_len = (u64)seq_len;
+  for (int i = 0; i < 5; ++i) F.L2[i] = (u64)L2[i];
+  F.sa_shift = 0;
+  while ((1 << F.sa_shift) < sa_intv) ++F.sa_shift;
+  fm.dev = F;
+  fm.seq_len = seq_len;
+  return BPSW_OK;
+}
+
+}  // namespace bpsw
 
 extern "C" {
 

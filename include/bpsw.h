@@ -459,6 +459,50 @@ void bpsw_seed_set_resident_lanes(int lanes);
 /* wall time of the calling thread's most recent bpsw_worker1_batch (ms): seeding call, chaining (host or device), round loop call */
 void bpsw_last_worker1_times(double ms[3]);
 
+/* ---- the FM-index built on the device from the 2-bit reference (bpsw_index.hip) -----------------------------------------------
+ *
+ * pac and l_pac are what bpsw_ref_load takes: the forward strand, base k = pac[k >> 2] >> ((~k & 3) << 1) & 3.  The text is the
+ * doubled sequence, the forward strand followed by its reverse complement (seq_len == 2 * l_pac); the device reads the second half
+ * from the forward bytes, the host never makes it.  The result is what bpsw_fmi_load documents and `bwa index` writes -- the
+ * sentinel's row removed from the BWT and recorded as primary, L2[0] == 0 and L2[4] == seq_len, the uint32 array in the
+ * interleaved form of bwt_occ_intv, n_sa == (seq_len + sa_intv) / sa_intv samples of the suffix array of text + sentinel at rows
+ * 0, sa_intv, 2 sa_intv ... with sa[0] == -1 -- and it is unique: every suffix of text + sentinel is distinct.
+ *
+ * bpsw_fmi_build_shape (host only) fills seq_len, bwt_size, n_sa and sa_intv: what the caller's arrays have to hold.
+ * bpsw_fmi_build writes bwt_size words to bwt and n_sa entries to sa and fills *out.  flags: BPSW_FMI_BUILD_LOAD -- the built index
+ * also becomes the device's loaded index, as after bpsw_fmi_load, with no second upload; bwt and sa may then be NULL (each on its
+ * own), and the index exists on the device only.  BPSW_FMI_BUILD_REF -- the pac also becomes the device's loaded reference, as after
+ * bpsw_ref_load.  Both follow those entries' rules: the index and the reference belong to the device, are seen by every context of
+ * it, must not be loaded while calls are in flight on it, and outlive bpsw_destroy.
+ *
+ * BPSW_ERR_ARG: NULL ctx, pac or out, l_pac < 1, sa_intv < 1 or not a power of two, unknown flag bits, bwt or sa NULL without
+ * BPSW_FMI_BUILD_LOAD.  BPSW_ERR_CAPACITY: bwt_cap below out->bwt_size or sa_cap below out->n_sa; the sizes are filled in *out and
+ * nothing is built.  BPSW_ERR_LIMIT: the working set does not fit the device memory that is free -- it is computed from seq_len
+ * before anything is allocated, about 105 bytes a suffix, and bpsw_last_error names the bytes needed and the
+ * bytes available -- or seq_len + 1 is above 2^32 (a round's sort key holds a group and a rank in 64 bits).  BPSW_ERR_DEVICE as
+ * elsewhere.  A failed call leaves a previously loaded index and reference as they were.
+ *
+ * Diagnostics (calling thread's most recent bpsw_fmi_build).  times, ms of wall clock: first keys and first sort, doubling rounds,
+ * BWT and counts and packing, sampling and copy-out (and the hand-over of LOAD / REF), the whole call.  stats: [0] doubling rounds
+ * run after the first sort, [1] suffixes still unresolved after the first sort, [2] the largest unresolved list over the rounds,
+ * [3] radix passes in all, [4] suffixes per workgroup in the sort (its tile), [5] peak device bytes, [6] bases in the first key,
+ * [7] 0.  bpsw_fmi_build_set_first_key, process-wide: 0 = the default (29, as many as fit the key), else the number of bases in the
+ * first sort key (clamped to 1 .. 29); the tests lower it to reach many rounds on small genomes.  bpsw_fmi_build_set_budget,
+ * process-wide: 0 = what the device has free, else the call pretends that this many bytes are. */
+#define BPSW_FMI_BUILD_LOAD 1
+#define BPSW_FMI_BUILD_REF 2
+typedef struct {
+  int64_t primary, L2[5], seq_len, bwt_size, n_sa;
+  int32_t sa_intv, pad_;
+} bpsw_fmi_shape_t;
+int bpsw_fmi_build_shape(int64_t l_pac, int32_t sa_intv, bpsw_fmi_shape_t *shape);
+int bpsw_fmi_build(bpsw_ctx_t *ctx, const uint8_t *pac, int64_t l_pac, int32_t sa_intv, int flags, uint32_t *bwt, int64_t bwt_cap,
+                   int64_t *sa, int64_t sa_cap, bpsw_fmi_shape_t *out);
+void bpsw_last_fmi_build_times(double ms[5]);
+void bpsw_last_fmi_build_stats(int64_t st[8]);
+void bpsw_fmi_build_set_first_key(int bases);
+void bpsw_fmi_build_set_budget(int64_t bytes);
+
 /* ---- worker2's tail: everything after the rescue ------------------------------------------
  *
  * memSamPeGroupRest (worker2/MemSamPe.scala:1390-1612 == mem_sam_pe after the rescue, native/bwamem_pair.c:385-452):
