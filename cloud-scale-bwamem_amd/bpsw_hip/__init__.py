@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "bpsw_align_fastq_bgzf_bam_se", "bpsw_align_fastq_bgzf_bam_pe",
     "bpsw_fmi_build_shape", "bpsw_fmi_build", "bpsw_last_fmi_build_times", "bpsw_last_fmi_build_stats", "bpsw_fmi_build_set_first_key",
     "bpsw_fmi_build_set_budget",
+    "bpsw_sam_header_ex", "bpsw_bam_header_ex", "bpsw_bam_sort", "bpsw_bam_sort_set_window", "bpsw_last_bam_sort_times",
 ]
 JNI_SYMBOLS = [
     "Java_cs_ucla_edu_bwaspark_jni_SWExtendFPGAJNI_swExtendFPGAJNI",
@@ -338,6 +339,15 @@ def _bind_seeding(lib):
         "bpsw_last_fmi_build_stats": ([C.c_void_p], None),
         "bpsw_fmi_build_set_first_key": ([C.c_int], None),
         "bpsw_fmi_build_set_budget": ([C.c_int64], None),
+        # a coordinate-sorted BAM and its .bai (bpsw_bam_sort.hip); the headers with a flags argument
+        "bpsw_sam_header_ex": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                C.POINTER(C.c_size_t)], C.c_int),
+        "bpsw_bam_header_ex": ([C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                C.POINTER(C.c_size_t)], C.c_int),
+        "bpsw_bam_sort": ([C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                           C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)], C.c_int),
+        "bpsw_bam_sort_set_window": ([C.c_int], C.c_int),
+        "bpsw_last_bam_sort_times": ([C.c_void_p], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name, None)
@@ -1585,23 +1595,26 @@ def _ctx_align_fastq_bgzf_bam_pe(self, opt: Opt, sopt, topt: "TailOpt", text1: b
             int(n.value), (int(consumed[0]), int(consumed[1])))
 
 
-def _header_call(entry: str, ctx, lens, names, extra: bytes, cap):
+HDR_COORDINATE = 1   # flags of sam_header / bam_header: "SO:coordinate" (BPSW_HDR_COORDINATE), for what bam_sort made
+
+
+def _header_call(entry: str, ctx, lens, names, extra: bytes, cap, flags: int = 0):
     lib = load_library() if ctx is None else ctx.lib
     ln = None if lens is None else np.ascontiguousarray(lens, np.int32)
     blob = None if names is None else b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
-    fn = getattr(lib, entry)
+    fn = getattr(lib, entry + "_ex")
     return _bytes_call(lib, entry, lambda buf, size, need: fn(None if ctx is None else ctx.h, 0 if ln is None else int(ln.shape[0]), _ptr(ln), blob,
-                                                             extra or None, len(extra or b""), buf, size, need), cap, 4096)
+                                                             extra or None, len(extra or b""), int(flags), buf, size, need), cap, 4096)
 
 
-def sam_header(lens=None, names=None, extra: bytes = b"", ctx: "Context | None" = None, cap: int | None = None) -> bytes:
-    """bpsw_sam_header: @HD, an @SQ per contig -- of the table loaded on ctx, or of lens / names without one -- then `extra` verbatim"""
-    return _header_call("bpsw_sam_header", ctx, lens, names, extra, cap)
+def sam_header(lens=None, names=None, extra: bytes = b"", ctx: "Context | None" = None, cap: int | None = None, flags: int = 0) -> bytes:
+    """bpsw_sam_header_ex: @HD, an @SQ per contig -- of the table loaded on ctx, or of lens / names without one -- then `extra` verbatim"""
+    return _header_call("bpsw_sam_header", ctx, lens, names, extra, cap, flags)
 
 
-def bam_header(lens=None, names=None, extra: bytes = b"", ctx: "Context | None" = None, cap: int | None = None) -> bytes:
-    """bpsw_bam_header: BAM\\1, that text and the reference list, in BGZF blocks"""
-    return _header_call("bpsw_bam_header", ctx, lens, names, extra, cap)
+def bam_header(lens=None, names=None, extra: bytes = b"", ctx: "Context | None" = None, cap: int | None = None, flags: int = 0) -> bytes:
+    """bpsw_bam_header_ex: BAM\\1, that text and the reference list, in BGZF blocks; flags=HDR_COORDINATE says SO:coordinate"""
+    return _header_call("bpsw_bam_header", ctx, lens, names, extra, cap, flags)
 
 
 def bam_eof(cap: int | None = None) -> bytes:
@@ -1627,6 +1640,53 @@ def last_bam_deflate_times():
     BAM entry; zeros when it ran without BAM_DEFLATE"""
     ms = (C.c_double * 4)()
     load_library().bpsw_last_bam_deflate_times(ms)
+    return tuple(ms)
+
+
+# ---- a coordinate-sorted BAM and its .bai (bpsw_bam_sort.hip) -------------------------------------------------------------------------
+class BamSortError(BpswError):
+    """a failed bpsw_bam_sort: rc is the library's code, needed its (*out_needed, *bai_needed), n_records what it counted"""
+
+    def __init__(self, msg, rc, needed=(0, 0), n_records=0):
+        super().__init__(msg)
+        self.rc, self.needed, self.n_records = rc, tuple(needed), n_records
+
+
+def _ctx_bam_sort(self, body: bytes, seg_off=None, flags: int = 0, file_off: int = 0, lens=None, cap: int | None = None,
+                  bai_cap: int | None = None):
+    """bpsw_bam_sort: the BAM entries' outputs, concatenated -> (the records sorted by coordinate in BGZF blocks, the .bai of a file in which
+    they begin at byte file_off, the number of records).  seg_off: where calls' outputs begin in `body`; lens: the contigs when the context
+    has no table.  Without cap / bai_cap the buffers are sized by a first call; with them one call is made, and a capacity refusal is a
+    BamSortError that carries `needed`."""
+    seg = None if seg_off is None else np.ascontiguousarray(seg_off, np.int64)
+    ln = None if lens is None else np.ascontiguousarray(lens, np.int32)
+    need, bneed, n = C.c_size_t(0), C.c_size_t(0), C.c_int64(0)
+    size, bsize = (0 if cap is None else int(cap)), (0 if bai_cap is None else int(bai_cap))
+    while True:
+        out, bai = np.full(size + 1, 0xee, np.uint8), np.full(bsize + 1, 0xee, np.uint8)
+        rc = self.lib.bpsw_bam_sort(self.h, body, len(body), _ptr(seg), 0 if seg is None else int(seg.shape[0]), 0 if ln is None else int(ln.shape[0]),
+                                    _ptr(ln), int(file_off), int(flags), _ptr(out), size, C.byref(need), _ptr(bai), bsize, C.byref(bneed),
+                                    C.byref(n))
+        if rc == -3 and cap is None and bai_cap is None and (need.value > size or bneed.value > bsize):
+            size, bsize = int(need.value), int(bneed.value)
+            continue
+        if rc != BPSW_OK:
+            raise BamSortError(f"bpsw_bam_sort failed ({rc}): {self.lib.bpsw_last_error().decode()}", rc, (int(need.value), int(bneed.value)),
+                               int(n.value))
+        assert out[size] == 0xee and bai[bsize] == 0xee   # (nothing is written past a capacity)
+        return out[: int(need.value)].tobytes(), bai[: int(bneed.value)].tobytes(), int(n.value)
+
+
+def bam_sort_set_window(n: int) -> int:
+    """bpsw_bam_sort_set_window: the bytes of the stream bam_walk_kernel holds in LDS, 64 .. 16384, 0 for the default; -> the return code"""
+    return int(load_library().bpsw_bam_sort_set_window(int(n)))
+
+
+def last_bam_sort_times():
+    """(inflate, walk, keys, sort, gather, frame or deflate, the index table's way back with the BAI's assembly, round trip) in ms of this
+    thread's last bam_sort"""
+    ms = (C.c_double * 8)()
+    load_library().bpsw_last_bam_sort_times(ms)
     return tuple(ms)
 
 
@@ -1728,8 +1788,9 @@ Context.align_fastq_bgzf_se = _ctx_align_fastq_bgzf_se
 Context.align_fastq_bgzf_pe = _ctx_align_fastq_bgzf_pe
 Context.align_fastq_bgzf_bam_se = _ctx_align_fastq_bgzf_bam_se
 Context.align_fastq_bgzf_bam_pe = _ctx_align_fastq_bgzf_bam_pe
-Context.sam_header = lambda self, extra=b"", cap=None: sam_header(extra=extra, ctx=self, cap=cap)
-Context.bam_header = lambda self, extra=b"", cap=None: bam_header(extra=extra, ctx=self, cap=cap)
+Context.sam_header = lambda self, extra=b"", cap=None, flags=0: sam_header(extra=extra, ctx=self, cap=cap, flags=flags)
+Context.bam_header = lambda self, extra=b"", cap=None, flags=0: bam_header(extra=extra, ctx=self, cap=cap, flags=flags)
+Context.bam_sort = _ctx_bam_sort
 Context.bam_eof = lambda self: bam_eof()
 Context.num_cu = lambda self: int(self.lib.bpsw_device_cus(self.h))   # compute units of the context's device
 

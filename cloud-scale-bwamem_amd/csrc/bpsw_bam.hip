@@ -1,7 +1,7 @@
 // bpsw_bam.hip -- alignments out as BAM: the records of a call's lines and the BGZF blocks around them, written on the device; the
 // header and the end-of-file block on the calling thread.  Behind the C ABI: bpsw_bam_se_batch, bpsw_bam_pe_batch,
 // bpsw_align_bam_se_batch, bpsw_align_bam_pe_batch (bpsw_align_fastq_bam_* are bpsw_fastq.hip's and end here), bpsw_sam_header,
-// bpsw_bam_header, bpsw_bam_eof, bpsw_bam_set_block_payload, bpsw_last_bam_times, bpsw_last_bam_deflate_times.
+// bpsw_bam_header (and the two with _ex), bpsw_bam_eof, bpsw_bam_set_block_payload, bpsw_last_bam_times, bpsw_last_bam_deflate_times.
 //
 // bam_on_device is a second writer beside text_on_device (bpsw_sam_se.hip): the entries hand it to sam_batch (bpsw_tail.cpp) through
 // the same pointer, it stages the same line table (stage_lines, with the mate assertion), and it has the text's shape -- a length per
@@ -27,6 +27,7 @@
 #include "bpsw_tail_internal.h"
 #include "bpsw_bam_core.h"
 #include "bpsw_deflate_core.h"
+#include "bpsw_wave.h"
 
 using namespace bpsw;
 namespace sc = bpsw::samcore;
@@ -86,20 +87,7 @@ __global__ __launch_bounds__(64) void bgzf_frame_kernel(const uint8_t* __restric
 }
 
 // ---- BPSW_BAM_DEFLATE: the payload as one dynamic-Huffman deflate block (bpsw_deflate_core.h) -----------------------------------------------
-// `n` bytes from src to dst, 16 bytes a lane where the destination allows: bgzf_frame_kernel's payload copy
-__device__ void copy_lines(const uint8_t* src, uint8_t* dst, int n, int lane) {
-  int head = (int)((16 - ((uintptr_t)dst & 15)) & 15);
-  if (head > n) head = n;
-  const int lines = (n - head) / 16, rest = head + 16 * lines;
-  if (lane < head) dst[lane] = src[lane];
-  for (int v = lane; v < lines; v += 64) {
-    uint4 x;
-    __builtin_memcpy(&x, src + head + 16 * v, 16);
-    *reinterpret_cast<uint4*>(dst + head + 16 * v) = x;
-  }
-  if (rest + lane < n) dst[rest + lane] = src[rest + lane];
-}
-
+// (copy_lines, bpsw_wave.h: `n` bytes from src to dst, 16 bytes a lane where the destination allows -- bgzf_frame_kernel's payload copy)
 // Block b of ceil(S / P), one wavefront: payload b compressed to wide[b stride ..), a place of its own that begins on a 16-byte line
 // (the words two lanes share are OR-ed into by both, and they must not be a neighbour's), sizes[b] = its framed bytes.  tok: two bytes of
 // scratch per byte of the stream.  The phases and what a lane does in each are bpsw_deflate_core.h's; the barriers are here.  When the
@@ -169,17 +157,11 @@ __global__ __launch_bounds__(64) void bgzf_pack_kernel(const uint8_t* __restrict
 }
 
 std::atomic<int> g_payload{0};
-int payload_bytes() {
-  const int p = g_payload.load(std::memory_order_relaxed);
-  return p > 0 ? p : bc::kBgzfMaxPayload;
-}
-size_t framed_size(size_t S, int P) { return S + (size_t)bc::kBgzfAround * ((S + (size_t)P - 1) / (size_t)P); }
 
 // bam_len_kernel, bam_write_kernel, bgzf_frame_kernel, tables, round trip
 thread_local double t_bam[5] = {0., 0., 0., 0., 0.};
 // bgzf_deflate_kernel, bgzf_pack_kernel, the size table's way back with the offsets' way out, the copy of the packed blocks
 thread_local double t_deflate[4] = {0., 0., 0., 0.};
-size_t deflate_stride(int P) { return ((size_t)P + bc::kBgzfAround + 15) & ~(size_t)15; }
 
 // ---- the calling thread's side: the table, a payload framed without a device, the header ----------------------------------------------
 const uint32_t* host_table() {
@@ -221,8 +203,8 @@ int contigs_of(const char* who, bpsw_ctx_t* c, int32_t n_seqs, const int32_t* le
     if (out->name[k].empty()) out->name[k] = "ctg" + std::to_string(k + 1);  // (put_contig's rule)
   return BPSW_OK;
 }
-std::string header_text(const Contigs& t, const char* extra, size_t extra_bytes) {
-  std::string s = "@HD\tVN:1.6\tSO:unsorted\n";
+std::string header_text(const Contigs& t, const char* extra, size_t extra_bytes, int flags) {
+  std::string s = (flags & BPSW_HDR_COORDINATE) ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unsorted\n";
   for (size_t k = 0; k < t.name.size(); ++k) s += "@SQ\tSN:" + t.name[k] + "\tLN:" + std::to_string(t.len[k]) + "\n";
   if (extra && extra_bytes) s.append(extra, extra_bytes);
   return s;
@@ -264,11 +246,11 @@ int64_t* own_offsets(long long n_reads) {
 int deflate_on_device(bpsw_ctx* c, const std::string& w, const sc::SamBatch& B, int n_lines, const std::vector<long long>& rec_off, size_t S, int P,
                       size_t blocks, char* out, size_t cap, size_t* total_out, double times[5], double t1) {
   const dim3 grid((unsigned)((n_lines + 63) / 64));
-  const size_t stride = deflate_stride(P);
+  const size_t stride = bgzf_deflate_stride(P);
   StageIn io;
   const int i_off = io.add(rec_off.data(), 8 * ((size_t)n_lines + 1));
   StageOut fr;
-  const int r_out = fr.add(framed_size(S, P)), r_status = fr.add(16), r_sizes = fr.add(4 * blocks);
+  const int r_out = fr.add(bgzf_framed_size(S, P)), r_status = fr.add(16), r_sizes = fr.add(4 * blocks);
   StageLayout dev;
   dev.add(fr.total());
   const size_t o_stream = dev.add(S), o_wide = dev.add(blocks * stride, 256), o_tok = dev.add(2 * S);
@@ -282,9 +264,8 @@ int deflate_on_device(bpsw_ctx* c, const std::string& w, const sc::SamBatch& B, 
                      fr.dev<int>(r_status));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev[7], c->stream));
-  hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)blocks), dim3(64), 0, c->stream, (const uint8_t*)(base + o_stream), (long long)S, P,
-                     (uint16_t*)(base + o_tok), base + o_wide, (long long)stride, fr.dev<uint32_t>(r_sizes));
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_bgzf_deflate(c->stream, base + o_stream, (long long)S, P, blocks, (uint16_t*)(base + o_tok), base + o_wide,
+                              fr.dev<uint32_t>(r_sizes)));
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
   const size_t back = fr.total() - fr.at[r_status];  // (the status and the sizes lie together)
   HIP_TRY(hipMemcpyAsync(fr.h + fr.at[r_status], fr.d + fr.at[r_status], back, hipMemcpyDeviceToHost, c->stream));
@@ -299,13 +280,9 @@ int deflate_on_device(bpsw_ctx* c, const std::string& w, const sc::SamBatch& B, 
   (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
   t_deflate[2] = ms;
   if (*fr.host<int>(r_status)) return fail(BPSW_ERR_DEVICE, w + ": a record's bytes differ in number from its length (bam_rec_write's status)");
-  std::vector<long long> off(blocks + 1, 0);
-  const uint32_t* sz = fr.host<uint32_t>(r_sizes);
-  for (size_t b = 0; b < blocks; ++b) {
-    const size_t n = std::min(S - b * (size_t)P, (size_t)P);
-    if (sz[b] < 28 || sz[b] > n + bc::kBgzfAround) return fail(BPSW_ERR_DEVICE, w + ": a block came back with a size no block has");
-    off[b + 1] = off[b] + sz[b];
-  }
+  std::vector<long long> off;
+  if (!bgzf_block_offsets(fr.host<uint32_t>(r_sizes), S, P, blocks, &off))
+    return fail(BPSW_ERR_DEVICE, w + ": a block came back with a size no block has");
   const size_t total = (size_t)off[blocks];
   *total_out = total;
   if (!out || total > cap) { times[4] = wall_ms() - t1; return BPSW_OK; }  // (the caller reports the capacity)
@@ -314,9 +291,7 @@ int deflate_on_device(bpsw_ctx* c, const std::string& w, const sc::SamBatch& B, 
   HIP_TRY(po.stage(c->h_stage_in, c->d_sw_out, c->stream));
   t_deflate[2] += wall_ms() - t2;
   HIP_TRY(hipEventRecord(c->ev[6], c->stream));
-  hipLaunchKernelGGL(bgzf_pack_kernel, dim3((unsigned)blocks), dim3(64), 0, c->stream, (const uint8_t*)(base + o_wide), (long long)stride,
-                     po.dev<long long>(p_off), fr.dev<uint8_t>(r_out));
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_bgzf_pack(c->stream, base + o_wide, P, po.dev<long long>(p_off), blocks, fr.dev<uint8_t>(r_out)));
   HIP_TRY(hipEventRecord(c->ev[7], c->stream));
   HIP_TRY(hipMemcpyAsync(fr.h + fr.at[r_out], fr.d + fr.at[r_out], total, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -366,8 +341,8 @@ int bam_device(bool deflate, bpsw_ctx* c, const char* who, const BnsView& bns, c
   }
   for (int r = 0; r <= n; ++r) out_off[r] = (int64_t)rec_off[(size_t)read_first[(size_t)r]];
   const size_t S = (size_t)rec_off[(size_t)n_lines];
-  const int P = payload_bytes();
-  const size_t blocks = (S + (size_t)P - 1) / (size_t)P, total = framed_size(S, P);
+  const int P = bam_payload_bytes();
+  const size_t blocks = (S + (size_t)P - 1) / (size_t)P, total = bgzf_framed_size(S, P);
   *total_out = total;
   times[0] = ms; times[1] = times[2] = 0.; times[3] = t1 - t0;
   if (deflate) {
@@ -391,9 +366,7 @@ int bam_device(bool deflate, bpsw_ctx* c, const char* who, const BnsView& bns, c
   hipLaunchKernelGGL(bam_write_kernel, grid, dim3(64), 0, c->stream, B, n_lines, io.dev<long long>(i_off), stream, fr.dev<int>(r_status));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev[7], c->stream));
-  hipLaunchKernelGGL(bgzf_frame_kernel, dim3((unsigned)blocks), dim3(64), 0, c->stream, (const uint8_t*)stream, (long long)S, P,
-                     fr.dev<uint8_t>(r_out));
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_bgzf_frame(c->stream, (const uint8_t*)stream, (long long)S, P, blocks, fr.dev<uint8_t>(r_out)));
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
   HIP_TRY(fr.fetch(c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -413,6 +386,42 @@ int bam_deflate_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, cons
 }
 
 }  // namespace
+
+// ---- the blocks of a stream that lies on the device: what the writers above run behind their records, and bpsw_bam_sort.hip behind its
+// sorted stream (the declarations and what they promise: bpsw_internal.h)
+int bpsw::bam_payload_bytes() {
+  const int p = g_payload.load(std::memory_order_relaxed);
+  return p > 0 ? p : bc::kBgzfMaxPayload;
+}
+size_t bpsw::bgzf_framed_size(size_t S, int P) { return S + (size_t)bc::kBgzfAround * ((S + (size_t)P - 1) / (size_t)P); }
+size_t bpsw::bgzf_deflate_stride(int P) { return ((size_t)P + bc::kBgzfAround + 15) & ~(size_t)15; }
+
+hipError_t bpsw::launch_bgzf_frame(hipStream_t s, const uint8_t* d_stream, long long S, int P, size_t blocks, uint8_t* d_out) {
+  if (!blocks) return hipSuccess;
+  hipLaunchKernelGGL(bgzf_frame_kernel, dim3((unsigned)blocks), dim3(64), 0, s, d_stream, S, P, d_out);
+  return hipGetLastError();
+}
+hipError_t bpsw::launch_bgzf_deflate(hipStream_t s, const uint8_t* d_stream, long long S, int P, size_t blocks, uint16_t* d_tok, uint8_t* d_wide,
+                                     uint32_t* d_sizes) {
+  if (!blocks) return hipSuccess;
+  hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)blocks), dim3(64), 0, s, d_stream, S, P, d_tok, d_wide, (long long)bgzf_deflate_stride(P),
+                     d_sizes);
+  return hipGetLastError();
+}
+bool bpsw::bgzf_block_offsets(const uint32_t* sizes, size_t S, int P, size_t blocks, std::vector<long long>* off) {
+  off->assign(blocks + 1, 0);
+  for (size_t b = 0; b < blocks; ++b) {
+    const size_t n = std::min(S - b * (size_t)P, (size_t)P);
+    if (sizes[b] < 28 || sizes[b] > n + bc::kBgzfAround) return false;
+    (*off)[b + 1] = (*off)[b] + sizes[b];
+  }
+  return true;
+}
+hipError_t bpsw::launch_bgzf_pack(hipStream_t s, const uint8_t* d_wide, int P, const long long* d_off, size_t blocks, uint8_t* d_out) {
+  if (!blocks) return hipSuccess;
+  hipLaunchKernelGGL(bgzf_pack_kernel, dim3((unsigned)blocks), dim3(64), 0, s, d_wide, (long long)bgzf_deflate_stride(P), d_off, d_out);
+  return hipGetLastError();
+}
 
 int bpsw::bam_on_device(bpsw_ctx* c, const char* who, const BnsView& bns, const bpsw_tail_opt_t& t, const TextReads& g, const SamLines& sl,
                         char* out, size_t cap, int64_t* out_off, size_t* total_out, double times[5]) {
@@ -457,21 +466,28 @@ int bpsw_align_bam_pe_batch(bpsw_ctx_t* c, const bpsw_opt_t* opt, const bpsw_see
   return align_pe(c, opt, sopt, topt, g, pes0, zdrop_mode, w1_flags, rescue_mode, flags, pe_tail, out, cap, none, out_needed, out_pes);
 }
 
-int bpsw_sam_header(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const char* names, const char* extra, size_t extra_bytes, char* out,
-                    size_t cap, size_t* out_needed) {
+int bpsw_sam_header_ex(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const char* names, const char* extra, size_t extra_bytes, int flags,
+                       char* out, size_t cap, size_t* out_needed) {
+  if (flags & ~BPSW_HDR_COORDINATE) return fail(BPSW_ERR_ARG, "sam_header: unknown flag");
   Contigs t;
   const int rc = contigs_of("sam_header", c, n_seqs, len, names, &t);
   if (rc != BPSW_OK) return rc;
-  const std::string s = header_text(t, extra, extra_bytes);
+  const std::string s = header_text(t, extra, extra_bytes, flags);
   return hand_out("sam_header", s.data(), s.size(), out, cap, out_needed);
 }
 
-int bpsw_bam_header(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const char* names, const char* extra, size_t extra_bytes, char* out,
+int bpsw_sam_header(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const char* names, const char* extra, size_t extra_bytes, char* out,
                     size_t cap, size_t* out_needed) {
+  return bpsw_sam_header_ex(c, n_seqs, len, names, extra, extra_bytes, 0, out, cap, out_needed);
+}
+
+int bpsw_bam_header_ex(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const char* names, const char* extra, size_t extra_bytes, int flags,
+                       char* out, size_t cap, size_t* out_needed) {
+  if (flags & ~BPSW_HDR_COORDINATE) return fail(BPSW_ERR_ARG, "bam_header: unknown flag");
   Contigs t;
   const int rc = contigs_of("bam_header", c, n_seqs, len, names, &t);
   if (rc != BPSW_OK) return rc;
-  const std::string text = header_text(t, extra, extra_bytes);
+  const std::string text = header_text(t, extra, extra_bytes, flags);
   if (text.size() > 0x7fffffffull) return fail(BPSW_ERR_LIMIT, "bam_header: a header text of 2^31 bytes or more");
   std::string s("BAM\1", 4);
   append_u32(s, (uint32_t)text.size());
@@ -482,12 +498,17 @@ int bpsw_bam_header(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const cha
     s.append(t.name[k].c_str(), t.name[k].size() + 1);
     append_u32(s, (uint32_t)t.len[k]);
   }
-  const int P = payload_bytes();
-  const size_t total = framed_size(s.size(), P);
+  const int P = bam_payload_bytes();
+  const size_t total = bgzf_framed_size(s.size(), P);
   if (out_needed) *out_needed = total;
   if (!out || total > cap) return fail(BPSW_ERR_CAPACITY, "bam_header: buffer too small (see *out_needed)");
   frame_host(s, P, out);
   return BPSW_OK;
+}
+
+int bpsw_bam_header(bpsw_ctx_t* c, int32_t n_seqs, const int32_t* len, const char* names, const char* extra, size_t extra_bytes, char* out,
+                    size_t cap, size_t* out_needed) {
+  return bpsw_bam_header_ex(c, n_seqs, len, names, extra, extra_bytes, 0, out, cap, out_needed);
 }
 
 int bpsw_bam_eof(char* out, size_t cap, size_t* out_needed) {

@@ -4,7 +4,8 @@
 // item per lane.  The construction is prefix doubling over a radix sort, and only unresolved suffixes stay in play:
 //   index_first_key_kernel   round 0's list: every suffix with its first key
 //   index_round_key_kernel   a later round's list: key = group << rank_bits | rank[suffix + h], gathered before any rank is written
-//   the sort                 stable LSD radix sort of (key, suffix), eight bits a pass, only as many passes as the keys have bits:
+//   the sort                 stable LSD radix sort of (key, suffix), eight bits a pass, only as many passes as the keys have bits
+//                            (radix_sort_pairs, declared in bpsw_internal.h: bpsw_bam_sort.hip sorts its records with it too):
 //     sort_hist_kernel         one workgroup per tile of 4 096: the tile's digit counts -> table[digit * tiles + tile]
 //     scan_exclusive_i64       (bpsw_scan.hip) over the whole table: where every tile's every digit begins
 //     sort_scatter_kernel      one workgroup per tile, 256 entries a step in list order: a lane's place is its digit's base, plus the
@@ -166,21 +167,11 @@ thread_local int64_t t_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 // (K, V)[from] sorted by the low `bits` of the keys; -> the buffer the sorted list is in
 int sort_list(hipStream_t s, uint8_t* D, const Arena& A, int from, i64 M, int bits, int scan_tile, hipError_t* err) {
-  const i64 tiles = (M + xc::kSortTile - 1) / xc::kSortTile;
-  i64* table = (i64*)(D + A.table);
-  int at = from;
-  *err = hipSuccess;
-  for (int p = 0; p < xc::radix_passes(bits) && M > 1; ++p, at ^= 1) {
-    const u64* K = (const u64*)(D + A.key[at]);
-    const i64* V = (const i64*)(D + A.val[at]);
-    hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)tiles), dim3(xc::kSortThreads), 0, s, K, M, p * xc::kRadixBits, tiles, table);
-    if ((*err = hipGetLastError()) != hipSuccess) return at;
-    if ((*err = scan_exclusive_i64(s, table, 1, tiles * xc::kRadix, scan_tile, (i64*)(D + A.sums))) != hipSuccess) return at;
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3((unsigned)tiles), dim3(xc::kSortThreads), 0, s, K, V, M, p * xc::kRadixBits, tiles,
-                       (const i64*)table, (u64*)(D + A.key[at ^ 1]), (i64*)(D + A.val[at ^ 1]));
-    if ((*err = hipGetLastError()) != hipSuccess) return at;
-    ++t_stats[3];
-  }
+  u64* key[2] = {(u64*)(D + A.key[0]), (u64*)(D + A.key[1])};
+  i64* val[2] = {(i64*)(D + A.val[0]), (i64*)(D + A.val[1])};
+  int passes = 0;
+  const int at = radix_sort_pairs(s, key, val, from, M, bits, (i64*)(D + A.table), scan_tile, (i64*)(D + A.sums), &passes, err);
+  t_stats[3] += passes;
   return at;
 }
 
@@ -195,6 +186,28 @@ int shape_fill(int64_t l_pac, int32_t sa_intv, bpsw_fmi_shape_t* out) {
 }
 
 }  // namespace
+
+int bpsw::sort_tile_items() { return xc::kSortTile; }
+
+int bpsw::radix_sort_pairs(hipStream_t s, unsigned long long* const key[2], long long* const val[2], int from, long long M, int bits,
+                           long long* table, int scan_tile, long long* sums, int* passes, hipError_t* err) {
+  const i64 tiles = (M + xc::kSortTile - 1) / xc::kSortTile;
+  int at = from;
+  *err = hipSuccess;
+  *passes = 0;
+  for (int p = 0; p < xc::radix_passes(bits) && M > 1; ++p, at ^= 1) {
+    const u64* K = key[at];
+    const i64* V = val[at];
+    hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)tiles), dim3(xc::kSortThreads), 0, s, K, M, p * xc::kRadixBits, tiles, table);
+    if ((*err = hipGetLastError()) != hipSuccess) return at;
+    if ((*err = scan_exclusive_i64(s, table, 1, tiles * xc::kRadix, scan_tile, sums)) != hipSuccess) return at;
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3((unsigned)tiles), dim3(xc::kSortThreads), 0, s, K, V, M, p * xc::kRadixBits, tiles,
+                       (const i64*)table, key[at ^ 1], val[at ^ 1]);
+    if ((*err = hipGetLastError()) != hipSuccess) return at;
+    ++*passes;
+  }
+  return at;
+}
 
 extern "C" {
 

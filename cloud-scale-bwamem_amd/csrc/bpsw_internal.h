@@ -575,6 +575,31 @@ int scan_tile_items();
 long long scan_tiles(long long n, int tile);
 hipError_t scan_exclusive_i64(hipStream_t s, long long* data, int cols, long long n, int tile, long long* tile_sums);
 
+// ---- a stable sort of (key, value) pairs on the device (bpsw_index.hip) ------------------------------------------------------------------
+// LSD radix sort, eight bits a pass over the low `bits` bits of the keys (none when M < 2): sort_hist_kernel, scan_exclusive_i64 and
+// sort_scatter_kernel per pass, one workgroup per tile of sort_tile_items() pairs.  (key, val)[from] holds the M pairs, the other pair of
+// buffers is the passes' second place; -> the index of the pair that holds the sorted list.  table: sort_table_items(M) values;
+// sums: scan_tiles(sort_table_items(M), scan_tile) values; *passes: the passes run; *err: the first failing launch's error.
+int sort_tile_items();
+inline long long sort_table_items(long long M) { return (M + sort_tile_items() - 1) / sort_tile_items() * 256 + 1; }
+int radix_sort_pairs(hipStream_t s, unsigned long long* const key[2], long long* const val[2], int from, long long M, int bits,
+                     long long* table, int scan_tile, long long* sums, int* passes, hipError_t* err);
+
+// ---- BGZF blocks over a stream that lies on the device (bpsw_bam.hip) -----------------------------------------------------------------
+// The stream's S bytes are cut every P bytes into `blocks` payloads.  launch_bgzf_frame: every payload stored, block b at
+// d_out + b (P + 31).  launch_bgzf_deflate: every payload compressed (or stored when that is not smaller) at d_wide + b stride
+// (bgzf_deflate_stride(P), d_wide on a 16-byte line), its framed size in d_sizes[b]; d_tok: two bytes of scratch per stream byte.
+// bgzf_block_offsets: the sizes that came back, checked and summed -> off[blocks + 1] (false: a size no block has).
+// launch_bgzf_pack: block b from its place in d_wide to d_out + d_off[b].
+int bam_payload_bytes();  // P: 65280, or what bpsw_bam_set_block_payload set
+size_t bgzf_framed_size(size_t S, int P);
+size_t bgzf_deflate_stride(int P);
+hipError_t launch_bgzf_frame(hipStream_t s, const uint8_t* d_stream, long long S, int P, size_t blocks, uint8_t* d_out);
+hipError_t launch_bgzf_deflate(hipStream_t s, const uint8_t* d_stream, long long S, int P, size_t blocks, uint16_t* d_tok, uint8_t* d_wide,
+                               uint32_t* d_sizes);
+bool bgzf_block_offsets(const uint32_t* sizes, size_t S, int P, size_t blocks, std::vector<long long>* off);
+hipError_t launch_bgzf_pack(hipStream_t s, const uint8_t* d_wide, int P, const long long* d_off, size_t blocks, uint8_t* d_out);
+
 // ---- an index that is on the device already (bpsw_seed.hip; bpsw_index.hip builds one) -------------------------------------------------
 // bwt (bwt_size words and 64 zero bytes behind them) and sa become the loaded index of c's device exactly as after bpsw_fmi_load, with
 // no copy: the buffers change hands, and the caller is left with the previous index's, to free.  Caller holds c->mu (ContextEntry).

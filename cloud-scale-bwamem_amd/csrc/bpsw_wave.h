@@ -74,4 +74,19 @@ __device__ __forceinline__ int wave_max(int v) { return __builtin_amdgcn_readlan
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// `n` bytes from src to dst by the 64 lanes of a wavefront: single bytes up to the first 16-byte line of the destination, whole lines
+// 16 bytes a lane (the source is wherever it is), single bytes behind the last line
+__device__ inline void copy_lines(const uint8_t* src, uint8_t* dst, int n, int lane) {
+  int head = (int)((16 - ((uintptr_t)dst & 15)) & 15);
+  if (head > n) head = n;
+  const int lines = (n - head) / 16, rest = head + 16 * lines;
+  if (lane < head) dst[lane] = src[lane];
+  for (int v = lane; v < lines; v += 64) {
+    uint4 x;
+    __builtin_memcpy(&x, src + head + 16 * v, 16);
+    *reinterpret_cast<uint4*>(dst + head + 16 * v) = x;
+  }
+  if (rest + lane < n) dst[rest + lane] = src[rest + lane];
+}
+
 }  // namespace bpsw

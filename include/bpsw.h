@@ -779,7 +779,7 @@ void bpsw_last_fastq_times(double ms[5]);
  * small (nothing is written then: the size is known before the records are); an empty batch is *out_needed == 0.  flags must be 0
  * (BPSW_ERR_ARG otherwise); the FASTQ twins keep fastq_flags, and w1_flags pass through.  A read name of more than 254 bytes cannot be
  * a BAM record: BPSW_ERR_LIMIT, nothing written.  Everything else -- arguments, refusals, out_regs, out_pes, n_reads, consumed,
- * bpsw_last_tail_times -- is the twin's.  Not here: sorting, an index.
+ * bpsw_last_tail_times -- is the twin's.  Sorting and an index: bpsw_bam_sort, below.
  *
  * flags = BPSW_BAM_DEFLATE (all six entries; any other bit is still BPSW_ERR_ARG): every member holds one dynamic-Huffman deflate block
  * with LZ77 matches (RFC 1951, BTYPE 10), made on the device by one wavefront a block (csrc/bpsw_deflate_core.h), unless that would not
@@ -812,7 +812,15 @@ int bpsw_align_fastq_bam_pe(bpsw_ctx_t *ctx, const bpsw_opt_t *opt, const bpsw_s
  * arguments: len[n_seqs] and names as bpsw_bns_load takes them (NULL: no names).  A contig without a name is "ctg<rid + 1>", as in the
  * lines.  bpsw_bam_header: "BAM\1", l_text, that text, n_ref and per contig l_name, the name with its NUL and l_ref, framed as BGZF
  * blocks like the records.  bpsw_bam_eof: the 28-byte end-of-file block of the specification.  All three: BPSW_ERR_CAPACITY with
- * *out_needed set, and nothing written, when cap is too small. */
+ * *out_needed set, and nothing written, when cap is too small.
+ * The two with _ex take flags behind extra_bytes: BPSW_HDR_COORDINATE writes "SO:coordinate" where the plain entries write
+ * "SO:unsorted" (for what bpsw_bam_sort made); 0 gives the plain entries' bytes, which are calls of these with 0; any other bit is
+ * BPSW_ERR_ARG. */
+#define BPSW_HDR_COORDINATE 1
+int bpsw_sam_header_ex(bpsw_ctx_t *ctx, int32_t n_seqs, const int32_t *len, const char *names, const char *extra, size_t extra_bytes,
+                       int flags, char *out, size_t cap, size_t *out_needed);
+int bpsw_bam_header_ex(bpsw_ctx_t *ctx, int32_t n_seqs, const int32_t *len, const char *names, const char *extra, size_t extra_bytes,
+                       int flags, char *out, size_t cap, size_t *out_needed);
 int bpsw_sam_header(bpsw_ctx_t *ctx, int32_t n_seqs, const int32_t *len, const char *names, const char *extra, size_t extra_bytes, char *out,
                     size_t cap, size_t *out_needed);
 int bpsw_bam_header(bpsw_ctx_t *ctx, int32_t n_seqs, const int32_t *len, const char *names, const char *extra, size_t extra_bytes, char *out,
@@ -828,6 +836,51 @@ void bpsw_last_bam_times(double ms[5]);
  * was refused), the blocks' size table back to the host with its sum and the offsets' way out, the copy of the packed blocks.  With the
  * flag, slot 2 of bpsw_last_bam_times (bgzf_frame_kernel) is 0. */
 void bpsw_last_bam_deflate_times(double ms[4]);
+
+/* ---- a coordinate-sorted BAM and its .bai: the records sorted on the device (bpsw_bam_sort.hip) -----------------------------------------
+ * in[0, in_bytes): what the BAM entries return, concatenated -- a whole number of BGZF blocks (stored or deflated in any mix; whatever
+ * bpsw_bgzf_inflate accepts, under its rules and refusals; empty blocks such as bpsw_bam_eof's may stand anywhere) whose inflated bytes
+ * are a whole number of BAM records.  A header is not accepted: the caller has it and puts it in front.
+ * seg_off[n_seg]: optional.  Offsets into `in`, ascending, each on a block boundary (0 and in_bytes are boundaries), at which a record
+ * is known to begin -- where the calls' outputs begin, or end.  They cut the input into n_seg + 1 segments: segment 0 from 0 to
+ * seg_off[0], segment k from seg_off[k - 1] to seg_off[k], the last one to in_bytes.  The one serial step, following block_size from
+ * record to record, then runs once per segment, side by side.  n_seg == 0: the whole input is one segment.  Two equal offsets, or a
+ * first one of 0, or a last one of in_bytes, are an empty segment.  An offset that is no block boundary, or a segment whose chain of
+ * block_size fields does not end exactly on the segment's end, is BPSW_ERR_ARG; the text names the segment and the offset in the
+ * inflated stream.
+ * The contigs: len[n_seqs] when len is given; with len NULL those of the table loaded with bpsw_bns_load on ctx's device (n_seqs is
+ * ignored then; no table and n_seqs != 0 is BPSW_ERR_ARG).  They must be the header's.
+ *
+ * The order -- this library's definition of SO:coordinate, which the specification leaves open beyond (refID, pos) with the reads
+ * without a coordinate last: the key is (refID, pos + 1, flag bit 0x10), a refID of -1 counting as n_seqs; records of equal keys keep
+ * the order they have in `in` (the sort is stable).  So at one position the forward strand stands before the reverse strand, and an
+ * input that is sorted comes back as it is.  The records' bytes are not changed (the bin field included).
+ *
+ * out: the sorted stream cut every P bytes (bpsw_bam_set_block_payload) and framed as the BAM entries frame theirs -- stored, or with
+ * flags = BPSW_BAM_DEFLATE compressed on the device -- so that  bpsw_bam_header_ex(BPSW_HDR_COORDINATE) || out || bpsw_bam_eof  is a
+ * sorted BAM file.  bai: its index (specification 5.2) for a file in which `out` begins at byte file_off (the header's size): per
+ * contig the bins in ascending order with their chunks in file order -- a chunk is a maximal run of consecutive records with the same
+ * bin, the bin recomputed from pos and the CIGAR; then the pseudo-bin 37450; the linear index (a 16 Kib window's entry is the start of
+ * the first record that overlaps it, a window that none overlaps takes the next one's, n_intv is the last overlapped window + 1);
+ * a contig without records has n_bin = n_intv = 0; n_no_coor at the end.  *n_records: the records.
+ * Capacity: as for the BAM entries, for both buffers together.  When cap or bai_cap is too small (or the buffer NULL) the call does
+ * all its work, writes nothing to either and returns BPSW_ERR_CAPACITY with *out_needed and *bai_needed exact; a repeat at those
+ * sizes succeeds.
+ * Refusals, with the first offending record named by its index in the input stream: in_bytes or the inflated size at 2^31 or above, or
+ * a contig longer than 2^29 (a BAI cannot bin it): BPSW_ERR_LIMIT.  A refID outside [-1, n_seqs); a pos below -1, or at or above its
+ * contig's length (a record with refID -1 has no contig: its pos is -1); a block_size below 32 + l_read_name + 4 n_cigar_op +
+ * ceil(l_seq / 2) + l_seq: BPSW_ERR_ARG.  Not here: merging the sorted outputs of several calls, CSI, other orders. */
+int bpsw_bam_sort(bpsw_ctx_t *ctx, const char *in, size_t in_bytes, const int64_t *seg_off, int64_t n_seg, int32_t n_seqs,
+                  const int32_t *len, int64_t file_off, int flags, char *out, size_t cap, size_t *out_needed, char *bai, size_t bai_cap,
+                  size_t *bai_needed, int64_t *n_records);
+/* The bytes of the stream a wavefront of bam_walk_kernel holds in LDS, process-wide: 64 .. 16384, rounded up to a multiple of 16;
+ * 0 = the default, 4096.  Anything else is BPSW_ERR_ARG and changes nothing.  The counterpart of bpsw_bam_set_block_payload: tests put
+ * the window's edge inside every part of a record with it. */
+int bpsw_bam_sort_set_window(int bytes);
+/* Diagnostics, of the calling thread's most recent bpsw_bam_sort (ms): bgzf_inflate_kernel, bam_walk_kernel (both passes and the scan
+ * between them), bam_key_kernel, the radix sort, the lengths' gather with its scan and bam_gather_kernel, bgzf_frame_kernel or
+ * bgzf_deflate_kernel with bgzf_pack_kernel, the index table's way back with the BAI's assembly, the call's round trip. */
+void bpsw_last_bam_sort_times(double ms[8]);
 
 /* ---- FASTQ in as BGZF: the blocks inflated on the device, parsed from there (bpsw_bgzf_in.hip, bpsw_fastq.hip) ------------------------
  * Accepted: a sequence of BGZF blocks -- gzip members that begin 1f 8b 08 04 and whose extra field has the subfield BC (SLEN 2) with
